@@ -1,7 +1,11 @@
 """Headline benchmark (driver contract): FourCastNet AFNO batch-DP inference samples/s on N
 MI355X GPUs (one process per GPU, RCCL all-gather of the outputs over xGMI, hipGraph-captured
-per-step forward), plus the rfft2 / irfft2 720x1440 fp32 single-op latency (us) and the FNO
-SpectralConv2d block (BASELINE config 3) as extra keys.
+per-step forward).  A plain run sets up, warms up, times the steps and prints the result line;
+``--full`` adds, as extra keys, the rfft2 / irfft2 720x1440 fp32 single-op latency (us), the FNO
+SpectralConv2d block (BASELINE config 3), the library-native export and the other precision.
+``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/output.npy`` (float32; a
+fixed seeded sample of the 2.65 GB full-size output): weights and inputs are seeded, so two builds
+of the library can be compared output for output.
 
 Metric/config from BASELINE.json: "rfft2 720x1440 us + FourCastNet-FNO samples/sec at 1/2/4/8
 MI355X"; FourCastNet AFNO (720x1440, patch 8, embed 768, depth 12, 8 AFNO blocks), batch 32
@@ -13,13 +17,13 @@ Headline engine = the reference's workflow (/root/reference/README.md:57-75,
 + Einsum / LayerNorm / MatMul ...), built into an engine whose build-time graph optimizer maps the
 stock patterns onto the hand kernels (every rewrite verified on the device), serialized,
 deserialized, and replayed as one hipGraph per step.  The library-native export (com.amd.dft
-nodes) is timed as the extra key ``native_export_samples_per_s``.
+nodes) is timed as the extra key ``native_export_samples_per_s`` (``--full``).
 
 Headline precision = fp32, the reference's only precision (its plugins accept kFLOAT only,
 /root/reference/src/dft_plugins/dft_plugins.cpp:101-102): fp32 activations / residual stream /
 spectra / FFTs; GEMMs as 3-product bf16 splits with fp32 accumulation (bf16x3: ~5e-6 relative
 error per GEMM, vs ~3e-7 for fp32 FMA and ~1e-3 for TF32).  The bf16 model (bf16 activations,
-bf16 MFMA) is reported as ``bf16_samples_per_s``.  Every timed step runs the full forward (all
+bf16 MFMA) is reported as ``bf16_samples_per_s`` (``--full``).  Every timed step runs the full forward (all
 12 blocks) and the output all-gather; K steps are bracketed by barrier + synchronize, and the
 max over ranks is reported.
 
@@ -30,6 +34,7 @@ global B=32 over 8 GPUs).  ``--gather-dtype bf16`` gathers a bf16 copy of an fp3
 (channels, algorithm / protocol lines from its INIT/TUNING log, parsed by ``rccl_choices``).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16] [--global-batch G]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -197,8 +202,9 @@ def time_fno_block_us(rounds: int = 5) -> dict:
                 "spectral_conv2d_720x1440_bf16_us": _graph_us(lambda: blk.spectral(x), 20, rounds)}
 
 
-def run_steps(runner, steps: int, warmup: int, world: int, dev, cuda: bool) -> float:
-    """Seconds for `steps` timed steps (after `warmup`), max over ranks."""
+def run_steps(runner, steps: int, warmup: int, world: int, dev, cuda: bool):
+    """(seconds for `steps` timed steps (after `warmup`), max over ranks; what the last timed step
+    returned to its caller: the gathered buffer, or the local output without a gather)."""
 
     def sync():
         if cuda:
@@ -216,9 +222,10 @@ def run_steps(runner, steps: int, warmup: int, world: int, dev, cuda: bool) -> f
     sync()
     if getattr(runner, "gather", False) and hasattr(runner, "time_comm"):
         runner.time_comm(True)  # event pair around each timed gather (comm-stream busy time)
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        runner.step()
+        last = runner.step()
     runner.drain()
     sync()
     barrier()
@@ -228,7 +235,34 @@ def run_steps(runner, steps: int, warmup: int, world: int, dev, cuda: bool) -> f
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if cuda else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed
+    return elapsed, last
+
+
+DUMP_WHOLE_BYTES = 48 << 20  # an output up to this size is written whole (the limit is 64 MB in all)
+DUMP_SAMPLE = 1 << 22        # elements sampled from a larger one (16 MB as float32)
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> dict:
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy`` (float32; float64 stays float64).  An output
+    larger than DUMP_WHOLE_BYTES is written as DUMP_SAMPLE of its elements in flat (row-major) order,
+    at positions drawn once with replacement from a CPU generator seeded with 0: the same positions
+    in every run and every build, so two dumps compare element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    note = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        sampled = t.numel() * (8 if dt == torch.float64 else 4) > DUMP_WHOLE_BYTES
+        if sampled:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g, dtype=torch.int64)
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        note[name] = {"shape": list(arr.shape), "dtype": str(arr.dtype), "sampled": sampled}
+    return note
 
 
 class _EngineFn:
@@ -275,7 +309,15 @@ def build_runner(cfg, dtype, B, dev, a, seed, input_seed=0, gather_dtype=None, e
         from tensorrt_dft_plugins_amd.engine import Engine
 
         t0 = time.perf_counter()
-        built = Engine.build(model, (x,), device=dev, use_graph=False)
+        # The stock patch-embedding Conv2d runs only while the export traces the model and while the
+        # optimizer checks its rewrite (the engine runs the hand kernel).  MIOpen would search and
+        # compile a solution for it at first use, ~10 s with an empty per-user MIOpen cache; ATen's
+        # own convolution needs no such step.
+        miopen, torch.backends.cudnn.enabled = torch.backends.cudnn.enabled, False
+        try:
+            built = Engine.build(model, (x,), device=dev, use_graph=False)
+        finally:
+            torch.backends.cudnn.enabled = miopen
         opt = built.header.extra.get("optimizer", {})
         if export == "contrib":
             log(f"{dtype}: contrib graph optimizer: {opt.get('nodes_before')} -> {opt.get('nodes_after')} nodes, "
@@ -330,11 +372,12 @@ def multi_gpu_diagnostics(runner, steps: int, world: int, dev, cuda: bool) -> di
     return out
 
 
-def _ensure_library(rank: int, world: int, cuda: bool) -> dict:
-    """The benchmarked library must be compiled from exactly these sources ON THIS HOST (the
-    reference builds and tests in one command, /root/reference/build_with_docker.sh:39): rebuild
-    from source here when the library's embedded digest does not match the sources or when it was
-    linked on another host (local rank 0 builds, the others wait).  Recorded in the JSON line."""
+def _ensure_library(rank: int, world: int, cuda: bool, full: bool) -> dict:
+    """The benchmarked library must be compiled from exactly these sources: rebuild from source
+    here when the library's embedded digest does not match them (local rank 0 builds, the others
+    wait).  ``full``: also when it was linked on another host, so that the timed binary is compiled
+    on the machine it runs on (a plain run records the build host in ``library.build_info`` and
+    leaves it at that).  Recorded in the JSON line."""
     import socket
 
     from tensorrt_dft_plugins_amd import _build
@@ -343,7 +386,7 @@ def _ensure_library(rank: int, world: int, cuda: bool) -> dict:
     rebuilt, err = False, None
     if not os.environ.get("MI_DFT_LIB"):
         info = _build.embedded_info(st["path"]) or ""
-        other_host = f"host={socket.gethostname()} " not in info + " "
+        other_host = full and f"host={socket.gethostname()} " not in info + " "
         if (not st["digest_ok"] or (cuda and other_host)) and os.environ.get("MI_DFT_BENCH_BUILD", "1") != "0":
             if int(os.environ.get("LOCAL_RANK", "0")) == 0:
                 log("native library " + ("does not match the sources" if not st["digest_ok"] else
@@ -375,24 +418,32 @@ def main(argv=None) -> int:
                     help="dtype of the gathered outputs (bf16: half the xGMI bytes of an fp32 model)")
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="fp32", help="headline precision")
-    ap.add_argument("--extra-steps", type=int, default=10, help="timed steps of the other-precision extra (0: skip)")
+    ap.add_argument("--extra-steps", type=int, default=10, help="--full: timed steps of the other-precision extra (0: skip)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-engine", dest="engine", action="store_false",
                     help="capture the nn.Module directly instead of the serialized engine")
     ap.add_argument("--export", choices=["contrib", "amd"], default="contrib",
                     help="headline engine: the stock ONNX-contrib export (reference workflow) or the native one")
     ap.add_argument("--native-steps", type=int, default=10,
-                    help="timed steps of the native-export fp32 engine extra (0: skip)")
+                    help="--full: timed steps of the native-export fp32 engine extra (0: skip)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--gather", choices=["rccl", "ipc"], default=os.environ.get("MI_DFT_GATHER", "rccl"),
                     help="output all-gather: RCCL ring collective or direct IPC pushes over xGMI")
     ap.add_argument("--force-gather", action="store_true",
                     help="single process: create a one-rank process group (RCCL on a GPU) and run the output "
                          "all-gather + its verification in every timed step (the multi-GPU comm path on one GPU)")
-    ap.add_argument("--no-fft", action="store_true", help="skip the rfft2 720x1440 / FNO block probes")
+    ap.add_argument("--no-fft", action="store_true", help="--full: skip the rfft2 720x1440 / FNO block probes")
     ap.add_argument("--tiny", action="store_true", help="tiny model/grid (harness smoke test, CPU ok)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the rfft2 / irfft2 / FNO block probes, "
+                         "the native-export engine and the other precision (extra keys of the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/output.npy (float32; "
+                         "a fixed seeded sample of an output too large to write whole)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rccl_dir = _rccl_log_setup(int(os.environ.get("WORLD_SIZE", "1")))
     rank, world, local = init_distributed()
@@ -405,7 +456,7 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", local % torch.cuda.device_count()) if cuda else torch.device("cpu")
     if cuda:
         torch.cuda.set_device(dev)
-    lib_note = _ensure_library(rank, world, cuda)
+    lib_note = _ensure_library(rank, world, cuda, a.full)
     tdp.load_plugins()
 
     if a.tiny:
@@ -422,7 +473,7 @@ def main(argv=None) -> int:
     gdt = torch.bfloat16 if a.gather_dtype == "bf16" else None
 
     extra = {}
-    if cuda and not a.no_fft and not a.tiny and rank == 0:
+    if a.full and cuda and not a.no_fft and not a.tiny and rank == 0:
         extra.update(time_fft_us())
         extra.update(time_fno_block_us())
         log(f"single-op probes: {extra}")
@@ -430,20 +481,22 @@ def main(argv=None) -> int:
     head_export = a.export if head_dt == torch.float32 else "amd"  # the contrib model is the reference's fp32
     eng_info, runner = build_runner(cfg, head_dt, B, dev, a, 1234, rank, gather_dtype=gdt, export=head_export)
     log(f"world={world} batch/GPU={B} dtype={head_dt} engine={eng_info.get('export', 'module')}")
-    if cuda and a.native_steps > 0 and not a.tiny and head_export == "contrib" and a.engine:
+    if a.full and cuda and a.native_steps > 0 and not a.tiny and head_export == "contrib" and a.engine:
         # the same fp32 model through the library-native export (com.amd.dft nodes), timed before the
         # headline so that neither engine is timed straight after a CPU-only build phase (the GPU
         # clocks down while the ONNX export runs on the host)
         _, r2 = build_runner(cfg, head_dt, B, dev, a, 1234, rank, gather_dtype=gdt, export="amd")
-        e2 = run_steps(r2, a.native_steps, 2, world, dev, cuda)
+        e2, _ = run_steps(r2, a.native_steps, 2, world, dev, cuda)
         extra["native_export_samples_per_s"] = round(world * B / (e2 / a.native_steps), 3)
         extra["native_export_ms_per_step"] = round(e2 * 1000.0 / a.native_steps, 3)
         r2.close()
         del r2
         torch.cuda.empty_cache()
-    elapsed = run_steps(runner, a.steps, a.warmup, world, dev, cuda)
+    elapsed, last = run_steps(runner, a.steps, a.warmup, world, dev, cuda)
     gathered = runner.gather
     gather_backend_used = runner.gather_backend
+    dumped = dump_outputs(a.dump_outputs, {"output": last}) if a.dump_outputs and rank == 0 else None
+    del last
     comm_diag = multi_gpu_diagnostics(runner, a.steps, world, dev, cuda) if gathered else {}
     runner.close()
     del runner
@@ -453,12 +506,12 @@ def main(argv=None) -> int:
     samples_per_s = world * B / (elapsed / a.steps)
     tflops = samples_per_s * flops_per_sample(cfg) / 1e12
 
-    if cuda and a.extra_steps > 0 and not a.tiny:
+    if a.full and cuda and a.extra_steps > 0 and not a.tiny:
         other = "bf16" if a.dtype == "fp32" else "fp32"
         # same weight / input seeds as the headline: only the precision differs (native export:
         # the contrib model is written the reference's fp32 way)
         _, r2 = build_runner(cfg, DTYPES[other], B, dev, a, 1234, rank, export="amd" if other == "bf16" else a.export)
-        e2 = run_steps(r2, a.extra_steps, 2, world, dev, cuda)
+        e2, _ = run_steps(r2, a.extra_steps, 2, world, dev, cuda)
         extra[f"{other}_samples_per_s"] = round(world * B / (e2 / a.extra_steps), 3)
         extra[f"{other}_ms_per_step"] = round(e2 * 1000.0 / a.extra_steps, 3)
         if other == "bf16":
@@ -518,6 +571,7 @@ def main(argv=None) -> int:
             **({"multi_gpu": dict(comm_diag, **({"rccl_nranks": rccl["nranks"]} if "nranks" in rccl else {}))}
                if comm_diag else {}),
             "library": dict(lib_note, build_info=tdp.build_info()),
+            **({"dumped_outputs": dumped} if dumped else {}),
         }
         out.update(extra)
         line = json.dumps(out)
