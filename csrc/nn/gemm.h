@@ -9,12 +9,18 @@ struct GemmLaunch {
   const uint16_t* x = nullptr;       // [M, K] bf16 (activations)
   const uint16_t* w = nullptr;       // [N, K] bf16 (weight, F.linear layout)
   const float* bias = nullptr;       // [N] fp32 or nullptr
-  const void* residual = nullptr;    // [M, N] bf16 (fp32 when out == 1) or nullptr (added after the activation)
+  // residual, added after the activation; nullptr or one of three forms:
+  //   [M, N] bf16 (out == 0) / fp32 (out == 1), the output's rows;
+  //   with res_rows > 0: [res_rows, N], row = token % res_rows (the patch embedding's pos);
+  //   with res_mean: [M, 2N] bf16 split pairs of x - m (below; the fp32 statistics GEMM only)
+  const void* residual = nullptr;
   void* y = nullptr;                 // [M, N] bf16 / fp32 (out == 1) / [M, 2N] split pair (out == 2)
   const float* ln_stats = nullptr;     // [M, 2] (mean, rstd) fp32 or nullptr: LayerNorm fold (see gemm.hip)
   const float* ln_c1 = nullptr;        // [N] fp32: sum_k W'[n, k] (required with ln_stats)
   int M = 0, N = 0, K = 0;
-  int act = 0;               // 0 none, 1 GELU (erf)
+  // 0 none, 1 GELU (erf), 2 GELU (tanh form), 3 GELU (erf fit at bf16 resolution, gelu.h).  The plain bf16
+  // GEMM, LayerNorm fold included, takes 0..3; split mode 0 or 1; the patch gather / scatter modes only 0.
+  int act = 0;
   // bf16x3 mode (fp32-class accuracy): x rows are [hi(K) | lo(K)] (row stride 2K; the
   // gathered image instead has its lo plane x_lo elements after the hi plane), w rows [hi | lo]
   int split = 0;

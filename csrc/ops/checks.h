@@ -64,4 +64,11 @@ inline void fallback_note(const char* op, const char* why) {
   if (first) TORCH_WARN("amd_dft.", op, ": falling back to ATen (", why, "); counted in amd_dft.fallback_counts()");
 }
 
+// ---- optional tensor arguments (a schema's "Tensor?"): None arrives as nullopt or as an undefined tensor
+inline bool present(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
+// the tensor as contiguous fp32 (what the kernels read for bias, c1, stats and pre), undefined when absent
+inline at::Tensor f32_or_undef(const c10::optional<at::Tensor>& t) {
+  return present(t) ? t->to(at::kFloat).contiguous() : at::Tensor();
+}
+
 }  // namespace amd_dft

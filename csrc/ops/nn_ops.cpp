@@ -18,6 +18,68 @@ void launch_patch_remap(const void* src, void* dst, int64_t B, int C, int h, int
 
 namespace {
 
+// ------------------------------------------------------------------ shared by the ops below
+void* current_stream(const c10::Device& d) { return c10::hip::getCurrentHIPStream(d.index()).stream(); }
+
+const void* data_or_null(const at::Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
+
+// rows of x when its last dim is k
+int64_t rows(const at::Tensor& x, int64_t k) { return x.numel() / std::max<int64_t>(k, 1); }
+
+// empty output with the leading dims of x, last dim n and dtype d, on x's device (so also the Meta shape)
+at::Tensor rows_like(const at::Tensor& x, int64_t n, at::ScalarType d) {
+  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
+  os.back() = n;
+  return at::empty(os, x.options().dtype(d));
+}
+
+// outputs of the statistics GEMMs: (y like x with N features, part [M, N/64, 2] fp32)
+std::tuple<at::Tensor, at::Tensor> stats_outputs(const at::Tensor& x, int64_t N, at::ScalarType d) {
+  return {rows_like(x, N, d), at::empty({rows(x, x.size(-1)), N / 64, 2}, x.options().dtype(at::kFloat))};
+}
+
+// One launch of the hand GEMM.  The constructor takes what every op has -- the contiguous operands, the
+// fp32 bias (undefined: none), the output and the problem size -- and does the pointer casts and the int
+// narrowing (gemm_supported bounds M, N and K) once; an op then sets only the GemmLaunch fields that make
+// it that op.  The tensors must outlive run().
+struct Gemm : GemmLaunch {
+  Gemm(const at::Tensor& xt, const at::Tensor& wt, const at::Tensor& bt, const at::Tensor& yt, int64_t m, int64_t n,
+       int64_t k) {
+    x = reinterpret_cast<const uint16_t*>(xt.data_ptr());
+    w = reinterpret_cast<const uint16_t*>(wt.data_ptr());
+    bias = bt.defined() ? bt.data_ptr<float>() : nullptr;
+    y = yt.data_ptr();
+    M = static_cast<int>(m);
+    N = static_cast<int>(n);
+    K = static_cast<int>(k);
+  }
+  // launches on the device's current HIP stream and returns it (for a kernel that follows)
+  void* run(const c10::Device& d) const {
+    void* stream = current_stream(d);
+    launch_gemm(*this, stream);
+    return stream;
+  }
+};
+
+bool bf16_gemm(const at::Tensor& x, const at::Tensor& w, int64_t M, int64_t N, int64_t K) {
+  return x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 && gemm_supported(M, N, K);
+}
+
+void check_act(const char* op, int64_t act, int64_t max_act) {
+  TORCH_CHECK(act >= 0 && act <= max_act, "amd_dft.", op, ": act must be 0 (none)",
+              max_act == 1 ? " or 1 (gelu)" : ", 1 (gelu), 2 (gelu, tanh form) or 3 (gelu, bf16 erf fit)");
+}
+
+// op with its prefix: the patch ops' messages carry no "amd_dft."
+void check_bias(const char* op, const c10::optional<at::Tensor>& bias, int64_t N) {
+  TORCH_CHECK(!present(bias) || bias->numel() == N, op, ": bias must have N entries");
+}
+
+void check_xw(const char* op, const at::Tensor& x, const at::Tensor& w) {
+  TORCH_CHECK(w.dim() == 2 && x.size(-1) == w.size(1), "amd_dft.", op, ": x [..., K], w [N, K]");
+}
+
+// ------------------------------------------------------------------ patchify / un-patchify
 // x [B, C, h*p, w*p] -> [B*h*w, C*p*p]
 at::Tensor patchify_cpu(const at::Tensor& x, int64_t p) {
   const int64_t B = x.size(0), C = x.size(1), h = x.size(2) / p, w = x.size(3) / p;
@@ -46,7 +108,7 @@ at::Tensor patchify_cuda(const at::Tensor& x_, int64_t p) {
   const int64_t B = x.size(0), C = x.size(1), h = x.size(2) / p, w = x.size(3) / p;
   at::Tensor out = at::empty({B * h * w, C * p * p}, x.options());
   launch_patch_remap(x.data_ptr(), out.data_ptr(), B, static_cast<int>(C), static_cast<int>(h), static_cast<int>(w), true,
-                     c10::hip::getCurrentHIPStream(x.device().index()).stream(), static_cast<int>(x.element_size()));
+                     current_stream(x.device()), static_cast<int>(x.element_size()));
   return out;
 }
 
@@ -61,24 +123,22 @@ at::Tensor unpatchify_cuda(const at::Tensor& t_, int64_t C, int64_t h, int64_t w
   const int64_t B = t.numel() / (h * w * C * p * p);
   at::Tensor out = at::empty({B, C, h * p, w * p}, t.options());
   launch_patch_remap(t.data_ptr(), out.data_ptr(), B, static_cast<int>(C), static_cast<int>(h), static_cast<int>(w), false,
-                     c10::hip::getCurrentHIPStream(t.device().index()).stream(), static_cast<int>(t.element_size()));
+                     current_stream(t.device()), static_cast<int>(t.element_size()));
   return out;
 }
 
 at::Tensor patchify_meta(const at::Tensor& x, int64_t p) {
-  const int64_t B = x.size(0), C = x.size(1), h = x.size(2) / p, w = x.size(3) / p;
-  return at::empty({B * h * w, C * p * p}, x.options());
+  return at::empty({x.size(0) * (x.size(2) / p) * (x.size(3) / p), x.size(1) * p * p}, x.options());
 }
 at::Tensor unpatchify_meta(const at::Tensor& t, int64_t C, int64_t h, int64_t w, int64_t p) {
   return at::empty({t.numel() / (h * w * C * p * p), C, h * p, w * p}, t.options());
 }
 
-
 // ------------------------------------------------------------------ fused-epilogue linear
 // y = act(x @ w^T + bias) (+ residual); x [..., K] bf16, w [N, K] bf16, y [..., N] bf16.
-// act: 0 none, 1 GELU (erf).  CUDA: the hand-written MFMA GEMM (csrc/nn/gemm.hip) when
-// N % 64 == 0 and K % 64 == 0 (a ragged last 256-feature panel is masked in the kernel), otherwise
-// hipBLASLt through at::linear (counted: fallback_counts / MI_DFT_STRICT).
+// act: 0 none, 1 GELU (erf), 2 GELU (tanh form), 3 GELU (the bf16 erf fit below).  CUDA: the hand-written
+// MFMA GEMM (csrc/nn/gemm.hip) when N % 64 == 0 and K % 64 == 0 (a ragged last 256-feature panel is masked
+// in the kernel), otherwise hipBLASLt through at::linear (counted: fallback_counts / MI_DFT_STRICT).
 // act 3: the bf16 paths' erf GELU, x sigmoid(x q(x^2)) (csrc/nn/gelu.h: gelu_erf_fit), same constants
 at::Tensor gelu_erf_fit_ref(const at::Tensor& y) {
   const at::Tensor x2 = at::clamp_max(y * y, 64.0);
@@ -93,57 +153,53 @@ at::Tensor apply_act_ref(const at::Tensor& y, int64_t act) {
   return y;
 }
 
+// x w^T + bias in fp32
+at::Tensor linear_f32(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias) {
+  return at::linear(x.to(at::kFloat), w.to(at::kFloat),
+                    present(bias) ? c10::optional<at::Tensor>(bias->to(at::kFloat)) : c10::nullopt);
+}
+
 at::Tensor linear_ref(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t act,
                       const c10::optional<at::Tensor>& residual) {
-  at::Tensor y = at::linear(x.to(at::kFloat), w.to(at::kFloat),
-                            bias.has_value() && bias->defined() ? c10::optional<at::Tensor>(bias->to(at::kFloat))
-                                                                : c10::nullopt);
-  y = apply_act_ref(y, act);
-  if (residual.has_value() && residual->defined()) y = y + residual->to(at::kFloat);
+  at::Tensor y = apply_act_ref(linear_f32(x, w, bias), act);
+  if (present(residual)) y = y + residual->to(at::kFloat);
   return y.to(x.scalar_type());
 }
 
 at::Tensor linear_cpu(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t act,
                       const c10::optional<at::Tensor>& residual) {
-  TORCH_CHECK(act >= 0 && act <= 3, "amd_dft.linear: act must be 0 (none), 1 (gelu), 2 (gelu, tanh form) or 3 (gelu, bf16 erf fit)");
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == w.size(0), "amd_dft.linear: bias must have N entries");
+  check_act("linear", act, 3);
+  check_bias("amd_dft.linear", bias, w.size(0));
   return linear_ref(x, w, bias, act, residual);
 }
 
 at::Tensor linear_cuda(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias,
                        int64_t act, const c10::optional<at::Tensor>& residual) {
   const c10::DeviceGuard guard(x_.device());
-  TORCH_CHECK(act >= 0 && act <= 3, "amd_dft.linear: act must be 0 (none), 1 (gelu), 2 (gelu, tanh form) or 3 (gelu, bf16 erf fit)");
-  TORCH_CHECK(w_.dim() == 2 && x_.size(-1) == w_.size(1), "amd_dft.linear: x [..., K], w [N, K]");
-  const int64_t K = w_.size(1), N = w_.size(0), M = x_.numel() / std::max<int64_t>(K, 1);
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == N, "amd_dft.linear: bias must have N entries");
-  if (x_.scalar_type() != at::kBFloat16 || w_.scalar_type() != at::kBFloat16 || !gemm_supported(M, N, K))
-  {
+  check_act("linear", act, 3);
+  check_xw("linear", x_, w_);
+  const int64_t K = w_.size(1), N = w_.size(0), M = rows(x_, K);
+  check_bias("amd_dft.linear", bias, N);
+  if (!bf16_gemm(x_, w_, M, N, K)) {
     fallback_note("linear", "needs bf16 operands, N % 64 == 0, K % 64 == 0 (fp32: use linear3)");
     return linear_ref(x_, w_, bias, act, residual);
   }
-  at::Tensor x = x_.contiguous(), w = w_.contiguous();
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  os.back() = N;
-  at::Tensor y = at::empty(os, x.options());
-  at::Tensor b, r;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  if (residual.has_value() && residual->defined()) {
+  at::Tensor x = x_.contiguous(), w = w_.contiguous(), b = f32_or_undef(bias), r;
+  if (present(residual)) {
     TORCH_CHECK(residual->numel() == M * N, "amd_dft.linear: residual must have the output's shape");
     r = residual->to(at::kBFloat16).contiguous();
   }
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(w.data_ptr());
-  p.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  p.residual = r.defined() ? r.data_ptr() : nullptr;
-  p.y = y.data_ptr();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.act = static_cast<int>(act);
-  launch_gemm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  at::Tensor y = rows_like(x, N, at::kBFloat16);
+  Gemm g(x, w, b, y, M, N, K);
+  g.act = static_cast<int>(act);
+  g.residual = data_or_null(r);
+  g.run(x.device());
   return y;
+}
+
+at::Tensor linear_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&, int64_t,
+                       const c10::optional<at::Tensor>&) {
+  return rows_like(x, w.size(0), x.scalar_type());
 }
 
 // ------------------------------------------------------------------ LayerNorm folded into a GEMM
@@ -154,11 +210,11 @@ at::Tensor linear_cuda(const at::Tensor& x_, const at::Tensor& w_, const c10::op
 // (x - mean) w exactly, with no cancellation beyond fp32 accumulation.
 void check_linear_ln(const at::Tensor& x, const at::Tensor& w, const at::Tensor& c1, const c10::optional<at::Tensor>& bias,
                      const at::Tensor& stats, int64_t act) {
-  TORCH_CHECK(act >= 0 && act <= 3, "amd_dft.linear_ln: act must be 0 (none), 1 (gelu), 2 (gelu, tanh form) or 3 (gelu, bf16 erf fit)");
-  TORCH_CHECK(w.dim() == 2 && x.size(-1) == w.size(1), "amd_dft.linear_ln: x [..., K], w [N, K]");
-  const int64_t K = w.size(1), N = w.size(0), M = x.numel() / std::max<int64_t>(K, 1);
+  check_act("linear_ln", act, 3);
+  check_xw("linear_ln", x, w);
+  const int64_t N = w.size(0), M = rows(x, w.size(1));
   TORCH_CHECK(c1.numel() == N, "amd_dft.linear_ln: c1 must have N entries");
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == N, "amd_dft.linear_ln: bias must have N entries");
+  check_bias("amd_dft.linear_ln", bias, N);
   TORCH_CHECK(stats.numel() == 2 * M && stats.size(-1) == 2, "amd_dft.linear_ln: stats must be [M, 2] (mean, rstd)");
 }
 
@@ -169,11 +225,29 @@ at::Tensor linear_ln_ref(const at::Tensor& x, const at::Tensor& w, const at::Ten
   at::Tensor st = stats.to(at::kFloat).reshape({-1, 2});
   at::Tensor t = at::matmul(xf, w.to(at::kFloat).t());
   at::Tensor y = st.select(1, 1).unsqueeze(1) * (t - st.select(1, 0).unsqueeze(1) * c1.to(at::kFloat).reshape({1, -1}));
-  if (bias.has_value() && bias->defined()) y = y + bias->to(at::kFloat).reshape({1, -1});
+  if (present(bias)) y = y + bias->to(at::kFloat).reshape({1, -1});
   y = apply_act_ref(y, act);
   std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
   os.back() = w.size(0);
   return y.reshape(os).to(x.scalar_type());
+}
+
+// linear_ln / linear3_ln on the hand GEMM, operands checked: bf16 rows in and out, or (split) split pairs in and out
+at::Tensor gemm_ln(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& c1_, const c10::optional<at::Tensor>& bias,
+                   const at::Tensor& stats_, int64_t act, int64_t M, int64_t N, int64_t K, bool split) {
+  at::Tensor x = x_.contiguous(), w = w_.contiguous(), b = f32_or_undef(bias);
+  at::Tensor c1 = c1_.to(at::kFloat).contiguous(), stats = stats_.to(at::kFloat).contiguous();
+  at::Tensor y = rows_like(x, split ? 2 * N : N, at::kBFloat16);
+  Gemm g(x, w, b, y, M, N, K);
+  g.act = static_cast<int>(act);
+  g.ln_stats = stats.data_ptr<float>();
+  g.ln_c1 = c1.data_ptr<float>();
+  if (split) {
+    g.split = 1;
+    g.out = 2;
+  }
+  g.run(x.device());
+  return y;
 }
 
 at::Tensor linear_ln_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& c1, const c10::optional<at::Tensor>& bias,
@@ -186,38 +260,17 @@ at::Tensor linear_ln_cuda(const at::Tensor& x_, const at::Tensor& w_, const at::
                           const c10::optional<at::Tensor>& bias, const at::Tensor& stats_, int64_t act) {
   const c10::DeviceGuard guard(x_.device());
   check_linear_ln(x_, w_, c1_, bias, stats_, act);
-  const int64_t K = w_.size(1), N = w_.size(0), M = x_.numel() / std::max<int64_t>(K, 1);
-  if (x_.scalar_type() != at::kBFloat16 || w_.scalar_type() != at::kBFloat16 || !gemm_supported(M, N, K)) {
+  const int64_t K = w_.size(1), N = w_.size(0), M = rows(x_, K);
+  if (!bf16_gemm(x_, w_, M, N, K)) {
     fallback_note("linear_ln", "needs bf16 operands, N % 64 == 0, K % 64 == 0");
     return linear_ln_ref(x_, w_, c1_, bias, stats_, act);
   }
-  at::Tensor x = x_.contiguous(), w = w_.contiguous();
-  at::Tensor c1 = c1_.to(at::kFloat).contiguous(), stats = stats_.to(at::kFloat).contiguous();
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  os.back() = N;
-  at::Tensor y = at::empty(os, x.options());
-  at::Tensor b;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(w.data_ptr());
-  p.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  p.y = y.data_ptr();
-  p.ln_stats = stats.data_ptr<float>();
-  p.ln_c1 = c1.data_ptr<float>();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.act = static_cast<int>(act);
-  launch_gemm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-  return y;
+  return gemm_ln(x_, w_, c1_, bias, stats_, act, M, N, K, false);
 }
 
 at::Tensor linear_ln_meta(const at::Tensor& x, const at::Tensor& w, const at::Tensor&, const c10::optional<at::Tensor>&,
                           const at::Tensor&, int64_t) {
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  os.back() = w.size(0);
-  return at::empty(os, x.options());
+  return rows_like(x, w.size(0), x.scalar_type());
 }
 
 // ------------------------------------------------------------------ patch embedding / head
@@ -225,17 +278,74 @@ at::Tensor linear_ln_meta(const at::Tensor& x, const at::Tensor& w, const at::Te
 // linear_unpatch: image = unpatchify(t @ w^T + bias)                     ([B, C, h*p, w*p])
 // CUDA with p == 8 and bf16: one MFMA GEMM each, the (un)patchify folded into its operand
 // gather / output scatter (csrc/nn/gemm.hip MODE 1 / 2).  The reference conv / linear +
-// permute path is the CPU implementation.
+// permute path is the CPU implementation.  The bf16x3 forms (patch_linear3 / linear_unpatch3,
+// below) run the same two launches with split operands and fp32 outputs.
+
+// fp32 token rows y [B*h*w, N] + pos [h*w, N], broadcast over the batch
+at::Tensor add_pos(const at::Tensor& y, const c10::optional<at::Tensor>& pos, int64_t hw) {
+  if (!present(pos)) return y;
+  const int64_t N = y.size(-1);
+  return (y.reshape({-1, hw, N}) + pos->to(at::kFloat).reshape({1, hw, N})).reshape({-1, N});
+}
+
+// the gather GEMM: x is the contiguous bf16 image [B, C, h*8, w*8] or (split) its planes [2, B, C, h*8, w*8];
+// tokens, bias and pos are bf16 / fp32 / bf16, on the split path all fp32
+at::Tensor gemm_patch(const char* op, const at::Tensor& x, const at::Tensor& w_, const c10::optional<at::Tensor>& bias,
+                      const c10::optional<at::Tensor>& pos, int64_t M, int64_t N, int64_t C, int64_t h, int64_t w,
+                      bool split) {
+  const at::ScalarType dt = split ? at::kFloat : at::kBFloat16;
+  at::Tensor wc = w_.contiguous(), b = f32_or_undef(bias), r;
+  if (present(pos)) {
+    TORCH_CHECK(pos->numel() == h * w * N, op, ": pos must be [h*w, N]");
+    r = pos->to(dt).contiguous();
+  }
+  at::Tensor y = at::empty({M, N}, x.options().dtype(dt));
+  Gemm g(x, wc, b, y, M, N, C * 64);
+  g.residual = data_or_null(r);
+  g.res_rows = static_cast<int>(h * w);
+  g.gC = static_cast<int>(C);
+  g.gh = static_cast<int>(h);
+  g.gw = static_cast<int>(w);
+  if (split) {
+    g.split = 1;
+    g.out = 1;
+    g.x_lo = x.numel() / 2;
+  }
+  g.run(x.device());
+  return y;
+}
+
+// the scatter GEMM: t bf16 rows or (split) split pairs, image bf16 / fp32.  N % 256 != 0 (C % 4 != 0):
+// token-major GEMM with a ragged last panel, then the remap kernel
+at::Tensor gemm_unpatch(const at::Tensor& t_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias, int64_t M,
+                        int64_t N, int64_t K, int64_t C, int64_t h, int64_t wd, bool split) {
+  at::Tensor t = t_.contiguous(), wc = w_.contiguous(), b = f32_or_undef(bias);
+  const int64_t B = M / (h * wd);
+  at::Tensor y = at::empty({B, C, h * 8, wd * 8}, t.options().dtype(split ? at::kFloat : at::kBFloat16));
+  const bool ragged = N % 256 != 0;
+  at::Tensor yt = ragged ? at::empty({M, N}, y.options()) : y;
+  Gemm g(t, wc, b, yt, M, N, K);
+  if (!ragged) {
+    g.sC = static_cast<int>(C);
+    g.sh = static_cast<int>(h);
+    g.sw = static_cast<int>(wd);
+  }
+  if (split) {
+    g.split = 1;
+    g.out = 1;
+  }
+  void* stream = g.run(t.device());
+  if (ragged)
+    launch_patch_remap(yt.data_ptr(), y.data_ptr(), B, static_cast<int>(C), static_cast<int>(h), static_cast<int>(wd),
+                       false, stream, static_cast<int>(y.element_size()));
+  return y;
+}
+
 at::Tensor patch_linear_cpu(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                             const c10::optional<at::Tensor>& pos, int64_t p) {
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == w.size(0), "patch_linear: bias must have N entries");
-  at::Tensor t = patchify_cpu(x, p);
-  at::Tensor y = linear_ref(t, w, bias, 0, c10::nullopt).to(at::kFloat);
-  if (pos.has_value() && pos->defined()) {
-    const int64_t hw = (x.size(2) / p) * (x.size(3) / p);
-    y = (y.reshape({-1, hw, w.size(0)}) + pos->to(at::kFloat).reshape({1, hw, w.size(0)})).reshape({-1, w.size(0)});
-  }
-  return y.to(x.scalar_type()).contiguous();
+  check_bias("patch_linear", bias, w.size(0));
+  at::Tensor y = linear_ref(patchify_cpu(x, p), w, bias, 0, c10::nullopt).to(at::kFloat);
+  return add_pos(y, pos, (x.size(2) / p) * (x.size(3) / p)).to(x.scalar_type()).contiguous();
 }
 
 at::Tensor patch_linear_cuda(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias,
@@ -245,36 +355,12 @@ at::Tensor patch_linear_cuda(const at::Tensor& x_, const at::Tensor& w_, const c
   TORCH_CHECK(w_.dim() == 2 && w_.size(1) == x_.size(1) * p * p, "patch_linear: w must be [N, C*p*p]");
   const int64_t B = x_.size(0), C = x_.size(1), h = x_.size(2) / p, w = x_.size(3) / p, N = w_.size(0);
   const int64_t M = B * h * w, K = C * p * p;
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == N, "patch_linear: bias must have N entries");
-  const bool native = p == 8 && x_.scalar_type() == at::kBFloat16 && w_.scalar_type() == at::kBFloat16 &&
-                      gemm_supported(M, N, K) && x_.numel() < (int64_t(1) << 31);
-  if (!native) {  // ATen ops on the device tensors
+  check_bias("patch_linear", bias, N);
+  if (!(p == 8 && bf16_gemm(x_, w_, M, N, K) && x_.numel() < (int64_t(1) << 31))) {  // ATen ops on the device tensors
     fallback_note("patch_linear", "needs bf16, p == 8, N % 64 == 0 (fp32: use patch_linear3)");
     return patch_linear_cpu(x_, w_, bias, pos, p);
   }
-  at::Tensor x = x_.contiguous(), wc = w_.contiguous();
-  at::Tensor y = at::empty({M, N}, x.options());
-  at::Tensor b, r;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  if (pos.has_value() && pos->defined()) {
-    TORCH_CHECK(pos->numel() == h * w * N, "patch_linear: pos must be [h*w, N]");
-    r = pos->to(at::kBFloat16).contiguous();
-  }
-  GemmLaunch g;
-  g.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
-  g.w = reinterpret_cast<const uint16_t*>(wc.data_ptr());
-  g.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  g.residual = r.defined() ? r.data_ptr() : nullptr;
-  g.res_rows = static_cast<int>(h * w);
-  g.y = y.data_ptr();
-  g.M = static_cast<int>(M);
-  g.N = static_cast<int>(N);
-  g.K = static_cast<int>(K);
-  g.gC = static_cast<int>(C);
-  g.gh = static_cast<int>(h);
-  g.gw = static_cast<int>(w);
-  launch_gemm(g, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-  return y;
+  return gemm_patch("patch_linear", x_.contiguous(), w_, bias, pos, M, N, C, h, w, false);
 }
 
 at::Tensor patch_linear_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&,
@@ -284,7 +370,7 @@ at::Tensor patch_linear_meta(const at::Tensor& x, const at::Tensor& w, const c10
 
 at::Tensor linear_unpatch_cpu(const at::Tensor& t, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                               int64_t C, int64_t h, int64_t wd, int64_t p) {
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == w.size(0), "linear_unpatch: bias must have N entries");
+  check_bias("linear_unpatch", bias, w.size(0));
   return unpatchify_cpu(linear_ref(t, w, bias, 0, c10::nullopt), C, h, wd, p);
 }
 
@@ -293,54 +379,19 @@ at::Tensor linear_unpatch_cuda(const at::Tensor& t_, const at::Tensor& w_, const
   const c10::DeviceGuard guard(t_.device());
   TORCH_CHECK(w_.dim() == 2 && t_.size(-1) == w_.size(1) && w_.size(0) == C * p * p,
               "linear_unpatch: t [..., K], w [C*p*p, K] in (c, py, px) feature order");
-  const int64_t K = w_.size(1), N = w_.size(0), M = t_.numel() / std::max<int64_t>(K, 1);
+  const int64_t K = w_.size(1), N = w_.size(0), M = rows(t_, K);
   TORCH_CHECK(M % (h * wd) == 0, "linear_unpatch: token count must be a multiple of h*w");
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == N, "linear_unpatch: bias must have N entries");
-  const bool native = p == 8 && t_.scalar_type() == at::kBFloat16 && w_.scalar_type() == at::kBFloat16 &&
-                      gemm_supported(M, N, K) && M * N < (int64_t(1) << 31);
-  if (!native) {
+  check_bias("linear_unpatch", bias, N);
+  if (!(p == 8 && bf16_gemm(t_, w_, M, N, K) && M * N < (int64_t(1) << 31))) {
     fallback_note("linear_unpatch", "needs bf16, p == 8, N % 64 == 0 (fp32: use linear_unpatch3)");
     return linear_unpatch_cpu(t_, w_, bias, C, h, wd, p);
   }
-  at::Tensor t = t_.contiguous(), wc = w_.contiguous();
-  const int64_t B = M / (h * wd);
-  at::Tensor y = at::empty({B, C, h * p, wd * p}, t.options());
-  at::Tensor b;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  // N % 256 != 0 (C % 4 != 0): token-major GEMM with a ragged last panel, then the remap kernel
-  const bool ragged = N % 256 != 0;
-  at::Tensor yt = ragged ? at::empty({M, N}, t.options()) : at::Tensor();
-  GemmLaunch g;
-  g.x = reinterpret_cast<const uint16_t*>(t.data_ptr());
-  g.w = reinterpret_cast<const uint16_t*>(wc.data_ptr());
-  g.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  g.y = ragged ? yt.data_ptr() : y.data_ptr();
-  g.M = static_cast<int>(M);
-  g.N = static_cast<int>(N);
-  g.K = static_cast<int>(K);
-  if (!ragged) {
-    g.sC = static_cast<int>(C);
-    g.sh = static_cast<int>(h);
-    g.sw = static_cast<int>(wd);
-  }
-  auto stream = c10::hip::getCurrentHIPStream(t.device().index()).stream();
-  launch_gemm(g, stream);
-  if (ragged)
-    launch_patch_remap(yt.data_ptr(), y.data_ptr(), B, static_cast<int>(C), static_cast<int>(h), static_cast<int>(wd),
-                       false, stream, 2);
-  return y;
+  return gemm_unpatch(t_, w_, bias, M, N, K, C, h, wd, false);
 }
 
 at::Tensor linear_unpatch_meta(const at::Tensor& t, const at::Tensor& w, const c10::optional<at::Tensor>&, int64_t C,
                                int64_t h, int64_t wd, int64_t p) {
   return at::empty({t.numel() / w.size(1) / (h * wd), C, h * p, wd * p}, t.options());
-}
-
-at::Tensor linear_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&, int64_t,
-                       const c10::optional<at::Tensor>&) {
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  os.back() = w.size(0);
-  return at::empty(os, x.options());
 }
 
 // ------------------------------------------------------------------ bf16x3 (fp32-class) GEMMs
@@ -375,6 +426,14 @@ at::Tensor split_ref(const at::Tensor& x, bool rows) {
 
 at::Tensor split_bf16_cpu(const at::Tensor& x, bool rows) { return split_ref(x, rows); }
 
+// empty bf16 pairs of x on its device: rows [..., 2K] or planes [2, ...]
+at::Tensor split_like(const at::Tensor& x, bool rows) {
+  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
+  if (rows) os.back() = 2 * os.back();
+  else os.insert(os.begin(), 2);
+  return at::empty(os, x.options().dtype(at::kBFloat16));
+}
+
 at::Tensor split_bf16_cuda(const at::Tensor& x_, bool rows) {
   const c10::DeviceGuard guard(x_.device());
   TORCH_CHECK(x_.scalar_type() == at::kFloat, "amd_dft.split_bf16: x must be float32");
@@ -383,137 +442,141 @@ at::Tensor split_bf16_cuda(const at::Tensor& x_, bool rows) {
   const int64_t cols = x.size(-1);
   TORCH_CHECK(x.numel() % 8 == 0 && (!rows || cols % 32 == 0),
               "amd_dft.split_bf16: needs multiples of 8 elements (rows: a last dim that is a multiple of 32)");
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  if (rows) os.back() = 2 * cols;
-  else os.insert(os.begin(), 2);
-  at::Tensor y = at::empty(os, x.options().dtype(at::kBFloat16));
+  at::Tensor y = split_like(x, rows);
   launch_split_bf16(x.data_ptr<float>(), reinterpret_cast<uint16_t*>(y.data_ptr()), x.numel(), static_cast<int>(cols),
-                    rows, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+                    rows, current_stream(x.device()));
   return y;
 }
 
-at::Tensor split_bf16_meta(const at::Tensor& x, bool rows) {
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  if (rows) os.back() = 2 * os.back();
-  else os.insert(os.begin(), 2);
-  return at::empty(os, x.options().dtype(at::kBFloat16));
-}
+at::Tensor split_bf16_meta(const at::Tensor& x, bool rows) { return split_like(x, rows); }
 
 void check_split_linear(const at::Tensor& xs, const at::Tensor& ws, const c10::optional<at::Tensor>& bias,
                         const char* op) {
   TORCH_CHECK(xs.scalar_type() == at::kBFloat16 && ws.scalar_type() == at::kBFloat16, "amd_dft.", op,
               ": split operands must be bfloat16 pairs");
   TORCH_CHECK(ws.dim() == 2 && ws.size(1) % 2 == 0, "amd_dft.", op, ": ws must be [N, 2K] = [hi | lo]");
-  TORCH_CHECK(!bias.has_value() || !bias->defined() || bias->numel() == ws.size(0), "amd_dft.", op,
-              ": bias must have N entries");
+  TORCH_CHECK(!present(bias) || bias->numel() == ws.size(0), "amd_dft.", op, ": bias must have N entries");
+}
+
+// split rows against split weights of the same K
+void check_split_rows(const at::Tensor& xs, const at::Tensor& ws, const c10::optional<at::Tensor>& bias,
+                      const char* op) {
+  check_split_linear(xs, ws, bias, op);
+  TORCH_CHECK(xs.size(-1) == ws.size(1), "amd_dft.", op, ": xs [..., 2K], ws [N, 2K]");
 }
 
 at::Tensor linear3_cpu(const at::Tensor& xs, const at::Tensor& ws, const c10::optional<at::Tensor>& bias, int64_t act,
                        const c10::optional<at::Tensor>& residual, bool split_out) {
-  check_split_linear(xs, ws, bias, "linear3");
-  TORCH_CHECK(xs.size(-1) == ws.size(1), "amd_dft.linear3: xs [..., 2K], ws [N, 2K]");
-  TORCH_CHECK(act == 0 || act == 1, "amd_dft.linear3: act must be 0 (none) or 1 (gelu)");
-  at::Tensor y = at::linear(unsplit_rows(xs), unsplit_rows(ws),
-                            bias.has_value() && bias->defined() ? c10::optional<at::Tensor>(bias->to(at::kFloat))
-                                                                : c10::nullopt);
-  if (act == 1) y = at::gelu(y);
-  if (residual.has_value() && residual->defined()) y = y + residual->to(at::kFloat).reshape(y.sizes());
+  check_split_rows(xs, ws, bias, "linear3");
+  check_act("linear3", act, 1);
+  at::Tensor y = apply_act_ref(linear_f32(unsplit_rows(xs), unsplit_rows(ws), bias), act);
+  if (present(residual)) y = y + residual->to(at::kFloat).reshape(y.sizes());
   return split_out ? split_ref(y, true) : y.contiguous();
 }
 
 at::Tensor linear3_cuda(const at::Tensor& xs_, const at::Tensor& ws_, const c10::optional<at::Tensor>& bias,
                         int64_t act, const c10::optional<at::Tensor>& residual, bool split_out) {
   const c10::DeviceGuard guard(xs_.device());
-  check_split_linear(xs_, ws_, bias, "linear3");
-  TORCH_CHECK(act == 0 || act == 1, "amd_dft.linear3: act must be 0 (none) or 1 (gelu)");
-  TORCH_CHECK(xs_.size(-1) == ws_.size(1), "amd_dft.linear3: xs [..., 2K], ws [N, 2K]");
-  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = xs_.numel() / std::max<int64_t>(2 * K, 1);
+  check_split_rows(xs_, ws_, bias, "linear3");
+  check_act("linear3", act, 1);
+  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = rows(xs_, 2 * K);
   TORCH_CHECK(gemm_supported(M, N, K), "amd_dft.linear3: the bf16x3 GEMM needs N % 64 == 0 and K % 64 == 0 (got N=",
               N, ", K=", K, ")");
-  TORCH_CHECK(!(split_out && residual.has_value() && residual->defined() &&
-                (act != 0 || (bias.has_value() && bias->defined()))),
+  TORCH_CHECK(!(split_out && present(residual) && (act != 0 || present(bias))),
               "amd_dft.linear3: a split-pair output takes a residual only without activation and bias");
-  at::Tensor xs = xs_.contiguous(), ws = ws_.contiguous();
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = split_out ? 2 * N : N;
-  at::Tensor y = at::empty(os, xs.options().dtype(split_out ? at::kBFloat16 : at::kFloat));
-  at::Tensor b, r;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  if (residual.has_value() && residual->defined()) {
+  at::Tensor xs = xs_.contiguous(), ws = ws_.contiguous(), b = f32_or_undef(bias), r;
+  if (present(residual)) {
     TORCH_CHECK(residual->numel() == M * N, "amd_dft.linear3: residual must have the output's shape");
     r = residual->to(at::kFloat).contiguous();
   }
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(xs.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  p.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  p.residual = r.defined() ? r.data_ptr() : nullptr;
-  p.y = y.data_ptr();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.act = static_cast<int>(act);
-  p.split = 1;
-  p.out = split_out ? 2 : 1;
-  if (M > 0) launch_gemm(p, c10::hip::getCurrentHIPStream(xs.device().index()).stream());
+  at::Tensor y = rows_like(xs, split_out ? 2 * N : N, split_out ? at::kBFloat16 : at::kFloat);
+  Gemm g(xs, ws, b, y, M, N, K);
+  g.act = static_cast<int>(act);
+  g.residual = data_or_null(r);
+  g.split = 1;
+  g.out = split_out ? 2 : 1;
+  g.run(xs.device());
   return y;
 }
 
-// fc2 of the fp32 FourCastNet block: y = xs ws^T + residual (bf16x3, fp32 out) and, from the same
-// epilogue, the next LayerNorm's partial statistics of y + pre: part [M, N/64, 2] = per 64-feature
-// chunk (mean, M2); ln_stats_merge turns them into (mean, rstd) without another pass over y
-std::tuple<at::Tensor, at::Tensor> linear3_stats_cpu(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& residual,
-                                                     const c10::optional<at::Tensor>& pre) {
-  at::Tensor y = linear3_cpu(xs, ws, c10::nullopt, 0, residual, false);
-  const int64_t N = ws.size(0);
-  TORCH_CHECK(N % 64 == 0, "amd_dft.linear3_stats: N must be a multiple of 64");
-  at::Tensor w = y.reshape({-1, N});
-  if (pre.has_value() && pre->defined()) w = w + pre->to(at::kFloat).reshape({1, N});
+at::Tensor linear3_meta(const at::Tensor& xs, const at::Tensor& ws, const c10::optional<at::Tensor>&, int64_t,
+                        const c10::optional<at::Tensor>&, bool split_out) {
+  return rows_like(xs, split_out ? 2 * ws.size(0) : ws.size(0), split_out ? at::kBFloat16 : at::kFloat);
+}
+
+// ------------------------------------------------------------------ fc2 with the next LayerNorm's statistics
+// linear_stats, the bf16 FourCastNet block: y = x w^T + residual (bf16) and, from the same epilogue, the
+// next LayerNorm's partial statistics of y + pre -- taken on the stored (bf16-rounded) y, so they
+// describe exactly the tensor that LayerNorm reads: part [M, N/64, 2] = per 64-feature chunk
+// (mean, M2), merged by ln_stats_merge (replaces an ln_stats pass over y).
+// linear3_stats, the fp32 block: y = xs ws^T + residual (bf16x3, fp32 out) with the same partials;
+// ln_stats_merge turns them into (mean, rstd) without another pass over y
+std::tuple<at::Tensor, at::Tensor> chunk_partials(const at::Tensor& y, const c10::optional<at::Tensor>& pre, int64_t N) {
+  at::Tensor w = y.to(at::kFloat).reshape({-1, N});
+  if (present(pre)) w = w + pre->to(at::kFloat).reshape({1, N});
   w = w.reshape({w.size(0), N / 64, 64});
   at::Tensor mean = w.mean(2);
   at::Tensor m2 = (w - mean.unsqueeze(2)).pow(2).sum(2);
   return {y, at::stack({mean, m2}, 2).contiguous()};
 }
 
-std::tuple<at::Tensor, at::Tensor> linear3_stats_cuda(const at::Tensor& xs_, const at::Tensor& ws_, const at::Tensor& residual,
-                                                      const c10::optional<at::Tensor>& pre_) {
-  const c10::DeviceGuard guard(xs_.device());
-  check_split_linear(xs_, ws_, c10::nullopt, "linear3_stats");
-  TORCH_CHECK(xs_.size(-1) == ws_.size(1), "amd_dft.linear3_stats: xs [..., 2K], ws [N, 2K]");
-  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = xs_.numel() / std::max<int64_t>(2 * K, 1);
-  TORCH_CHECK(gemm_supported(M, N, K), "amd_dft.linear3_stats: the bf16x3 GEMM needs N % 64 == 0 and K % 64 == 0");
-  TORCH_CHECK(residual.numel() == M * N, "amd_dft.linear3_stats: residual must have the output's shape");
-  at::Tensor xs = xs_.contiguous(), ws = ws_.contiguous(), r = residual.to(at::kFloat).contiguous();
-  // the kernel always reads pre (zeros when absent): an optional load behind a branch made the compiler
-  // wait for it -- and for every store before it -- right where it was issued
-  at::Tensor pre;
-  if (pre_.has_value() && pre_->defined()) {
-    pre = pre_->to(at::kFloat).contiguous();
-    TORCH_CHECK(pre.numel() == N, "amd_dft.linear3_stats: pre must have N entries");
-  } else {
-    pre = at::zeros({N}, xs.options().dtype(at::kFloat));
+void check_pre(const char* op, const c10::optional<at::Tensor>& pre, int64_t N) {
+  TORCH_CHECK(!present(pre) || pre->numel() == N, "amd_dft.", op, ": pre must have N entries");
+}
+
+// the kernel always reads pre (zeros when absent): an optional load behind a branch made the compiler
+// wait for it -- and for every store before it -- right where it was issued
+at::Tensor stats_pre(const char* op, const c10::optional<at::Tensor>& pre, int64_t N, const at::Tensor& like) {
+  check_pre(op, pre, N);
+  return present(pre) ? f32_or_undef(pre) : at::zeros({N}, like.options().dtype(at::kFloat));
+}
+
+void check_linear_stats(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& pre) {
+  check_xw("linear_stats", x, w);
+  TORCH_CHECK(w.size(0) % 64 == 0, "amd_dft.linear_stats: N must be a multiple of 64");
+  check_pre("linear_stats", pre, w.size(0));
+}
+
+std::tuple<at::Tensor, at::Tensor> linear_stats_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& residual,
+                                                    const c10::optional<at::Tensor>& pre) {
+  check_linear_stats(x, w, pre);
+  return chunk_partials(linear_ref(x, w, c10::nullopt, 0, residual), pre, w.size(0));
+}
+
+std::tuple<at::Tensor, at::Tensor> linear_stats_cuda(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& residual,
+                                                     const c10::optional<at::Tensor>& pre_) {
+  const c10::DeviceGuard guard(x_.device());
+  check_linear_stats(x_, w_, pre_);
+  const int64_t K = w_.size(1), N = w_.size(0), M = rows(x_, K);
+  TORCH_CHECK(residual.numel() == M * N, "amd_dft.linear_stats: residual must have the output's shape");
+  if (!bf16_gemm(x_, w_, M, N, K)) {
+    fallback_note("linear_stats", "needs bf16 operands, N % 64 == 0, K % 64 == 0");
+    return chunk_partials(linear_ref(x_, w_, c10::nullopt, 0, residual), pre_, N);
   }
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = N;
-  at::Tensor y = at::empty(os, xs.options().dtype(at::kFloat));
-  at::Tensor part = at::empty({M, N / 64, 2}, xs.options().dtype(at::kFloat));
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(xs.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  p.residual = r.data_ptr();
-  p.y = y.data_ptr();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.split = 1;
-  p.out = 1;
-  p.stats_part = part.data_ptr<float>();
-  p.stats_pre = pre.data_ptr<float>();
-  if (M > 0) launch_gemm(p, c10::hip::getCurrentHIPStream(xs.device().index()).stream());
+  at::Tensor x = x_.contiguous(), w = w_.contiguous(), r = residual.to(at::kBFloat16).contiguous();
+  at::Tensor pre = stats_pre("linear_stats", pre_, N, x);
+  auto [y, part] = stats_outputs(x, N, at::kBFloat16);
+  Gemm g(x, w, at::Tensor(), y, M, N, K);
+  g.residual = r.data_ptr();
+  g.stats_part = part.data_ptr<float>();
+  g.stats_pre = pre.data_ptr<float>();
+  g.run(x.device());
   return {y, part};
 }
 
-// fc2 of the fp32 block with the residual stream carried as c2r_ln_add_split's split pairs (no fp32 copy of it):
+std::tuple<at::Tensor, at::Tensor> linear_stats_meta(const at::Tensor& x, const at::Tensor& w, const at::Tensor&,
+                                                     const c10::optional<at::Tensor>&) {
+  return stats_outputs(x, w.size(0), x.scalar_type());
+}
+
+std::tuple<at::Tensor, at::Tensor> linear3_stats_cpu(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& residual,
+                                                     const c10::optional<at::Tensor>& pre) {
+  at::Tensor y = linear3_cpu(xs, ws, c10::nullopt, 0, residual, false);
+  TORCH_CHECK(ws.size(0) % 64 == 0, "amd_dft.linear3_stats: N must be a multiple of 64");
+  return chunk_partials(y, pre, ws.size(0));
+}
+
+// linear3_stats_pr: the residual stream carried as c2r_ln_add_split's split pairs (no fp32 copy of it):
 // residual = m + (hi + lo), rpairs [M, 2N] bf16 k32-interleaved pairs of x - m, rstats [M, 2] with m = rstats[:, 0]
 // (the block's LN1 statistics, which centred those pairs).  2^-18 of |x - m| off the fp32 residual.
 // rlo2 (optional): the split's third term bf16(x - m - (hi + lo)) [M, N] (c2r_ln_add_split out_mode 2): the
@@ -522,7 +585,7 @@ at::Tensor pairs_residual_cpu(const at::Tensor& rpairs, const at::Tensor& rstats
                               const c10::optional<at::Tensor>& rlo2) {
   at::Tensor pr = rpairs.to(at::kFloat).reshape({-1, N / 32, 2, 32});
   at::Tensor z = (pr.select(2, 0) + pr.select(2, 1)).reshape({-1, N});
-  if (rlo2.has_value() && rlo2->defined()) z = z + rlo2->to(at::kFloat).reshape({-1, N});
+  if (present(rlo2)) z = z + rlo2->to(at::kFloat).reshape({-1, N});
   return z + rstats.to(at::kFloat).reshape({-1, 2}).select(1, 0).unsqueeze(1);
 }
 
@@ -536,135 +599,68 @@ void check_pairs_residual(const at::Tensor& rpairs, const at::Tensor& rstats, in
 std::tuple<at::Tensor, at::Tensor> linear3_stats_pr_cpu(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& rpairs,
                                                         const at::Tensor& rstats, const c10::optional<at::Tensor>& pre,
                                                         const c10::optional<at::Tensor>& rlo2) {
-  const int64_t N = ws.size(0), M = xs.numel() / std::max<int64_t>(xs.size(-1), 1);
+  const int64_t N = ws.size(0), M = rows(xs, xs.size(-1));
   check_pairs_residual(rpairs, rstats, M, N);
   return linear3_stats_cpu(xs, ws, pairs_residual_cpu(rpairs, rstats, N, rlo2), pre);
 }
 
-std::tuple<at::Tensor, at::Tensor> linear3_stats_pr_cuda(const at::Tensor& xs_, const at::Tensor& ws_, const at::Tensor& rpairs_,
-                                                         const at::Tensor& rstats_, const c10::optional<at::Tensor>& pre_,
-                                                         const c10::optional<at::Tensor>& rlo2_) {
+// Both statistics GEMMs of the fp32 block.  rstats == nullptr: residual is the [M, N] tensor, read as fp32.
+// Otherwise the pairs form: residual = rpairs and rlo2, both left as the bf16 they are, with rstats as fp32.
+std::tuple<at::Tensor, at::Tensor> gemm3_stats(const char* op, const at::Tensor& xs_, const at::Tensor& ws_,
+                                               const at::Tensor& residual, const at::Tensor* rstats,
+                                               const c10::optional<at::Tensor>& rlo2, const c10::optional<at::Tensor>& pre_) {
   const c10::DeviceGuard guard(xs_.device());
-  check_split_linear(xs_, ws_, c10::nullopt, "linear3_stats_pr");
-  TORCH_CHECK(xs_.size(-1) == ws_.size(1), "amd_dft.linear3_stats_pr: xs [..., 2K], ws [N, 2K]");
-  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = xs_.numel() / std::max<int64_t>(2 * K, 1);
-  TORCH_CHECK(gemm_supported(M, N, K), "amd_dft.linear3_stats_pr: the bf16x3 GEMM needs N % 64 == 0 and K % 64 == 0");
-  check_pairs_residual(rpairs_, rstats_, M, N);
-  at::Tensor xs = xs_.contiguous(), ws = ws_.contiguous(), rp = rpairs_.contiguous(), rs = rstats_.to(at::kFloat).contiguous();
-  at::Tensor pre;
-  if (pre_.has_value() && pre_->defined()) {
-    pre = pre_->to(at::kFloat).contiguous();
-    TORCH_CHECK(pre.numel() == N, "amd_dft.linear3_stats_pr: pre must have N entries");
+  check_split_rows(xs_, ws_, c10::nullopt, op);
+  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = rows(xs_, 2 * K);
+  TORCH_CHECK(gemm_supported(M, N, K), "amd_dft.", op, ": the bf16x3 GEMM needs N % 64 == 0 and K % 64 == 0");
+  at::Tensor xs = xs_.contiguous(), ws = ws_.contiguous(), r, rs, rl;
+  if (rstats) {
+    check_pairs_residual(residual, *rstats, M, N);
+    r = residual.contiguous();
+    rs = rstats->to(at::kFloat).contiguous();
+    if (present(rlo2)) {
+      TORCH_CHECK(rlo2->scalar_type() == at::kBFloat16 && rlo2->numel() == M * N,
+                  "amd_dft.linear3_stats_pr: rlo2 must be [M, N] bf16");
+      rl = rlo2->contiguous();
+    }
   } else {
-    pre = at::zeros({N}, xs.options().dtype(at::kFloat));
+    TORCH_CHECK(residual.numel() == M * N, "amd_dft.", op, ": residual must have the output's shape");
+    r = residual.to(at::kFloat).contiguous();
   }
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = N;
-  at::Tensor y = at::empty(os, xs.options().dtype(at::kFloat));
-  at::Tensor part = at::empty({M, N / 64, 2}, xs.options().dtype(at::kFloat));
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(xs.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  at::Tensor rl;
-  if (rlo2_.has_value() && rlo2_->defined()) {
-    TORCH_CHECK(rlo2_->scalar_type() == at::kBFloat16 && rlo2_->numel() == M * N,
-                "amd_dft.linear3_stats_pr: rlo2 must be [M, N] bf16");
-    rl = rlo2_->contiguous();
-  }
-  p.residual = rp.data_ptr();
-  p.res_mean = rs.data_ptr<float>();
-  p.res_lo2 = rl.defined() ? reinterpret_cast<const uint16_t*>(rl.data_ptr()) : nullptr;
-  p.y = y.data_ptr();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.split = 1;
-  p.out = 1;
-  p.stats_part = part.data_ptr<float>();
-  p.stats_pre = pre.data_ptr<float>();
-  if (M > 0) launch_gemm(p, c10::hip::getCurrentHIPStream(xs.device().index()).stream());
+  at::Tensor pre = stats_pre(op, pre_, N, xs);
+  auto [y, part] = stats_outputs(xs, N, at::kFloat);
+  Gemm g(xs, ws, at::Tensor(), y, M, N, K);
+  g.split = 1;
+  g.out = 1;
+  g.residual = r.data_ptr();
+  g.res_mean = rstats ? rs.data_ptr<float>() : nullptr;
+  g.res_lo2 = reinterpret_cast<const uint16_t*>(data_or_null(rl));
+  g.stats_part = part.data_ptr<float>();
+  g.stats_pre = pre.data_ptr<float>();
+  g.run(xs.device());
   return {y, part};
+}
+
+std::tuple<at::Tensor, at::Tensor> linear3_stats_cuda(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& residual,
+                                                      const c10::optional<at::Tensor>& pre) {
+  return gemm3_stats("linear3_stats", xs, ws, residual, nullptr, c10::nullopt, pre);
+}
+
+std::tuple<at::Tensor, at::Tensor> linear3_stats_pr_cuda(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& rpairs,
+                                                         const at::Tensor& rstats, const c10::optional<at::Tensor>& pre,
+                                                         const c10::optional<at::Tensor>& rlo2) {
+  return gemm3_stats("linear3_stats_pr", xs, ws, rpairs, &rstats, rlo2, pre);
+}
+
+std::tuple<at::Tensor, at::Tensor> linear3_stats_meta(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor&,
+                                                      const c10::optional<at::Tensor>&) {
+  return stats_outputs(xs, ws.size(0), at::kFloat);
 }
 
 std::tuple<at::Tensor, at::Tensor> linear3_stats_pr_meta(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor&,
                                                          const at::Tensor&, const c10::optional<at::Tensor>&,
                                                          const c10::optional<at::Tensor>&) {
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = ws.size(0);
-  const int64_t M = xs.numel() / std::max<int64_t>(xs.size(-1), 1);
-  return {at::empty(os, xs.options().dtype(at::kFloat)), at::empty({M, ws.size(0) / 64, 2}, xs.options().dtype(at::kFloat))};
-}
-
-std::tuple<at::Tensor, at::Tensor> linear3_stats_meta(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor&,
-                                                      const c10::optional<at::Tensor>&) {
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = ws.size(0);
-  const int64_t M = xs.numel() / std::max<int64_t>(xs.size(-1), 1);
-  return {at::empty(os, xs.options().dtype(at::kFloat)), at::empty({M, ws.size(0) / 64, 2}, xs.options().dtype(at::kFloat))};
-}
-
-// fc2 of the bf16 FourCastNet block: y = x w^T + residual (bf16) and, from the same epilogue, the
-// next LayerNorm's partial statistics of y + pre -- taken on the stored (bf16-rounded) y, so they
-// describe exactly the tensor that LayerNorm reads: part [M, N/64, 2] = per 64-feature chunk
-// (mean, M2), merged by ln_stats_merge (replaces an ln_stats pass over y)
-std::tuple<at::Tensor, at::Tensor> chunk_partials(const at::Tensor& y, const c10::optional<at::Tensor>& pre, int64_t N) {
-  at::Tensor w = y.to(at::kFloat).reshape({-1, N});
-  if (pre.has_value() && pre->defined()) w = w + pre->to(at::kFloat).reshape({1, N});
-  w = w.reshape({w.size(0), N / 64, 64});
-  at::Tensor mean = w.mean(2);
-  at::Tensor m2 = (w - mean.unsqueeze(2)).pow(2).sum(2);
-  return {y, at::stack({mean, m2}, 2).contiguous()};
-}
-
-std::tuple<at::Tensor, at::Tensor> linear_stats_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& residual,
-                                                    const c10::optional<at::Tensor>& pre) {
-  TORCH_CHECK(w.dim() == 2 && x.size(-1) == w.size(1), "amd_dft.linear_stats: x [..., K], w [N, K]");
-  const int64_t N = w.size(0);
-  TORCH_CHECK(N % 64 == 0, "amd_dft.linear_stats: N must be a multiple of 64");
-  TORCH_CHECK(!pre.has_value() || !pre->defined() || pre->numel() == N, "amd_dft.linear_stats: pre must have N entries");
-  return chunk_partials(linear_ref(x, w, c10::nullopt, 0, residual), pre, N);
-}
-
-std::tuple<at::Tensor, at::Tensor> linear_stats_cuda(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& residual,
-                                                     const c10::optional<at::Tensor>& pre_) {
-  const c10::DeviceGuard guard(x_.device());
-  TORCH_CHECK(w_.dim() == 2 && x_.size(-1) == w_.size(1), "amd_dft.linear_stats: x [..., K], w [N, K]");
-  const int64_t K = w_.size(1), N = w_.size(0), M = x_.numel() / std::max<int64_t>(K, 1);
-  TORCH_CHECK(N % 64 == 0, "amd_dft.linear_stats: N must be a multiple of 64");
-  TORCH_CHECK(residual.numel() == M * N, "amd_dft.linear_stats: residual must have the output's shape");
-  TORCH_CHECK(!pre_.has_value() || !pre_->defined() || pre_->numel() == N, "amd_dft.linear_stats: pre must have N entries");
-  if (x_.scalar_type() != at::kBFloat16 || w_.scalar_type() != at::kBFloat16 || !gemm_supported(M, N, K)) {
-    fallback_note("linear_stats", "needs bf16 operands, N % 64 == 0, K % 64 == 0");
-    return chunk_partials(linear_ref(x_, w_, c10::nullopt, 0, residual), pre_, N);
-  }
-  at::Tensor x = x_.contiguous(), w = w_.contiguous(), r = residual.to(at::kBFloat16).contiguous();
-  // the kernel always reads pre (zeros when absent): see linear3_stats
-  at::Tensor pre = pre_.has_value() && pre_->defined() ? pre_->to(at::kFloat).contiguous()
-                                                       : at::zeros({N}, x.options().dtype(at::kFloat));
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  os.back() = N;
-  at::Tensor y = at::empty(os, x.options());
-  at::Tensor part = at::empty({M, N / 64, 2}, x.options().dtype(at::kFloat));
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(w.data_ptr());
-  p.residual = r.data_ptr();
-  p.y = y.data_ptr();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.stats_part = part.data_ptr<float>();
-  p.stats_pre = pre.data_ptr<float>();
-  if (M > 0) launch_gemm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-  return {y, part};
-}
-
-std::tuple<at::Tensor, at::Tensor> linear_stats_meta(const at::Tensor& x, const at::Tensor& w, const at::Tensor&,
-                                                     const c10::optional<at::Tensor>&) {
-  std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
-  os.back() = w.size(0);
-  const int64_t M = x.numel() / std::max<int64_t>(x.size(-1), 1);
-  return {at::empty(os, x.options()), at::empty({M, w.size(0) / 64, 2}, x.options().dtype(at::kFloat))};
+  return stats_outputs(xs, ws.size(0), at::kFloat);
 }
 
 // fc1 of the fp32 FourCastNet block: y = split(act(LN(x) W^T + b)) from the split pairs of the RAW
@@ -674,10 +670,9 @@ std::tuple<at::Tensor, at::Tensor> linear_stats_meta(const at::Tensor& x, const 
 // stats [M, 2] = (mean, rstd) of x.  Output: split-pair rows (the next GEMM's operand).
 void check_linear3_ln(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& c1, const c10::optional<at::Tensor>& bias,
                       const at::Tensor& stats, int64_t act) {
-  check_split_linear(xs, ws, bias, "linear3_ln");
-  TORCH_CHECK(act == 0 || act == 1, "amd_dft.linear3_ln: act must be 0 (none) or 1 (gelu)");
-  TORCH_CHECK(xs.size(-1) == ws.size(1), "amd_dft.linear3_ln: xs [..., 2K], ws [N, 2K]");
-  const int64_t N = ws.size(0), M = xs.numel() / std::max<int64_t>(ws.size(1), 1);
+  check_split_rows(xs, ws, bias, "linear3_ln");
+  check_act("linear3_ln", act, 1);
+  const int64_t N = ws.size(0), M = rows(xs, ws.size(1));
   TORCH_CHECK(c1.numel() == N, "amd_dft.linear3_ln: c1 must have N entries");
   TORCH_CHECK(stats.numel() == 2 * M && stats.size(-1) == 2, "amd_dft.linear3_ln: stats must be [M, 2] (mean, rstd)");
 }
@@ -685,53 +680,22 @@ void check_linear3_ln(const at::Tensor& xs, const at::Tensor& ws, const at::Tens
 at::Tensor linear3_ln_cpu(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor& c1, const c10::optional<at::Tensor>& bias,
                           const at::Tensor& stats, int64_t act) {
   check_linear3_ln(xs, ws, c1, bias, stats, act);
-  at::Tensor y = linear_ln_ref(unsplit_rows(xs), unsplit_rows(ws), c1, bias, stats, act);
-  return split_ref(y, true);
+  return split_ref(linear_ln_ref(unsplit_rows(xs), unsplit_rows(ws), c1, bias, stats, act), true);
 }
 
 at::Tensor linear3_ln_cuda(const at::Tensor& xs_, const at::Tensor& ws_, const at::Tensor& c1_,
                            const c10::optional<at::Tensor>& bias, const at::Tensor& stats_, int64_t act) {
   const c10::DeviceGuard guard(xs_.device());
   check_linear3_ln(xs_, ws_, c1_, bias, stats_, act);
-  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = xs_.numel() / std::max<int64_t>(2 * K, 1);
+  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = rows(xs_, 2 * K);
   TORCH_CHECK(gemm_supported(M, N, K), "amd_dft.linear3_ln: the bf16x3 GEMM needs N % 64 == 0 and K % 64 == 0 (got N=",
               N, ", K=", K, ")");
-  at::Tensor xs = xs_.contiguous(), ws = ws_.contiguous();
-  at::Tensor c1 = c1_.to(at::kFloat).contiguous(), stats = stats_.to(at::kFloat).contiguous();
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = 2 * N;
-  at::Tensor y = at::empty(os, xs.options());
-  at::Tensor b;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  GemmLaunch p;
-  p.x = reinterpret_cast<const uint16_t*>(xs.data_ptr());
-  p.w = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  p.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  p.y = y.data_ptr();
-  p.ln_stats = stats.data_ptr<float>();
-  p.ln_c1 = c1.data_ptr<float>();
-  p.M = static_cast<int>(M);
-  p.N = static_cast<int>(N);
-  p.K = static_cast<int>(K);
-  p.act = static_cast<int>(act);
-  p.split = 1;
-  p.out = 2;
-  if (M > 0) launch_gemm(p, c10::hip::getCurrentHIPStream(xs.device().index()).stream());
-  return y;
+  return gemm_ln(xs_, ws_, c1_, bias, stats_, act, M, N, K, true);
 }
 
 at::Tensor linear3_ln_meta(const at::Tensor& xs, const at::Tensor& ws, const at::Tensor&, const c10::optional<at::Tensor>&,
                            const at::Tensor&, int64_t) {
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = 2 * ws.size(0);
-  return at::empty(os, xs.options());
-}
-
-at::Tensor linear3_meta(const at::Tensor& xs, const at::Tensor& ws, const c10::optional<at::Tensor>&, int64_t,
-                        const c10::optional<at::Tensor>&, bool split_out) {
-  std::vector<int64_t> os(xs.sizes().begin(), xs.sizes().end());
-  os.back() = split_out ? 2 * ws.size(0) : ws.size(0);
-  return at::empty(os, xs.options().dtype(split_out ? at::kBFloat16 : at::kFloat));
+  return rows_like(xs, 2 * ws.size(0), xs.scalar_type());
 }
 
 // xs = split planes [2, B, C, h*p, w*p] of the fp32 image; ws [N, 2*C*p*p]; fp32 tokens [B*h*w, N]
@@ -750,15 +714,8 @@ at::Tensor patch_linear3_cpu(const at::Tensor& xs, const at::Tensor& ws, const c
   // the split pair of the raw image is exactly what the GEMM multiplies (hi + lo of each value)
   at::Tensor planes = raw ? split_ref(xs, false) : xs;
   at::Tensor x = planes.select(0, 0).to(at::kFloat) + planes.select(0, 1).to(at::kFloat);
-  at::Tensor t = patchify_cpu(x, p);
-  at::Tensor y = at::linear(t, unsplit_rows(ws),
-                            bias.has_value() && bias->defined() ? c10::optional<at::Tensor>(bias->to(at::kFloat))
-                                                                : c10::nullopt);
-  if (pos.has_value() && pos->defined()) {
-    const int64_t hw = (x.size(2) / p) * (x.size(3) / p);
-    y = (y.reshape({-1, hw, ws.size(0)}) + pos->to(at::kFloat).reshape({1, hw, ws.size(0)})).reshape({-1, ws.size(0)});
-  }
-  return y.contiguous();
+  at::Tensor y = linear_f32(patchify_cpu(x, p), unsplit_rows(ws), bias);
+  return add_pos(y, pos, (x.size(2) / p) * (x.size(3) / p)).contiguous();
 }
 
 at::Tensor patch_linear3_cuda(const at::Tensor& xs_, const at::Tensor& ws_, const c10::optional<at::Tensor>& bias,
@@ -773,32 +730,8 @@ at::Tensor patch_linear3_cuda(const at::Tensor& xs_, const at::Tensor& ws_, cons
   const int64_t M = B * h * w, K = C * p * p;
   TORCH_CHECK(p == 8 && ws_.size(1) == 2 * K && gemm_supported(M, N, K) && xs_.numel() < (int64_t(1) << 31),
               "amd_dft.patch_linear3: needs p == 8, ws [N, 2*C*64], N % 64 == 0 and < 2^31 image elements");
-  at::Tensor xs = raw ? split_bf16_cuda(xs_, false) : xs_.contiguous(), ws = ws_.contiguous();
-  at::Tensor y = at::empty({M, N}, xs.options().dtype(at::kFloat));
-  at::Tensor b, r;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  if (pos.has_value() && pos->defined()) {
-    TORCH_CHECK(pos->numel() == h * w * N, "amd_dft.patch_linear3: pos must be [h*w, N]");
-    r = pos->to(at::kFloat).contiguous();
-  }
-  GemmLaunch g;
-  g.x = reinterpret_cast<const uint16_t*>(xs.data_ptr());
-  g.w = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  g.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  g.residual = r.defined() ? r.data_ptr() : nullptr;
-  g.res_rows = static_cast<int>(h * w);
-  g.y = y.data_ptr();
-  g.M = static_cast<int>(M);
-  g.N = static_cast<int>(N);
-  g.K = static_cast<int>(K);
-  g.gC = static_cast<int>(C);
-  g.gh = static_cast<int>(h);
-  g.gw = static_cast<int>(w);
-  g.split = 1;
-  g.out = 1;
-  g.x_lo = xs.numel() / 2;
-  launch_gemm(g, c10::hip::getCurrentHIPStream(xs.device().index()).stream());
-  return y;
+  at::Tensor xs = raw ? split_bf16_cuda(xs_, false) : xs_.contiguous();
+  return gemm_patch("amd_dft.patch_linear3", xs, ws_, bias, pos, M, N, C, h, w, true);
 }
 
 at::Tensor patch_linear3_meta(const at::Tensor& xs, const at::Tensor& ws, const c10::optional<at::Tensor>&,
@@ -810,47 +743,17 @@ at::Tensor patch_linear3_meta(const at::Tensor& xs, const at::Tensor& ws, const 
 at::Tensor linear_unpatch3_cpu(const at::Tensor& ts, const at::Tensor& ws, const c10::optional<at::Tensor>& bias,
                                int64_t C, int64_t h, int64_t wd, int64_t p) {
   check_split_linear(ts, ws, bias, "linear_unpatch3");
-  at::Tensor y = at::linear(unsplit_rows(ts), unsplit_rows(ws),
-                            bias.has_value() && bias->defined() ? c10::optional<at::Tensor>(bias->to(at::kFloat))
-                                                                : c10::nullopt);
-  return unpatchify_cpu(y, C, h, wd, p);
+  return unpatchify_cpu(linear_f32(unsplit_rows(ts), unsplit_rows(ws), bias), C, h, wd, p);
 }
 
 at::Tensor linear_unpatch3_cuda(const at::Tensor& ts_, const at::Tensor& ws_, const c10::optional<at::Tensor>& bias,
                                 int64_t C, int64_t h, int64_t wd, int64_t p) {
   const c10::DeviceGuard guard(ts_.device());
   check_split_linear(ts_, ws_, bias, "linear_unpatch3");
-  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = ts_.numel() / std::max<int64_t>(2 * K, 1);
+  const int64_t K = ws_.size(1) / 2, N = ws_.size(0), M = rows(ts_, 2 * K);
   TORCH_CHECK(ts_.size(-1) == 2 * K && N == C * p * p && p == 8 && M % (h * wd) == 0 && gemm_supported(M, N, K),
               "amd_dft.linear_unpatch3: ts [..., 2K], ws [C*64, 2K] in (c, py, px) order, p == 8");
-  at::Tensor ts = ts_.contiguous(), ws = ws_.contiguous();
-  const int64_t B = M / (h * wd);
-  at::Tensor y = at::empty({B, C, h * p, wd * p}, ts.options().dtype(at::kFloat));
-  at::Tensor b;
-  if (bias.has_value() && bias->defined()) b = bias->to(at::kFloat).contiguous();
-  const bool ragged = N % 256 != 0;  // see linear_unpatch_cuda
-  at::Tensor yt = ragged ? at::empty({M, N}, ts.options().dtype(at::kFloat)) : at::Tensor();
-  GemmLaunch g;
-  g.x = reinterpret_cast<const uint16_t*>(ts.data_ptr());
-  g.w = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  g.bias = b.defined() ? b.data_ptr<float>() : nullptr;
-  g.y = ragged ? yt.data_ptr() : y.data_ptr();
-  g.M = static_cast<int>(M);
-  g.N = static_cast<int>(N);
-  g.K = static_cast<int>(K);
-  if (!ragged) {
-    g.sC = static_cast<int>(C);
-    g.sh = static_cast<int>(h);
-    g.sw = static_cast<int>(wd);
-  }
-  g.split = 1;
-  g.out = 1;
-  auto stream = c10::hip::getCurrentHIPStream(ts.device().index()).stream();
-  launch_gemm(g, stream);
-  if (ragged)
-    launch_patch_remap(yt.data_ptr(), y.data_ptr(), B, static_cast<int>(C), static_cast<int>(h), static_cast<int>(wd),
-                       false, stream, 4);
-  return y;
+  return gemm_unpatch(ts_, ws_, bias, M, N, K, C, h, wd, true);
 }
 
 at::Tensor linear_unpatch3_meta(const at::Tensor& ts, const at::Tensor& ws, const c10::optional<at::Tensor>&, int64_t C,
@@ -861,68 +764,30 @@ at::Tensor linear_unpatch3_meta(const at::Tensor& ts, const at::Tensor& ws, cons
 }  // namespace
 }  // namespace amd_dft
 
-TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
-  m.def("patchify(Tensor x, int p) -> Tensor");
-  m.def("unpatchify(Tensor t, int C, int h, int w, int p) -> Tensor");
-  m.def("linear(Tensor x, Tensor w, Tensor? bias=None, int act=0, Tensor? residual=None) -> Tensor");
-  m.def("linear_ln(Tensor x, Tensor w, Tensor c1, Tensor? bias, Tensor stats, int act=0) -> Tensor");
-  m.def("patch_linear(Tensor x, Tensor w, Tensor? bias=None, Tensor? pos=None, int p=8) -> Tensor");
-  m.def("linear_unpatch(Tensor t, Tensor w, Tensor? bias, int C, int h, int w, int p=8) -> Tensor");
-  m.def("split_bf16(Tensor x, bool rows=True) -> Tensor");
-  m.def("linear3(Tensor xs, Tensor ws, Tensor? bias=None, int act=0, Tensor? residual=None, bool split_out=False) -> Tensor");
-  m.def("linear3_stats(Tensor xs, Tensor ws, Tensor residual, Tensor? pre=None) -> (Tensor, Tensor)");
-  m.def("linear3_stats_pr(Tensor xs, Tensor ws, Tensor rpairs, Tensor rstats, Tensor? pre=None, Tensor? rlo2=None) -> "
-        "(Tensor, Tensor)");
-  m.def("linear_stats(Tensor x, Tensor w, Tensor residual, Tensor? pre=None) -> (Tensor, Tensor)");
-  m.def("linear3_ln(Tensor xs, Tensor ws, Tensor c1, Tensor? bias, Tensor stats, int act=0) -> Tensor");
-  m.def("patch_linear3(Tensor xs, Tensor ws, Tensor? bias=None, Tensor? pos=None, int p=8) -> Tensor");
-  m.def("linear_unpatch3(Tensor ts, Tensor ws, Tensor? bias, int C, int h, int w, int p=8) -> Tensor");
-}
-TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
-  m.impl("patchify", AMD_DFT_TRACED("amd_dft::patchify", amd_dft::patchify_cuda));
-  m.impl("unpatchify", AMD_DFT_TRACED("amd_dft::unpatchify", amd_dft::unpatchify_cuda));
-  m.impl("linear", AMD_DFT_TRACED("amd_dft::linear", amd_dft::linear_cuda));
-  m.impl("linear_ln", AMD_DFT_TRACED("amd_dft::linear_ln", amd_dft::linear_ln_cuda));
-  m.impl("patch_linear", AMD_DFT_TRACED("amd_dft::patch_linear", amd_dft::patch_linear_cuda));
-  m.impl("linear_unpatch", AMD_DFT_TRACED("amd_dft::linear_unpatch", amd_dft::linear_unpatch_cuda));
-  m.impl("split_bf16", AMD_DFT_TRACED("amd_dft::split_bf16", amd_dft::split_bf16_cuda));
-  m.impl("linear3", AMD_DFT_TRACED("amd_dft::linear3", amd_dft::linear3_cuda));
-  m.impl("linear3_stats", AMD_DFT_TRACED("amd_dft::linear3_stats", amd_dft::linear3_stats_cuda));
-  m.impl("linear3_stats_pr", AMD_DFT_TRACED("amd_dft::linear3_stats_pr", amd_dft::linear3_stats_pr_cuda));
-  m.impl("linear_stats", AMD_DFT_TRACED("amd_dft::linear_stats", amd_dft::linear_stats_cuda));
-  m.impl("linear3_ln", AMD_DFT_TRACED("amd_dft::linear3_ln", amd_dft::linear3_ln_cuda));
-  m.impl("patch_linear3", AMD_DFT_TRACED("amd_dft::patch_linear3", amd_dft::patch_linear3_cuda));
-  m.impl("linear_unpatch3", AMD_DFT_TRACED("amd_dft::linear_unpatch3", amd_dft::linear_unpatch3_cuda));
-}
-TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
-  m.impl("patchify", AMD_DFT_TRACED("amd_dft::patchify", amd_dft::patchify_cpu));
-  m.impl("unpatchify", AMD_DFT_TRACED("amd_dft::unpatchify", amd_dft::unpatchify_cpu));
-  m.impl("linear", AMD_DFT_TRACED("amd_dft::linear", amd_dft::linear_cpu));
-  m.impl("linear_ln", AMD_DFT_TRACED("amd_dft::linear_ln", amd_dft::linear_ln_cpu));
-  m.impl("patch_linear", AMD_DFT_TRACED("amd_dft::patch_linear", amd_dft::patch_linear_cpu));
-  m.impl("linear_unpatch", AMD_DFT_TRACED("amd_dft::linear_unpatch", amd_dft::linear_unpatch_cpu));
-  m.impl("split_bf16", AMD_DFT_TRACED("amd_dft::split_bf16", amd_dft::split_bf16_cpu));
-  m.impl("linear3", AMD_DFT_TRACED("amd_dft::linear3", amd_dft::linear3_cpu));
-  m.impl("linear3_stats", AMD_DFT_TRACED("amd_dft::linear3_stats", amd_dft::linear3_stats_cpu));
-  m.impl("linear3_stats_pr", AMD_DFT_TRACED("amd_dft::linear3_stats_pr", amd_dft::linear3_stats_pr_cpu));
-  m.impl("linear_stats", AMD_DFT_TRACED("amd_dft::linear_stats", amd_dft::linear_stats_cpu));
-  m.impl("linear3_ln", AMD_DFT_TRACED("amd_dft::linear3_ln", amd_dft::linear3_ln_cpu));
-  m.impl("patch_linear3", AMD_DFT_TRACED("amd_dft::patch_linear3", amd_dft::patch_linear3_cpu));
-  m.impl("linear_unpatch3", AMD_DFT_TRACED("amd_dft::linear_unpatch3", amd_dft::linear_unpatch3_cpu));
-}
-TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
-  m.impl("patchify", &amd_dft::patchify_meta);
-  m.impl("unpatchify", &amd_dft::unpatchify_meta);
-  m.impl("linear", &amd_dft::linear_meta);
-  m.impl("linear_ln", &amd_dft::linear_ln_meta);
-  m.impl("patch_linear", &amd_dft::patch_linear_meta);
-  m.impl("linear_unpatch", &amd_dft::linear_unpatch_meta);
-  m.impl("split_bf16", &amd_dft::split_bf16_meta);
-  m.impl("linear3", &amd_dft::linear3_meta);
-  m.impl("linear3_stats", &amd_dft::linear3_stats_meta);
-  m.impl("linear3_stats_pr", &amd_dft::linear3_stats_pr_meta);
-  m.impl("linear_stats", &amd_dft::linear_stats_meta);
-  m.impl("linear3_ln", &amd_dft::linear3_ln_meta);
-  m.impl("patch_linear3", &amd_dft::patch_linear3_meta);
-  m.impl("linear_unpatch3", &amd_dft::linear_unpatch3_meta);
-}
+// The ops of this file, once: name and schema.  Each has name_cuda, name_cpu and name_meta above, so an
+// op missing from one backend fails to compile.
+#define AMD_DFT_NN_OPS(X)                                                                                             \
+  X(patchify, "(Tensor x, int p) -> Tensor")                                                                          \
+  X(unpatchify, "(Tensor t, int C, int h, int w, int p) -> Tensor")                                                   \
+  X(linear, "(Tensor x, Tensor w, Tensor? bias=None, int act=0, Tensor? residual=None) -> Tensor")                    \
+  X(linear_ln, "(Tensor x, Tensor w, Tensor c1, Tensor? bias, Tensor stats, int act=0) -> Tensor")                    \
+  X(patch_linear, "(Tensor x, Tensor w, Tensor? bias=None, Tensor? pos=None, int p=8) -> Tensor")                     \
+  X(linear_unpatch, "(Tensor t, Tensor w, Tensor? bias, int C, int h, int w, int p=8) -> Tensor")                     \
+  X(split_bf16, "(Tensor x, bool rows=True) -> Tensor")                                                               \
+  X(linear3, "(Tensor xs, Tensor ws, Tensor? bias=None, int act=0, Tensor? residual=None, bool split_out=False) -> Tensor") \
+  X(linear3_stats, "(Tensor xs, Tensor ws, Tensor residual, Tensor? pre=None) -> (Tensor, Tensor)")                   \
+  X(linear3_stats_pr, "(Tensor xs, Tensor ws, Tensor rpairs, Tensor rstats, Tensor? pre=None, Tensor? rlo2=None) -> " \
+                      "(Tensor, Tensor)")                                                                             \
+  X(linear_stats, "(Tensor x, Tensor w, Tensor residual, Tensor? pre=None) -> (Tensor, Tensor)")                      \
+  X(linear3_ln, "(Tensor xs, Tensor ws, Tensor c1, Tensor? bias, Tensor stats, int act=0) -> Tensor")                 \
+  X(patch_linear3, "(Tensor xs, Tensor ws, Tensor? bias=None, Tensor? pos=None, int p=8) -> Tensor")                  \
+  X(linear_unpatch3, "(Tensor ts, Tensor ws, Tensor? bias, int C, int h, int w, int p=8) -> Tensor")
+
+#define AMD_DFT_DEF(op, schema) m.def(#op schema);
+#define AMD_DFT_IMPL_CUDA(op, schema) m.impl(#op, AMD_DFT_TRACED("amd_dft::" #op, amd_dft::op##_cuda));
+#define AMD_DFT_IMPL_CPU(op, schema) m.impl(#op, AMD_DFT_TRACED("amd_dft::" #op, amd_dft::op##_cpu));
+#define AMD_DFT_IMPL_META(op, schema) m.impl(#op, &amd_dft::op##_meta);
+TORCH_LIBRARY_FRAGMENT(amd_dft, m) { AMD_DFT_NN_OPS(AMD_DFT_DEF) }
+TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) { AMD_DFT_NN_OPS(AMD_DFT_IMPL_CUDA) }
+TORCH_LIBRARY_IMPL(amd_dft, CPU, m) { AMD_DFT_NN_OPS(AMD_DFT_IMPL_CPU) }
+TORCH_LIBRARY_IMPL(amd_dft, Meta, m) { AMD_DFT_NN_OPS(AMD_DFT_IMPL_META) }

@@ -164,8 +164,8 @@ at::Tensor fno_pointwise_cpu(const c10::optional<at::Tensor>& spec, const at::Te
   TORCH_CHECK(w2.size(1) == Cin, "fno_pointwise: weight must be [Cout, Cin]");
   at::Tensor xf = x.to(at::kFloat).reshape({B, Cin, -1});
   at::Tensor y = at::einsum("oi,bip->bop", {w2, xf});
-  if (bias.has_value() && bias->defined()) y = y + bias->to(at::kFloat).reshape({1, -1, 1});
-  if (spec.has_value() && spec->defined()) y = y + spec->to(at::kFloat).reshape({B, w2.size(0), -1});
+  if (present(bias)) y = y + bias->to(at::kFloat).reshape({1, -1, 1});
+  if (present(spec)) y = y + spec->to(at::kFloat).reshape({B, w2.size(0), -1});
   if (gelu) y = at::gelu(y);
   std::vector<int64_t> shape = x.sizes().vec();
   shape[1] = w2.size(0);
@@ -188,12 +188,11 @@ at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec_, const at::
   TORCH_CHECK(P < (int64_t(1) << 31) / 4 && B <= 65535, "fno_pointwise: tensor too large");
   at::Tensor x = x_.contiguous();
   at::Tensor spec;
-  if (spec_.has_value() && spec_->defined()) {
+  if (present(spec_)) {
     TORCH_CHECK(spec_->numel() == B * Cout * P, "fno_pointwise: spec must be [B, Cout, ...] like the output");
     spec = spec_->to(x.scalar_type()).contiguous();
   }
-  at::Tensor bf;
-  if (bias.has_value() && bias->defined()) bf = bias->to(at::kFloat).contiguous();
+  at::Tensor bf = f32_or_undef(bias);
   std::vector<int64_t> shape = x.sizes().vec();
   shape[1] = Cout;
   at::Tensor y = at::empty(shape, x.options());
@@ -266,8 +265,7 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
   // the tail kernel reads 4 modes per 16-byte load: a view at an odd float2 offset gets its own copy
   if (reinterpret_cast<uintptr_t>(yw.data_ptr()) % 16 != 0) yw = yw.clone();
   at::Tensor wc = wc_.to(at::kFloat).reshape({Cout, Cin}).contiguous();
-  at::Tensor bf;
-  if (bias.has_value() && bias->defined()) bf = bias->to(at::kFloat).contiguous();
+  at::Tensor bf = f32_or_undef(bias);
   at::Tensor y = at::empty({B, Cout, H, W}, x.options());
   auto tabs = get_dft_gemm_tables(x.scalar_type() == at::kBFloat16 ? DftTable::C2R_BF16 : DftTable::C2R_F32,
                                   static_cast<int>(W), static_cast<int>(m), x.device());

@@ -170,3 +170,125 @@ def test_linear_gelu_erf_fit_gpu(device):
     assert rel_l2(y, ref) < 4e-3  # bf16 output rounding
     yt = torch.ops.amd_dft.linear(x, w, b, 2).float()
     assert rel_l2(y, ref) <= rel_l2(yt, ref)
+
+
+# ------------------------------------------------------------------ Meta and CPU implementations agree
+def _meta_cases():
+    """(id, op, args) for every op of csrc/ops/nn_ops.cpp: the smallest shapes the ops accept with a ragged
+    256-panel (N = 128), a multi-dim leading shape and, for the patch ops, a non-square 2 x 3 patch grid."""
+    bf = torch.bfloat16
+    x, w, b = torch.randn(2, 3, 64), torch.randn(128, 64) / 8, torch.randn(128)
+    r, pre, c1 = torch.randn(2, 3, 128), torch.randn(128), torch.randn(128)
+    stats = torch.stack([torch.zeros(6), torch.ones(6)], -1)
+    xs, ws = torch.ops.amd_dft.split_bf16(x, True), torch.ops.amd_dft.split_bf16(w, True)
+    img = torch.randn(1, 2, 16, 24)  # C = 2, h = 2, w = 3 at p = 8: K = 128
+    pw, pb, pos = torch.randn(64, 128) / 8, torch.randn(64), torch.randn(6, 64)
+    pws = torch.ops.amd_dft.split_bf16(pw, True)
+    uw, ub = torch.randn(64, 64) / 8, torch.randn(64)  # linear_unpatch*: C = 1, N = 64
+    uws = torch.ops.amd_dft.split_bf16(uw, True)
+    return [
+        ("patchify", "patchify", (img, 8)),
+        ("unpatchify", "unpatchify", (torch.randn(1, 2, 3, 128), 2, 2, 3, 8)),
+        ("linear", "linear", (x, w, b, 1, r)),
+        ("linear-bf16", "linear", (x.to(bf), w.to(bf), None, 0, None)),
+        ("linear_ln", "linear_ln", (x, w, c1, b, stats, 1)),
+        ("patch_linear", "patch_linear", (img, pw, pb, pos, 8)),
+        ("linear_unpatch", "linear_unpatch", (x, uw, ub, 1, 2, 3, 8)),
+        ("split_bf16-rows", "split_bf16", (x, True)),
+        ("split_bf16-planes", "split_bf16", (x, False)),
+        ("linear3", "linear3", (xs, ws, b, 1, r, False)),
+        ("linear3-split_out", "linear3", (xs, ws, b, 1, None, True)),
+        ("linear3_stats", "linear3_stats", (xs, ws, r, pre)),
+        ("linear3_stats_pr", "linear3_stats_pr", (xs, ws, torch.ops.amd_dft.split_bf16(r.reshape(6, 128), True), stats,
+                                                  pre, torch.zeros(6, 128, dtype=bf))),
+        ("linear_stats", "linear_stats", (x.to(bf), w.to(bf), r.to(bf), pre)),
+        ("linear3_ln", "linear3_ln", (xs, ws, c1, b, stats, 1)),
+        ("patch_linear3-planes", "patch_linear3", (torch.ops.amd_dft.split_bf16(img, False), pws, pb, pos, 8)),
+        ("patch_linear3-raw", "patch_linear3", (img, pws, pb, pos, 8)),
+        ("linear_unpatch3", "linear_unpatch3", (xs, uws, ub, 1, 2, 3, 8)),
+    ]
+
+
+_META_IDS = ["patchify", "unpatchify", "linear", "linear-bf16", "linear_ln", "patch_linear", "linear_unpatch",
+             "split_bf16-rows", "split_bf16-planes", "linear3", "linear3-split_out", "linear3_stats", "linear3_stats_pr",
+             "linear_stats", "linear3_ln", "patch_linear3-planes", "patch_linear3-raw", "linear_unpatch3"]
+
+
+@pytest.mark.parametrize("case", _META_IDS)
+def test_nn_ops_meta_matches_cpu(case):
+    """Every op's Meta kernel reports the shapes and dtypes its CPU kernel returns (tuples element by element)."""
+    torch.manual_seed(0)
+    cases = _meta_cases()
+    assert [c[0] for c in cases] == _META_IDS
+    assert {c[1] for c in cases} == {
+        "patchify", "unpatchify", "linear", "linear_ln", "patch_linear", "linear_unpatch", "split_bf16", "linear3",
+        "linear3_stats", "linear3_stats_pr", "linear_stats", "linear3_ln", "patch_linear3", "linear_unpatch3"}
+    _, name, args = cases[_META_IDS.index(case)]
+    op = getattr(torch.ops.amd_dft, name)
+    got = op(*args)
+    meta = op(*[a.to("meta") if isinstance(a, torch.Tensor) else a for a in args])
+    got, meta = (got, meta) if isinstance(got, tuple) else ((got,), (meta,))
+    assert len(got) == len(meta)
+    for g, m in zip(got, meta):
+        assert m.device.type == "meta"
+        assert m.shape == g.shape and m.dtype == g.dtype
+
+
+# ------------------------------------------------------------------ operand normalisation
+def _strided(t):
+    """A buffer twice as wide whose every other column holds t: buf[..., ::2] is t as a non-contiguous view."""
+    buf = torch.zeros(*t.shape[:-1], 2 * t.shape[-1], dtype=t.dtype)
+    buf[..., ::2] = t
+    return buf
+
+
+def _normalisation_outputs(dev, strided):
+    """linear / linear_stats / linear3 / linear3_stats at M=300, N=256, K=64 on ``dev``.  ``strided``: x and the
+    residual arrive as non-contiguous views and bias / pre as bf16 (the same, bf16-representable, values)."""
+    ops = torch.ops.amd_dft
+    bf = torch.bfloat16
+    torch.manual_seed(5)
+    M, N, K = 300, 256, 64
+    x, w, r = (torch.randn(M, K) * 0.5).to(bf), (torch.randn(N, K) / 8).to(bf), torch.randn(M, N).to(bf)
+    xs, ws = ops.split_bf16(torch.randn(M, K) * 0.5, True), ops.split_bf16(torch.randn(N, K) / 8, True)
+    rf = torch.randn(M, N)
+    b, pre = (torch.randn(N) * 0.1).to(bf), (torch.randn(N) * 0.1).to(bf)
+
+    def view(t):
+        if not strided:
+            return t.to(dev)
+        v = _strided(t).to(dev)[..., ::2]
+        assert not v.is_contiguous() and torch.equal(v.cpu(), t)
+        return v
+
+    def vec(t):
+        return t.to(dev) if strided else t.float().to(dev)
+
+    w, ws = w.to(dev), ws.to(dev)
+    out = [ops.linear(view(x), w, vec(b), 1, view(r))]
+    out += ops.linear_stats(view(x), w, view(r), vec(pre))
+    out += [ops.linear3(view(xs), ws, vec(b), 0, view(rf), False)]
+    out += ops.linear3_stats(view(xs), ws, view(rf), vec(pre))
+    return out
+
+
+@pytest.mark.gpu
+def test_operand_normalisation_reaches_kernel_unchanged(device):
+    """Contiguous operands with fp32 bias / pre, and the same values as non-contiguous views with bf16 bias / pre,
+    give bit-identical outputs on the hand GEMM: the wrappers' .contiguous() / dtype conversions hand the kernel the
+    same bytes (same kernel, one workgroup per tile, no atomics: no tolerance).  The CPU implementation is checked
+    first, so the inputs' construction cannot be what fails."""
+    from tensorrt_dft_plugins_amd.utils import strict_mode
+
+    cpu = torch.device("cpu")
+    for a, b in zip(_normalisation_outputs(cpu, False), _normalisation_outputs(cpu, True)):
+        assert torch.equal(a, b)
+    prev = strict_mode(True)
+    try:
+        plain, views = _normalisation_outputs(device, False), _normalisation_outputs(device, True)
+    finally:
+        strict_mode(prev)
+    assert len(plain) == len(views) == 6
+    for a, b in zip(plain, views):
+        assert a.shape == b.shape and a.dtype == b.dtype
+        assert torch.equal(a, b)
