@@ -28,8 +28,22 @@ struct FixedCfg {
 const std::vector<FixedCfg>& fixed_configs();
 // Radix order used for L by the fixed kernels (empty if L has no fixed config).
 std::vector<int32_t> fixed_radices(int32_t L);
+// The selection score: index in fixed_configs() of the configuration that a pass of this kind
+// and length over I inner signals and O outer indices runs (cols: column-like layout; radix: the
+// plan's radix order), or -1 when no configuration applies.
+int select_fixed_config(Kind kind, int32_t L, bool cols, int64_t I, int64_t O, const int32_t* radix, int32_t npass);
 // Launch the best fixed configuration for d; returns false when none applies.
 bool launch_fft_fixed(const PassDesc& d, void* stream);
+// What launch_fft_fixed(d) would launch, without touching a device; false when it would launch
+// nothing (the generic kernel runs).
+struct FixedLaunchInfo {
+  int cfg = -1;  // index in fixed_configs()
+  int64_t nblocks = 0;
+  int32_t tiles_per_outer = 0;
+  bool xcd = false;      // XCD-aware tile order
+  bool pairvec = false;  // paired-vector IO variant
+};
+bool describe_fft_fixed(const PassDesc& d, FixedLaunchInfo& info);
 
 
 }  // namespace amd_dft

@@ -86,34 +86,36 @@ const FixedKnobs& knobs() {
   return k;
 }
 
-// Picks the configuration for d and fills its kernel arguments; false if none applies.
-bool prepare_fixed(const PassDesc& d, int& best_out, FixedArgs& a, int64_t& nblocks_out) {
+}  // namespace
+
+// The selection score: index in fixed_configs() of the configuration a (kind, L, cols) pass over I
+// inner signals and O outer indices with this radix order runs, or -1 if none applies.
+int select_fixed_config(Kind kind, int32_t L, bool cols, int64_t I, int64_t O, const int32_t* radix, int32_t npass) {
   const FixedKnobs& kn = knobs();
-  if (!kn.enabled) return false;
-  const bool cols = d.Si_in < d.Sn_in || d.Si_out < d.Sn_out;
-  const bool paired = d.kind != Kind::C2C;
-  const int64_t nsig = paired ? (d.I + 1) / 2 : d.I;
+  if (!kn.enabled) return -1;
+  const bool paired = kind != Kind::C2C;
+  const int64_t nsig = paired ? (I + 1) / 2 : I;
   int force_tp = kn.force_tp, force_t = kn.force_t;
   const auto& cfgs = fixed_configs();
   if (force_tp) {  // the override only applies where such a configuration exists
     bool any = false;
-    for (const auto& c : cfgs) any |= c.L == d.L && c.cols == cols && c.TP == force_tp && c.T == force_t;
+    for (const auto& c : cfgs) any |= c.L == L && c.cols == cols && c.TP == force_tp && c.T == force_t;
     if (!any) force_tp = force_t = 0;
   }
   int best = -1;
   double best_score = -1e300;
   for (int i = 0; i < static_cast<int>(cfgs.size()); ++i) {
     const FixedCfg& c = cfgs[i];
-    if (c.L != d.L || c.cols != cols) continue;
-    if (c.npass != d.npass || !std::equal(c.radix, c.radix + c.npass, d.radix)) continue;
+    if (c.L != L || c.cols != cols) continue;
+    if (c.npass != npass || !std::equal(c.radix, c.radix + c.npass, radix)) continue;
     if (force_tp && (c.TP != force_tp || c.T != force_t)) continue;
-    const int64_t wgs = d.O * ((nsig + c.T - 1) / c.T);
+    const int64_t wgs = O * ((nsig + c.T - 1) / c.T);
     const int64_t waves = wgs * ((c.TP * c.T + 63) / 64);
     // enough waves to put >= 2 on every SIMD (1024 SIMDs), then the widest tile
     // (coalescing, fewer twiddle re-reads); otherwise the most waves.
     // Measured on the AFNO W-transforms ([32,90,180,768] bf16, bench/bench_afno_w.py): the
     // C2R with fused addends prefers 32-channel tiles, the R2C 16 (wider R2C tiles lose).
-    const int t_pref = (cols && d.kind == Kind::R2C) ? 16 : 1 << 30;
+    const int t_pref = (cols && kind == Kind::R2C) ? 16 : 1 << 30;
     const double tw = c.T <= t_pref ? c.T : -c.T;
     // Small problems (rfft2 720x1440 column pass: 721 columns): with the XCD-aware tile order
     // (tiles sharing a 128-B line run on one XCD, see xcd_block) 4-column tiles win
@@ -128,8 +130,20 @@ bool prepare_fixed(const PassDesc& d, int& best_out, FixedArgs& a, int64_t& nblo
       best = i;
     }
   }
+  return best;
+}
+
+namespace {
+
+// Picks the configuration for d and fills its kernel arguments; false if none applies.
+bool prepare_fixed(const PassDesc& d, int& best_out, FixedArgs& a, int64_t& nblocks_out) {
+  const FixedKnobs& kn = knobs();
+  const bool cols = d.Si_in < d.Sn_in || d.Si_out < d.Sn_out;
+  const bool paired = d.kind != Kind::C2C;
+  const int64_t nsig = paired ? (d.I + 1) / 2 : d.I;
+  const int best = select_fixed_config(d.kind, d.L, cols, d.I, d.O, d.radix, d.npass);
   if (best < 0) return false;
-  const FixedCfg& cfg = cfgs[best];
+  const FixedCfg& cfg = fixed_configs()[best];
   a = FixedArgs{};
   a.in = d.in;
   a.out = d.out;
@@ -197,6 +211,19 @@ bool prepare_fixed(const PassDesc& d, int& best_out, FixedArgs& a, int64_t& nblo
 }
 
 }  // namespace
+
+bool describe_fft_fixed(const PassDesc& d, FixedLaunchInfo& info) {
+  int best = -1;
+  FixedArgs a;
+  int64_t nblocks = 0;
+  if (!prepare_fixed(d, best, a, nblocks)) return false;
+  info.cfg = best;
+  info.nblocks = nblocks;
+  info.tiles_per_outer = a.tiles_per_outer;
+  info.xcd = a.xcd_nb > 0;
+  info.pairvec = a.pairvec != 0;
+  return true;
+}
 
 bool launch_fft_fixed(const PassDesc& d, void* stream) {
   int best = -1;

@@ -86,6 +86,14 @@ void run_pass_large(Kind kind, const at::Tensor& in, const at::Tensor& out, cons
                     const std::vector<int64_t>& out_shape, int axis, int64_t L, int in_lo, int in_hi, int out_lo,
                     int out_hi, float scale, bool inverse, const void* add1, const void* add2);
 
+// The kernels read a complex element with one load of the whole (re, im) pair.  A contiguous view
+// at an odd scalar offset into a larger buffer is aligned to one scalar only: copy it (allocations
+// are pair-aligned; a pointer test, no cost for an aligned tensor).
+at::Tensor pair_aligned(const at::Tensor& x) {
+  if (x.numel() == 0 || reinterpret_cast<uintptr_t>(x.data_ptr()) % (2 * x.element_size()) == 0) return x;
+  return x.clone(at::MemoryFormat::Contiguous);
+}
+
 int64_t lds_limit() {
   static const int64_t lim = max_lds_length();
   return lim;
@@ -468,7 +476,7 @@ at::Tensor c2r_cuda_impl(const at::Tensor& x_, at::IntArrayRef dim, at::IntArray
                          at::IntArrayRef keep, std::optional<at::ScalarType> out_dtype,
                          const std::optional<at::Tensor>& add1, const std::optional<at::Tensor>& add2) {
   const c10::DeviceGuard guard(x_.device());
-  at::Tensor x = x_.contiguous();
+  at::Tensor x = pair_aligned(x_.contiguous());
   to_dtype(x.scalar_type());
   const at::ScalarType odt = out_dtype.value_or(x.scalar_type());
   to_dtype(odt);
@@ -528,7 +536,7 @@ at::Tensor c2r_add_cuda(const at::Tensor& x, at::IntArrayRef dim, at::IntArrayRe
 at::Tensor c2c_cuda(const at::Tensor& x_, at::IntArrayRef dim, bool inverse, double scale,
                     std::optional<at::ScalarType> out_dtype) {
   const c10::DeviceGuard guard(x_.device());
-  at::Tensor x = x_.contiguous();
+  at::Tensor x = pair_aligned(x_.contiguous());
   TORCH_CHECK(x.dim() >= 2 && x.size(-1) == 2, "amd_dft: complex input must have a trailing dim of size 2");
   to_dtype(x.scalar_type());
   const at::ScalarType odt = out_dtype.value_or(x.scalar_type());
@@ -565,7 +573,7 @@ void check_c2c_axis(const at::Tensor& x, int64_t dim, int64_t n, int64_t in_lo, 
 at::Tensor c2c_axis_cuda(const at::Tensor& x_, int64_t dim, int64_t n, int64_t in_lo, int64_t in_hi, int64_t out_lo,
                          int64_t out_hi, bool inverse, double scale) {
   const c10::DeviceGuard guard(x_.device());
-  at::Tensor x = x_.contiguous();
+  at::Tensor x = pair_aligned(x_.contiguous());
   to_dtype(x.scalar_type());
   const int64_t nd = x.dim() - 1;
   dim = dim < 0 ? dim + nd : dim;
@@ -1235,6 +1243,93 @@ std::string plan_info(int64_t n) {
   return os.str();
 }
 
+Kind parse_kind(const std::string& kind, const char* op) {
+  if (kind == "r2c") return Kind::R2C;
+  if (kind == "c2r") return Kind::C2R;
+  TORCH_CHECK(kind == "c2c", "amd_dft.", op, ": kind must be r2c, c2r or c2c");
+  return Kind::C2C;
+}
+
+// Which kernel one full (unpruned) transform pass along `axis` would launch, from the functions
+// run_pass uses (make_plan_1d, apply_plan, set_axis_geometry, choose_tiling, the fixed kernels'
+// selection), on the host alone: no device, no allocation, pointers taken as aligned.  `shape` is
+// the pass input's logical shape (without the trailing re/im dim), `n` the transform length
+// (default: shape[axis]; for c2r 2 * (shape[axis] - 1)).
+std::string fft_pass_info(std::string kind_s, at::IntArrayRef shape, int64_t axis, int64_t n, bool bf16_in,
+                          bool bf16_out) {
+  const Kind kind = parse_kind(kind_s, "fft_pass_info");
+  const int64_t nd = static_cast<int64_t>(shape.size());
+  axis = axis < 0 ? axis + nd : axis;
+  TORCH_CHECK(axis >= 0 && axis < nd, "amd_dft.fft_pass_info: axis out of range");
+  for (int64_t v : shape) TORCH_CHECK(v >= 1, "amd_dft.fft_pass_info: empty shape");
+  const int64_t stored = shape[axis];
+  const int64_t L = n > 0 ? n : (kind == Kind::C2R ? 2 * (stored - 1) : stored);
+  TORCH_CHECK(L >= 1 && L < (1 << 30), "amd_dft.fft_pass_info: bad length");
+  if (L > lds_limit()) return "large L=" + std::to_string(L);
+  const int64_t half = L / 2 + 1;
+  TORCH_CHECK(kind == Kind::C2R || stored == L, "amd_dft.fft_pass_info: shape[axis] must be the transform length");
+  std::vector<int64_t> in_shape(shape.begin(), shape.end()), out_shape = in_shape;
+  out_shape[axis] = kind == Kind::R2C ? half : L;
+  Plan1D plan = make_plan_1d(static_cast<int32_t>(L));
+  PassDesc d;
+  d.kind = kind;
+  apply_plan(d, plan);
+  set_axis_geometry(d, in_shape, out_shape, static_cast<int>(axis), kind != Kind::R2C, kind != Kind::C2R);
+  d.in_lo = static_cast<int32_t>(kind == Kind::C2R ? std::min(stored, half) : L);
+  d.in_hi = 0;
+  d.out_lo = static_cast<int32_t>(kind == Kind::R2C ? half : L);
+  d.out_hi = 0;
+  d.inverse = kind == Kind::C2R ? 1 : 0;
+  d.tin = bf16_in ? DType::BF16 : DType::F32;
+  d.tout = bf16_out ? DType::BF16 : DType::F32;
+  TORCH_CHECK(choose_tiling(d), "amd_dft.fft_pass_info: length exceeds the LDS-resident limit");
+  finalize_vec_flags(d, bf16_in ? 2 : 4, bf16_out ? 2 : 4);
+  const int64_t nsig = kind == Kind::C2C ? d.I : (d.I + 1) / 2;
+  std::ostringstream os;
+  FixedLaunchInfo fi;
+  if (describe_fft_fixed(d, fi)) {
+    const FixedCfg& c = fixed_configs()[fi.cfg];
+    os << "fixed L=" << c.L << " cols=" << (c.cols ? 1 : 0) << " TP=" << c.TP << " T=" << c.T << " cfg=" << fi.cfg
+       << " tiles=" << fi.tiles_per_outer << " blocks=" << fi.nblocks << " xcd=" << (fi.xcd ? 1 : 0)
+       << " pairvec=" << (fi.pairvec ? 1 : 0);
+  } else {
+    const bool cols = d.Si_in < d.Sn_in || d.Si_out < d.Sn_out;
+    os << "generic L=" << d.L << " radices=[";
+    for (int i = 0; i < d.npass; ++i) os << (i ? "," : "") << d.radix[i];
+    os << "] cols=" << (cols ? 1 : 0) << " logT=" << d.logT << " nthreads=" << d.nthreads
+       << " tiles=" << d.tiles_per_outer << " blocks=" << d.O * d.tiles_per_outer << " lds=" << pass_lds_bytes(d)
+       << " vec_in=" << d.vec_in << " vec_out=" << d.vec_out;
+  }
+  os << " I=" << d.I << " O=" << d.O << " nsig=" << nsig;
+  return os.str();
+}
+
+// The compiled fixed configurations, one "L cols TP T r,r,..." entry per table index, ';'-separated.
+std::string fft_fixed_configs() {
+  std::ostringstream os;
+  for (const FixedCfg& c : fixed_configs()) {
+    os << c.L << ' ' << (c.cols ? 1 : 0) << ' ' << c.TP << ' ' << c.T << ' ';
+    for (int i = 0; i < c.npass; ++i) os << (i ? "," : "") << c.radix[i];
+    os << ';';
+  }
+  return os.str();
+}
+
+// Brute force over the selection score: how often each table index wins for I in 1..I_max, O in 1..O_max
+// with the default radix order of L.
+std::vector<int64_t> fft_fixed_sweep(std::string kind_s, int64_t L, bool cols, int64_t I_max, int64_t O_max) {
+  const Kind kind = parse_kind(kind_s, "fft_fixed_sweep");
+  TORCH_CHECK(L >= 1 && L < (1 << 30), "amd_dft.fft_fixed_sweep: bad length");
+  const std::vector<int32_t> rad = factorize(static_cast<int32_t>(L));
+  std::vector<int64_t> wins(fixed_configs().size(), 0);
+  for (int64_t O = 1; O <= O_max; ++O)
+    for (int64_t I = 1; I <= I_max; ++I) {
+      const int b = select_fixed_config(kind, static_cast<int32_t>(L), cols, I, O, rad.data(), static_cast<int32_t>(rad.size()));
+      if (b >= 0) ++wins[b];
+    }
+  return wins;
+}
+
 std::string plugin_registry() {
   // Mirrors the two TensorRT plugin creators (dft_plugins.cpp:497-570): name, version,
   // namespace, field list in the creator's order.
@@ -1276,6 +1371,10 @@ TORCH_LIBRARY(amd_dft, m) {
   m.def("Rfft(Tensor x, int normalized=0, int onesided=1, int signal_ndim=1) -> Tensor");
   m.def("Irfft(Tensor x, int normalized=0, int onesided=1, int signal_ndim=1) -> Tensor");
   m.def("plan_info(int n) -> str", &amd_dft::plan_info);
+  m.def("fft_pass_info(str kind, int[] shape, int axis, int n=-1, bool bf16_in=False, bool bf16_out=False) -> str",
+        &amd_dft::fft_pass_info);
+  m.def("fft_fixed_configs() -> str", &amd_dft::fft_fixed_configs);
+  m.def("fft_fixed_sweep(str kind, int L, bool cols, int I_max, int O_max) -> int[]", &amd_dft::fft_fixed_sweep);
   m.def("plugin_registry() -> str", &amd_dft::plugin_registry);
   m.def("plan_cache_size() -> int", &amd_dft::plan_cache_size);
   m.def("plan_cache_clear() -> ()", &amd_dft::plan_cache_clear);

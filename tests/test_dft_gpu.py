@@ -5,14 +5,12 @@ W=4 only) to every length 1..64, the FourCastNet/FNO lengths (90, 180, 720, 1440
 two, large primes (generic radix), signal_ndim 1/2/3, channel-last dims, bf16 I/O, norms,
 pruned (mode-truncated) transforms, input-not-clobbered and hipGraph replay.
 """
-import math
-
 import pytest
 import torch
 
 import tensorrt_dft_plugins_amd as tdp
 from tensorrt_dft_plugins_amd.ops import dft
-from helpers import rel_l2
+from helpers import long_fft_tol, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -209,41 +207,6 @@ def test_finite_check_mode_gpu(device):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert "RAISED True" in r.stdout, r.stdout + r.stderr[-2000:]
-
-
-def _smooth_at_least(n: int) -> int:
-    m = n
-    while True:
-        k = m
-        for p in (2, 3, 5):
-            while k % p == 0:
-                k //= p
-        if k == 1:
-            return m
-        m += 1
-
-
-def long_fft_tol(n: int, limit: int = 6552) -> float:
-    """Error model of the long-length compositions (csrc/ops/dft_ops.cpp:151-238), rel-L2 vs fp64,
-    eps = 2^-24 (fp32 unit roundoff):
-      * four-step / LDS-resident: eps (log2 n + 2 + sqrt(p)), p = largest prime factor of n
-        (radix-r Stockham passes add ~eps per level, the fp32 twiddle multiply ~2 eps, and a
-        prime factor above the specialised radices runs as a direct p-point DFT: ~eps sqrt(p));
-      * Bluestein (n prime above the LDS limit): eps (3 log2 M + 3), M = the smallest 2,3,5-smooth
-        length >= 2n - 1 (three chained M-point FFTs plus three complex products).
-    The tolerance is 2x the model; measured errors sit 6-18x below it on MI355X
-    (scripts/diag/long_fft_errors.py: 1.3e-7 .. 5.1e-7, 1.5e-6 for n = 8198 = 2 * 4099)."""
-    eps = 2.0 ** -24
-    p, k, f = 1, n, 2
-    while f * f <= k:
-        while k % f == 0:
-            p, k = max(p, f), k // f
-        f += 1
-    p = max(p, k) if k > 1 else p
-    if n <= limit or p < n:  # LDS-resident or four-step
-        return 2 * eps * (math.log2(n) + 2 + math.sqrt(p))
-    m = _smooth_at_least(2 * n - 1)
-    return 2 * eps * (3 * math.log2(m) + 3)
 
 
 @pytest.mark.parametrize("n", [6553, 8192, 8198, 10007, 20000, 65536, 100003])
