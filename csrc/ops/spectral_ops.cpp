@@ -131,12 +131,25 @@ at::Tensor fno_mix_cuda(const at::Tensor& x_, const at::Tensor& w_, int64_t path
                   w_.size(2) == x_.size(2),
               "fno_mix: x [B, Cin, M, 2], w [Cin, Cout, M, 2]");
   const int64_t B = x_.size(0), Cin = x_.size(1), M = x_.size(2), Cout = w_.size(1);
-  if (!fno_mix_fits(B, Cin, Cout)) {  // ATen on the device tensors
-    fallback_note("fno_mix", "operand tiles exceed the 160 KB LDS");
-    return fno_mix_cpu(x_, w_, path);
-  }
   at::Tensor x = x_.to(at::kFloat).contiguous(), w = w_.to(at::kFloat).contiguous();
   at::Tensor y = at::empty({B, Cout, M, 2}, x.options());
+  if (!fno_mix_fits(B, Cin, Cout)) {
+    // operand tiles beyond the MFMA kernel's 160 KB LDS (e.g. width 40 at any batch): the split-K stream
+    // kernel has no channel limit and takes up to 8 samples per launch
+    for (int64_t b0 = 0; b0 < B; b0 += 8) {
+      FnoMixLaunch q;
+      q.x = x.data_ptr<float>() + b0 * Cin * M * 2;
+      q.w = w.data_ptr<float>();
+      q.y = y.data_ptr<float>() + b0 * Cout * M * 2;
+      q.B = static_cast<int>(std::min<int64_t>(8, B - b0));
+      q.Cin = static_cast<int>(Cin);
+      q.Cout = static_cast<int>(Cout);
+      q.M = static_cast<int>(M);
+      q.mfma = 0;
+      launch_fno_mix(q, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    }
+    return checked(y, "fno_mix");
+  }
   FnoMixLaunch p;
   p.x = x.data_ptr<float>();
   p.w = w.data_ptr<float>();
@@ -183,8 +196,8 @@ at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec_, const at::
   at::Tensor w2 = w.reshape({w.size(0), -1}).to(at::kFloat).contiguous();
   TORCH_CHECK(w2.size(1) == Cin, "fno_pointwise: weight must be [Cout, Cin]");
   const int64_t Cout = w2.size(0);
-  TORCH_CHECK(fno_pointwise_supported(static_cast<int>(Cin)), "fno_pointwise: unsupported channel count ", Cin,
-              " (kernel instances: 4, 8, 16, 20, 32, 64, 128)");
+  // any channel counts: fno_pointwise_route picks the register-resident instance or the MFMA kernel
+  TORCH_CHECK(Cin >= 1 && Cin < (1 << 20) && Cout < (1 << 20), "fno_pointwise: bad channel count ", Cin, " -> ", Cout);
   TORCH_CHECK(P < (int64_t(1) << 31) / 4 && B <= 65535, "fno_pointwise: tensor too large");
   at::Tensor x = x_.contiguous();
   at::Tensor spec;
@@ -210,6 +223,17 @@ at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec_, const at::
   p.gelu = gelu;
   launch_fno_pointwise(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
   return checked(y, "fno_pointwise");
+}
+
+// Which kernel fno_pointwise runs for (Cin, Cout, dtype, P) on aligned tensors -- host only, no device
+// (the companion of fft_pass_info): "fixed cin=20 vp=4" or "mfma slabs=2 otiles=3 groups=1 x3=1 vp=4"
+std::string fno_pointwise_info(int64_t cin, int64_t cout, bool bf16, int64_t P) {
+  TORCH_CHECK(cin >= 1 && cin < (1 << 20) && cout >= 1 && cout < (1 << 20) && P >= 1,
+              "amd_dft.fno_pointwise_info: cin, cout, P must be >= 1");
+  const FnoPointwiseRoute r = fno_pointwise_route(static_cast<int>(cin), static_cast<int>(cout), bf16, P, true);
+  if (!r.mfma) return "fixed cin=" + std::to_string(cin) + " vp=" + std::to_string(r.vp);
+  return "mfma slabs=" + std::to_string(r.slabs) + " otiles=" + std::to_string(r.otiles) +
+         " groups=" + std::to_string(r.groups) + " x3=" + std::to_string(r.x3 ? 1 : 0) + " vp=" + std::to_string(r.vp);
 }
 
 at::Tensor fno_pointwise_meta(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
@@ -249,7 +273,8 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
                 m = yw_.size(3);
   if (!fno_c2r_pw_supported(static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(m),
                             static_cast<int>(W), x_.scalar_type() == at::kBFloat16)) {
-    // shapes outside the fused kernel: C2R on the FFT kernels + the pointwise kernel
+    // shapes outside the fused kernel (Cin or Cout > 32, m > 64, W % 8 != 0): C2R on the FFT kernels + the
+    // pointwise kernel, which takes any channel counts (fixed instance or MFMA, fno_pointwise_route)
     static auto c2r = c10::Dispatcher::singleton()
                           .findSchemaOrThrow("amd_dft::c2r", "")
                           .typed<at::Tensor(const at::Tensor&, at::IntArrayRef, at::IntArrayRef, double,
@@ -577,6 +602,7 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("layer_norm_split(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? pre=None) -> Tensor");
   m.def("fno_mix(Tensor x, Tensor w, int path=0) -> Tensor");
   m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
+  m.def("fno_pointwise_info(int cin, int cout, bool bf16, int P) -> str", &amd_dft::fno_pointwise_info);
   m.def("fno_c2r_pw(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor");
   m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
 }

@@ -125,12 +125,8 @@ void launch_cin(const FnoPointwiseLaunch& p, hipStream_t st) {
 }
 
 template <int CIN>
-void launch_vp(const FnoPointwiseLaunch& p, hipStream_t st) {
+void launch_vp(const FnoPointwiseLaunch& p, bool vec, hipStream_t st) {
   // VP * CIN input values live in VGPRs; vector IO needs every row start 4-element aligned
-  const uintptr_t al = 4 * (p.bf16 ? 2 : 4) - 1;
-  const bool aligned = !((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.y) |
-                          reinterpret_cast<uintptr_t>(p.spec)) & al);
-  const bool vec = p.P % 4 == 0 && CIN <= 32 && aligned;
   if (p.bf16) {
     if (vec) launch_cin<CIN, 4, true>(p, st);
     else launch_cin<CIN, 1, true>(p, st);
@@ -142,21 +138,26 @@ void launch_vp(const FnoPointwiseLaunch& p, hipStream_t st) {
 
 }  // namespace
 
-bool fno_pointwise_supported(int cin) { return cin == 4 || cin == 8 || cin == 16 || cin == 20 || cin == 32 || cin == 64 || cin == 128; }
-
 void launch_fno_pointwise(const FnoPointwiseLaunch& p, void* stream) {
   if (p.B == 0 || p.P == 0 || p.Cout == 0) return;
   if (p.B > 65535) throw std::runtime_error("amd_dft: fno_pointwise: batch > 65535");
+  if (p.Cin < 1) throw std::runtime_error("amd_dft: fno_pointwise: Cin must be >= 1");
+  const uintptr_t al = 4 * (p.bf16 ? 2 : 4) - 1;
+  const bool aligned = !((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.y) |
+                          reinterpret_cast<uintptr_t>(p.spec)) & al);
+  const FnoPointwiseRoute r = fno_pointwise_route(p.Cin, p.Cout, p.bf16 != 0, p.P, aligned);
+  if (r.mfma) return launch_fno_pointwise_mfma(p, r.vp == 4, stream);
+  const bool vec = r.vp == 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
   switch (p.Cin) {
-    case 4: launch_vp<4>(p, st); break;
-    case 8: launch_vp<8>(p, st); break;
-    case 16: launch_vp<16>(p, st); break;
-    case 20: launch_vp<20>(p, st); break;
-    case 32: launch_vp<32>(p, st); break;
-    case 64: launch_vp<64>(p, st); break;
-    case 128: launch_vp<128>(p, st); break;
-    default: throw std::runtime_error("amd_dft: fno_pointwise: unsupported Cin " + std::to_string(p.Cin));
+    case 4: launch_vp<4>(p, vec, st); break;
+    case 8: launch_vp<8>(p, vec, st); break;
+    case 16: launch_vp<16>(p, vec, st); break;
+    case 20: launch_vp<20>(p, vec, st); break;
+    case 32: launch_vp<32>(p, vec, st); break;
+    case 64: launch_vp<64>(p, vec, st); break;
+    case 128: launch_vp<128>(p, vec, st); break;
+    default: throw std::runtime_error("amd_dft: fno_pointwise: no fixed instance for Cin " + std::to_string(p.Cin));
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: fno_pointwise launch: ") + hipGetErrorString(e));

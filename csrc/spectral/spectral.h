@@ -5,6 +5,8 @@
 #include <utility>
 #include <vector>
 
+#include "../ops/tuning.h"
+
 namespace amd_dft {
 
 // ---- AFNO: fused FFT_H -> block-diagonal complex MLP (MFMA) -> softshrink -> IFFT_H
@@ -47,8 +49,42 @@ struct FnoPointwiseLaunch {
   int B, Cin, Cout, P;
   int bf16 = 0, gelu = 1;
 };
-bool fno_pointwise_supported(int cin);
+// the register-resident instances of fno_pointwise.hip
+inline bool fno_pointwise_fixed(int cin) {
+  return cin == 4 || cin == 8 || cin == 16 || cin == 20 || cin == 32 || cin == 64 || cin == 128;
+}
 void launch_fno_pointwise(const FnoPointwiseLaunch& p, void* stream);
+// the MFMA kernel (fno_pointwise_mfma.hip): any Cin, Cout, P; vec = 4-pixel vector I/O
+void launch_fno_pointwise_mfma(const FnoPointwiseLaunch& p, bool vec, void* stream);
+
+// Which pointwise kernel a call takes (host only; launch_fno_pointwise and the fno_pointwise_info op
+// both answer from here).  The seven register-resident instances keep their channel counts; every
+// other Cin >= 1 runs on the MFMA kernel.  aligned: x, y and spec start on a 4-element boundary.
+constexpr int kPwSlab = 32;        // input channels per K slab of the MFMA kernel
+constexpr int kPwGroupTiles = 4;   // 16-channel output tiles per accumulator group (64 channels)
+struct FnoPointwiseRoute {
+  bool mfma;    // false: fixed instance of Cin
+  int vp;       // pixels per lane-load: 4 (vector I/O) or 1
+  int slabs;    // mfma: ceil(Cin / 32) K slabs
+  int otiles;   // mfma: ceil(Cout / 16) output tiles
+  int groups;   // mfma: ceil(otiles / 4) passes over the x slabs
+  bool x3;      // mfma: fp32 I/O, 3-product bf16 split
+};
+inline FnoPointwiseRoute fno_pointwise_route(int cin, int cout, bool bf16, int64_t P, bool aligned) {
+  FnoPointwiseRoute r{};
+  // tuning builds: MI_DFT_PW_MFMA=1 sends the fixed channel counts to the MFMA kernel too (A/B runs)
+  const char* e = tuning_env("MI_DFT_PW_MFMA");
+  r.mfma = !fno_pointwise_fixed(cin) || (e && e[0] == '1');
+  const bool vec = P % 4 == 0 && aligned;
+  r.vp = vec && (r.mfma || cin <= 32) ? 4 : 1;  // the fixed instances above 32 channels load per element
+  if (r.mfma) {
+    r.slabs = (cin + kPwSlab - 1) / kPwSlab;
+    r.otiles = (cout + 15) / 16;
+    r.groups = (r.otiles + kPwGroupTiles - 1) / kPwGroupTiles;
+    r.x3 = !bf16;
+  }
+  return r;
+}
 
 // ---- LayerNorm over the last dim (bf16/fp32 I/O, fp32 statistics)
 struct LayerNormLaunch {

@@ -37,6 +37,11 @@ __all__ = ["FNOConfig", "SpectralConv2d", "FNOBlock", "FNO2d", "spectral_conv2d_
 
 @dataclass
 class FNOConfig:
+    """Any channel counts are accepted (``in_chans``, ``out_chans``, ``width``, ``proj_hidden`` >= 1): the 1x1
+    convolutions of the amd backend run on the register-resident ``fno_pointwise`` instances at 4, 8, 16, 20, 32,
+    64 and 128 input channels and on the MFMA pointwise kernel at every other count; a layer tail is the fused
+    ``fno_c2r_pw`` kernel up to ``width`` 32 and ``c2r`` + ``fno_pointwise`` above."""
+
     img_size: Tuple[int, int] = (720, 1440)
     in_chans: int = 20
     out_chans: int = 20
@@ -45,6 +50,12 @@ class FNOConfig:
     modes2: int = 32  # kept W modes (one-sided)
     n_layers: int = 4
     proj_hidden: int = 128
+
+
+def _load_plugins() -> None:
+    from .._loader import load_plugins
+
+    load_plugins()
 
 
 def spectral_conv2d_reference(x: torch.Tensor, weight: torch.Tensor, m1: int, m2: int) -> torch.Tensor:
@@ -108,6 +119,7 @@ class SpectralConv2d(nn.Module):
         # FNOBlock's kernels without the pointwise branch: truncated DFT along W on MFMA, pruned FFT
         # along H, mixing inside the pruned inverse H transform, inverse truncated DFT along W (fno_c2r:
         # the layer tail with no x read) -- the full-resolution spectrum never exists
+        _load_plugins()
         ops = torch.ops.amd_dft
         xw = ops.dftw_r2c(x, m2, 1.0)  # [B, Cin, H, m2, 2]
         xm = ops.c2c_axis(xw, 2, H, H, 0, m1, m1, False, 1.0)  # [B, Cin, 2*m1, m2, 2]
@@ -149,6 +161,7 @@ class FNOBlock(nn.Module):
         FFT along H] -> fused [inverse DFT-GEMM along W + 1x1 conv + bias + GELU]: four kernels.
         From batch 8 the mixing runs as batched per-mode GEMMs on MFMA (fno_mix.hip: every mode's
         weights read once for the whole batch) followed by the pruned inverse transform: five."""
+        _load_plugins()  # a standalone block in a fresh process: the ops are registered on first use
         sp = self.spectral
         B, C, H, W = x.shape
         sp._check(H, W)
@@ -193,9 +206,7 @@ class FNO2d(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.backend == "amd":
-            from .._loader import load_plugins
-
-            load_plugins()
+            _load_plugins()
         x = self._pw(self.lift, x, False)
         for b in self.blocks:
             x = b(x)
