@@ -271,10 +271,12 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
               "fno_c2r_pw: x must be float32 or bfloat16");
   const int64_t B = x_.size(0), Cin = x_.size(1), H = x_.size(2), W = x_.size(3), Cout = yw_.size(1),
                 m = yw_.size(3);
-  if (!fno_c2r_pw_supported(static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(m),
-                            static_cast<int>(W), x_.scalar_type() == at::kBFloat16)) {
-    // shapes outside the fused kernel (Cin or Cout > 32, m > 64, W % 8 != 0): C2R on the FFT kernels + the
-    // pointwise kernel, which takes any channel counts (fixed instance or MFMA, fno_pointwise_route)
+  const bool is_bf = x_.scalar_type() == at::kBFloat16;
+  const FnoTailRoute route = fno_c2r_pw_route(static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(m),
+                                              static_cast<int>(W), is_bf);
+  if (route.kind == FnoTailKind::Split) {
+    // shapes outside both fused kernels (m > 64, W % 8 != 0, a rotation table beyond LDS): C2R on the FFT
+    // kernels + the pointwise kernel, which takes any channel counts (fixed instance or MFMA, fno_pointwise_route)
     static auto c2r = c10::Dispatcher::singleton()
                           .findSchemaOrThrow("amd_dft::c2r", "")
                           .typed<at::Tensor(const at::Tensor&, at::IntArrayRef, at::IntArrayRef, double,
@@ -283,6 +285,7 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
     at::Tensor spec = c2r.call(yw_.to(at::kFloat).contiguous(), dim, out_size, 1.0, {}, x_.scalar_type());
     return fno_pointwise_cuda(spec, x_, wc_.reshape({Cout, Cin}), bias, gelu);
   }
+  const bool wide = route.kind == FnoTailKind::Wide;  // Cin or Cout > 32: fno_c2r_pw_wide.hip, 64-pixel chunks
   TORCH_CHECK(B * Cin * H * W < (int64_t(1) << 31) && B * Cout * H * W < (int64_t(1) << 31),
               "fno_c2r_pw: tensor too large");
   at::Tensor x = x_.contiguous();
@@ -292,8 +295,8 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
   at::Tensor wc = wc_.to(at::kFloat).reshape({Cout, Cin}).contiguous();
   at::Tensor bf = f32_or_undef(bias);
   at::Tensor y = at::empty({B, Cout, H, W}, x.options());
-  auto tabs = get_dft_gemm_tables(x.scalar_type() == at::kBFloat16 ? DftTable::C2R_BF16 : DftTable::C2R_F32,
-                                  static_cast<int>(W), static_cast<int>(m), x.device());
+  auto tabs = get_dft_gemm_tables(is_bf && !wide ? DftTable::C2R_BF16 : DftTable::C2R_F32, static_cast<int>(W),
+                                  static_cast<int>(m), x.device());
   FnoC2RPwLaunch p;
   p.yw = yw.data_ptr();
   p.x = x.data_ptr();
@@ -310,8 +313,27 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
   p.m = static_cast<int>(m);
   p.bf16 = x.scalar_type() == at::kBFloat16;
   p.gelu = gelu;
-  launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  if (wide) launch_fno_c2r_pw_wide(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  else launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
   return checked(y, "fno_c2r_pw");
+}
+
+// Which route fno_c2r_pw (cin >= 1) or fno_c2r (cin = 0) takes for a shape -- host only, no device (the
+// companion of fno_pointwise_info): "fused ks=2 co=2 chunk=128", "wide slabs=2 otiles=4 groups=1 ks=2 chunk=64
+// x3=0" or "split"
+std::string fno_c2r_pw_info(int64_t cin, int64_t cout, int64_t m, int64_t W, bool bf16) {
+  TORCH_CHECK(cin >= 0 && cin < (1 << 20) && cout >= 1 && cout < (1 << 20) && m >= 1 && W >= 1 &&
+                  W < (int64_t(1) << 31) && m < (int64_t(1) << 31),
+              "amd_dft.fno_c2r_pw_info: cin must be >= 0 and cout, m, W >= 1");
+  const FnoTailRoute r = fno_c2r_pw_route(static_cast<int>(cin), static_cast<int>(cout), static_cast<int>(m),
+                                          static_cast<int>(W), bf16);
+  if (r.kind == FnoTailKind::Fused)
+    return "fused ks=" + std::to_string(r.ks) + " co=" + std::to_string(r.co) + " chunk=" + std::to_string(r.chunk);
+  if (r.kind == FnoTailKind::Wide)
+    return "wide slabs=" + std::to_string(r.slabs) + " otiles=" + std::to_string(r.otiles) +
+           " groups=" + std::to_string(r.groups) + " ks=" + std::to_string(r.ks) + " chunk=" + std::to_string(r.chunk) +
+           " x3=" + std::to_string(r.x3 ? 1 : 0);
+  return "split";
 }
 
 at::Tensor fno_c2r_pw_meta(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
@@ -344,8 +366,10 @@ at::Tensor fno_c2r_cuda(const at::Tensor& yw_, int64_t W, std::optional<at::Scal
   const c10::DeviceGuard guard(yw_.device());
   const at::ScalarType dt = fno_c2r_dtype(yw_, W, out_dtype);
   const int64_t B = yw_.size(0), Cout = yw_.size(1), H = yw_.size(2), m = yw_.size(3);
-  if (!fno_c2r_pw_supported(1, static_cast<int>(Cout), static_cast<int>(m), static_cast<int>(W), dt == at::kBFloat16) ||
-      B * Cout * H * W >= (int64_t(1) << 31)) {
+  const FnoTailRoute route =
+      fno_c2r_pw_route(0, static_cast<int>(Cout), static_cast<int>(m), static_cast<int>(W), dt == at::kBFloat16);
+  const bool wide = route.kind == FnoTailKind::Wide;  // Cout > 32: fno_c2r_pw_wide.hip, 64-pixel chunks
+  if (route.kind == FnoTailKind::Split || B * Cout * H * W >= (int64_t(1) << 31)) {
     // shapes outside the fused kernel: C2R on the FFT kernels
     static auto c2r = c10::Dispatcher::singleton()
                           .findSchemaOrThrow("amd_dft::c2r", "")
@@ -358,8 +382,8 @@ at::Tensor fno_c2r_cuda(const at::Tensor& yw_, int64_t W, std::optional<at::Scal
   // the tail kernel reads 4 modes per 16-byte load: a view at an odd float2 offset gets its own copy
   if (reinterpret_cast<uintptr_t>(yw.data_ptr()) % 16 != 0) yw = yw.clone();
   at::Tensor y = at::empty({B, Cout, H, W}, yw.options().dtype(dt));
-  auto tabs = get_dft_gemm_tables(dt == at::kBFloat16 ? DftTable::C2R_BF16 : DftTable::C2R_F32, static_cast<int>(W),
-                                  static_cast<int>(m), yw.device());
+  auto tabs = get_dft_gemm_tables(dt == at::kBFloat16 && !wide ? DftTable::C2R_BF16 : DftTable::C2R_F32,
+                                  static_cast<int>(W), static_cast<int>(m), yw.device());
   FnoC2RPwLaunch p;
   p.yw = yw.data_ptr();
   p.x = nullptr;  // spectral path only
@@ -376,7 +400,8 @@ at::Tensor fno_c2r_cuda(const at::Tensor& yw_, int64_t W, std::optional<at::Scal
   p.m = static_cast<int>(m);
   p.bf16 = dt == at::kBFloat16;
   p.gelu = 0;
-  launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(yw.device().index()).stream());
+  if (wide) launch_fno_c2r_pw_wide(p, c10::hip::getCurrentHIPStream(yw.device().index()).stream());
+  else launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(yw.device().index()).stream());
   return checked(y, "fno_c2r");
 }
 
@@ -604,6 +629,7 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
   m.def("fno_pointwise_info(int cin, int cout, bool bf16, int P) -> str", &amd_dft::fno_pointwise_info);
   m.def("fno_c2r_pw(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor");
+  m.def("fno_c2r_pw_info(int cin, int cout, int m, int W, bool bf16) -> str", &amd_dft::fno_c2r_pw_info);
   m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
 }
 

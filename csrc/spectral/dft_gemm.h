@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../ops/tuning.h"
+
 namespace amd_dft {
 
 constexpr int kDftGemmKB = 64;     // samples per phase block of the forward kernel
@@ -50,5 +52,51 @@ void fno_c2r_tables(int W, int m, int chunk, std::vector<uint16_t>& g0, std::vec
 // Cin, Cout <= 32, m <= 64, W % 8 == 0 and the rotation table fits in LDS (W <= 4096 bf16 / 2048 fp32 at m = 64)
 bool fno_c2r_pw_supported(int cin, int cout, int m, int W, bool bf16);
 void launch_fno_c2r_pw(const FnoC2RPwLaunch& p, void* stream);
+
+// ---- the same tail at any channel count (fno_c2r_pw_wide.hip): 64-pixel chunks for both dtypes, so g0 / rot are
+// the chunk-64 tables (DftTable::C2R_F32; bf16 I/O reads the hi plane only).  cin = 0: spectral-only (fno_c2r).
+// m <= 64, 2 (m - 1) <= W, W % 8 == 0 and the rotation table (ceil(W / 64) x 16 ceil(m / 16)) fits in LDS
+constexpr int kFnoWideChunk = 64;
+bool fno_c2r_pw_wide_supported(int cin, int cout, int m, int W, bool bf16);
+void launch_fno_c2r_pw_wide(const FnoC2RPwLaunch& p, void* stream);
+
+// Which kernel(s) a layer tail takes (host only; fno_c2r_pw, fno_c2r and the fno_c2r_pw_info op all answer
+// from here): the narrow fused kernel wherever it applies, else the wide fused kernel, else C2R on the FFT
+// kernels + the pointwise kernel.  cin = 0 asks about fno_c2r.
+enum class FnoTailKind { Fused, Wide, Split };
+struct FnoTailRoute {
+  FnoTailKind kind;
+  int ks;      // fused / wide: ceil(m / 16) spectral K slabs
+  int chunk;   // fused / wide: pixels per phase block
+  int co;      // fused: 16-channel output tiles (1 or 2)
+  int slabs;   // wide: ceil(cin / 32) conv K slabs
+  int otiles;  // wide: ceil(cout / 16) output tiles
+  int groups;  // wide: ceil(otiles / 4) accumulator groups
+  bool x3;     // wide: fp32 I/O, 3-product bf16 split
+};
+inline FnoTailRoute fno_c2r_pw_route(int cin, int cout, int m, int W, bool bf16) {
+  FnoTailRoute r{};
+  r.kind = FnoTailKind::Split;
+  if (fno_c2r_pw_supported(cin == 0 ? 1 : cin, cout, m, W, bf16)) {
+    r.kind = FnoTailKind::Fused;
+    r.ks = (m + 15) / 16;
+    r.chunk = bf16 ? kFnoChunkBF : kFnoChunkF32;
+    r.co = cout <= 16 ? 1 : 2;
+    return r;
+  }
+  // tuning builds: MI_DFT_FNO_WIDE=0 keeps the split route (A/B runs of the two routes in one build)
+  const char* e = tuning_env("MI_DFT_FNO_WIDE");
+  if (e && e[0] == '0') return r;
+  if (fno_c2r_pw_wide_supported(cin, cout, m, W, bf16)) {
+    r.kind = FnoTailKind::Wide;
+    r.ks = (m + 15) / 16;
+    r.chunk = kFnoWideChunk;
+    r.slabs = (cin + 31) / 32;
+    r.otiles = (cout + 15) / 16;
+    r.groups = (r.otiles + 3) / 4;
+    r.x3 = !bf16;
+  }
+  return r;
+}
 
 }  // namespace amd_dft

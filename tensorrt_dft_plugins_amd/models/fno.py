@@ -14,8 +14,9 @@ kernels per stage, and the full-resolution spectral output is never written to H
      ``csrc/spectral/fno_mix.hip``, plus ``c2c_axis`` where no fixed column kernel covers H);
   3. ``fno_c2r_pw``: the inverse truncated DFT
      along W on MFMA fused with the 1x1 convolution, bias and GELU
-     (``csrc/spectral/fno_c2r_pw.hip``) -- reads x, writes y, nothing else; ``SpectralConv2d`` on its
-     own ends with ``fno_c2r``, the same kernel without the pointwise branch (writes y only).
+     (``csrc/spectral/fno_c2r_pw.hip`` up to 32 channels, ``csrc/spectral/fno_c2r_pw_wide.hip`` above) --
+     reads x, writes y, nothing else; ``SpectralConv2d`` on its own ends with ``fno_c2r``, the same kernels
+     without the pointwise branch (writes y only).  ``torch.ops.amd_dft.fno_c2r_pw_info`` names the route.
 
 Backends: ``"torch"`` (torch.fft + einsum + conv2d, the numerics oracle), ``"contrib"`` (the same
 layer written the reference's way: ONNX-contrib ``OnnxRfft2`` / ``OnnxIrfft2`` + real/imaginary
@@ -39,8 +40,10 @@ __all__ = ["FNOConfig", "SpectralConv2d", "FNOBlock", "FNO2d", "spectral_conv2d_
 class FNOConfig:
     """Any channel counts are accepted (``in_chans``, ``out_chans``, ``width``, ``proj_hidden`` >= 1): the 1x1
     convolutions of the amd backend run on the register-resident ``fno_pointwise`` instances at 4, 8, 16, 20, 32,
-    64 and 128 input channels and on the MFMA pointwise kernel at every other count; a layer tail is the fused
-    ``fno_c2r_pw`` kernel up to ``width`` 32 and ``c2r`` + ``fno_pointwise`` above."""
+    64 and 128 input channels and on the MFMA pointwise kernel at every other count; a layer tail is one fused
+    ``fno_c2r_pw`` kernel at every ``width`` (the narrow kernel up to 32 channels, the wide one above); only
+    ``modes2`` > 64, a W that is no multiple of 8 or a very long W take ``c2r`` + ``fno_pointwise``
+    (``torch.ops.amd_dft.fno_c2r_pw_info``)."""
 
     img_size: Tuple[int, int] = (720, 1440)
     in_chans: int = 20
