@@ -108,6 +108,123 @@ bool afno_spectral_ok(int64_t H, int64_t block_size) {
   return afno_spectral_supported(static_cast<int>(H), static_cast<int>(block_size));
 }
 
+// ------------------------------------------------------------------ AFNO block MLP on a transformed spectrum
+// x [..., C, 2] fp32 (any leading dims: the kept modes), weights / biases as afno_spectral.  Returns the same
+// shape:  softshrink( ReLU([xr|xi] W1' + b1') W2' + b2' )  per token and channel block, stored interleaved.
+// afno_mlp_out writes into a given contiguous fp32 tensor of x's shape.
+void check_afno_mlp(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
+                    const at::Tensor& b2) {
+  TORCH_CHECK(x.dim() >= 2 && x.size(-1) == 2 && x.scalar_type() == at::kFloat,
+              "afno_mlp: x must be [..., C, 2] float32");
+  TORCH_CHECK(w1t.dim() == 3, "afno_mlp: bad weight shapes");
+  const int64_t NB = w1t.size(0), K = w1t.size(1);
+  TORCH_CHECK((w1t.size(2) == K || w1t.size(2) == 2 * K) && w2t.sizes() == w1t.sizes(),
+              "afno_mlp: weights must be [NB, 2BS, 2BS] (bf16) or split [NB, 2BS, 2*2BS] (bf16x3)");
+  TORCH_CHECK(NB >= 1 && K >= 2 && K % 2 == 0 && NB * K == 2 * x.size(-2),
+              "afno_mlp: NB * 2 * block_size must equal 2 * C");
+  TORCH_CHECK(b1.sizes() == at::IntArrayRef({NB, K}) && b2.sizes() == b1.sizes(), "afno_mlp: bad bias shapes");
+}
+
+void check_afno_mlp_out(const at::Tensor& x, const at::Tensor& out) {
+  TORCH_CHECK(out.sizes() == x.sizes() && out.scalar_type() == at::kFloat && out.is_contiguous() &&
+                  out.device() == x.device(),
+              "afno_mlp_out: out must be a contiguous float32 tensor of x's shape on x's device");
+}
+
+at::Tensor afno_mlp_cpu(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
+                        const at::Tensor& b2, double lam) {
+  check_afno_mlp(x, w1t, w2t, b1, b2);
+  const int64_t C = x.size(-2), NB = w1t.size(0), BS = C / NB;
+  at::Tensor Xr = x.contiguous().reshape({-1, NB, BS, 2});
+  at::Tensor A = at::cat({Xr.select(-1, 0), Xr.select(-1, 1)}, -1);  // [T, NB, 2BS]
+  auto unsplit = [&](const at::Tensor& w) {  // k32-interleaved split rows -> fp32
+    if (w.size(2) == w.size(1)) return w.to(at::kFloat);
+    const int64_t k = w.size(1);
+    TORCH_CHECK(k % 32 == 0, "afno_mlp: split weights need 2 * block_size % 32 == 0");
+    return w.to(at::kFloat).reshape({w.size(0), k, k / 32, 2, 32}).sum(3).reshape({w.size(0), k, k});
+  };
+  at::Tensor W1 = unsplit(w1t).transpose(1, 2), W2 = unsplit(w2t).transpose(1, 2);  // [NB, k, n]
+  at::Tensor H1 = at::relu(at::einsum("tbk,bkn->tbn", {A, W1}) + b1.to(at::kFloat));
+  at::Tensor O = at::softshrink(at::einsum("tbk,bkn->tbn", {H1, W2}) + b2.to(at::kFloat), lam);
+  return at::stack({O.narrow(-1, 0, BS), O.narrow(-1, BS, BS)}, -1).reshape(x.sizes()).contiguous();
+}
+
+at::Tensor& afno_mlp_out_cpu(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
+                             const at::Tensor& b2, double lam, at::Tensor& out) {
+  check_afno_mlp_out(x, out);
+  out.copy_(afno_mlp_cpu(x, w1t, w2t, b1, b2, lam));
+  return out;
+}
+
+void afno_mlp_run(const at::Tensor& x_, const at::Tensor& w1t_, const at::Tensor& w2t_, const at::Tensor& b1_,
+                  const at::Tensor& b2_, double lam, at::Tensor& y) {
+  at::Tensor x = x_.contiguous();
+  // 16-byte loads of two channels' (re, im): a view at an odd offset gets its own copy
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone();
+  at::Tensor w1t = w1t_.to(at::kBFloat16).contiguous(), w2t = w2t_.to(at::kBFloat16).contiguous();
+  at::Tensor b1 = b1_.to(at::kFloat).contiguous(), b2 = b2_.to(at::kFloat).contiguous();
+  const int64_t C = x.size(-2), NB = w1t.size(0), BS = C / NB;
+  const bool x3 = w1t.size(2) == 2 * w1t.size(1);
+  const int64_t T = x.numel() / (2 * C);
+  const AfnoMlpRoute r = afno_mlp_route(BS, x3, T);
+  TORCH_CHECK(r.ok, "afno_mlp: no kernel for block size ", BS, " (", r.why ? r.why : "", "); use the generic path");
+  TORCH_CHECK(C < (1 << 28) && reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
+              "afno_mlp: channel count too large or misaligned output");
+  if (T == 0) return;
+  AfnoMlpLaunch p;
+  p.x = x.data_ptr<float>();
+  p.y = y.data_ptr<float>();
+  p.w1t = reinterpret_cast<const uint16_t*>(w1t.data_ptr());
+  p.w2t = reinterpret_cast<const uint16_t*>(w2t.data_ptr());
+  p.b1 = b1.data_ptr<float>();
+  p.b2 = b2.data_ptr<float>();
+  p.T = T;
+  p.C = static_cast<int>(C);
+  p.NB = static_cast<int>(NB);
+  p.x3 = x3 ? 1 : 0;
+  p.lambda = static_cast<float>(lam);
+  launch_afno_mlp(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+}
+
+at::Tensor afno_mlp_cuda(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
+                         const at::Tensor& b2, double lam) {
+  check_afno_mlp(x, w1t, w2t, b1, b2);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(x.sizes(), x.options());
+  afno_mlp_run(x, w1t, w2t, b1, b2, lam, y);
+  return checked(y, "afno_mlp");
+}
+
+at::Tensor& afno_mlp_out_cuda(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
+                              const at::Tensor& b2, double lam, at::Tensor& out) {
+  check_afno_mlp(x, w1t, w2t, b1, b2);
+  check_afno_mlp_out(x, out);
+  const c10::DeviceGuard guard(x.device());
+  afno_mlp_run(x, w1t, w2t, b1, b2, lam, out);
+  checked(out, "afno_mlp_out");
+  return out;
+}
+
+at::Tensor afno_mlp_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                         double) {
+  return at::empty(x.sizes(), x.options());
+}
+
+at::Tensor& afno_mlp_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                              const at::Tensor&, double, at::Tensor& out) {
+  return out;
+}
+
+// Which kernel afno_mlp runs for (block size, packing, tokens) -- host only, no device (the companion of
+// fno_pointwise_info): "mfma TOK=32 ksteps=6 x3=1 lds=51200 tiles=512" or "none <reason>"
+std::string afno_mlp_info(int64_t block_size, bool split, int64_t tokens) {
+  TORCH_CHECK(tokens >= 0, "amd_dft.afno_mlp_info: tokens must be >= 0");
+  const AfnoMlpRoute r = afno_mlp_route(block_size, split, tokens);
+  if (!r.ok) return std::string("none ") + r.why;
+  return "mfma TOK=" + std::to_string(r.tok) + " ksteps=" + std::to_string(r.ksteps) + " x3=" +
+         std::to_string(split ? 1 : 0) + " lds=" + std::to_string(r.lds) + " tiles=" + std::to_string(r.tiles);
+}
+
 // ------------------------------------------------------------------ FNO mode mixing
 // x [B, Cin, M, 2] fp32, w [Cin, Cout, M, 2] fp32 -> y [B, Cout, M, 2] fp32
 at::Tensor fno_mix_cpu(const at::Tensor& x, const at::Tensor& w, int64_t /*path*/) {
@@ -621,6 +738,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("afno_spectral(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam) -> Tensor");
   m.def("afno_spectral_supported(int H, int block_size) -> bool", &amd_dft::afno_spectral_ok);
   m.def("afno_spectral_shapes() -> int[]", &amd_dft::afno_spectral_shape_list);
+  m.def("afno_mlp(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam) -> Tensor");
+  m.def("afno_mlp_out(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam, Tensor(a!) out) -> Tensor(a!)");
+  m.def("afno_mlp_info(int block_size, bool split, int tokens) -> str", &amd_dft::afno_mlp_info);
   m.def("layer_norm(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? residual=None) -> (Tensor, Tensor)");
   m.def("ln_stats(Tensor x, Tensor? pre=None, float eps=1e-6) -> Tensor");
   m.def("ln_stats_merge(Tensor part, float eps=1e-6, Tensor? shift=None) -> Tensor");
@@ -635,6 +755,8 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
 
 TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("afno_spectral", AMD_DFT_TRACED("amd_dft::afno_spectral", amd_dft::afno_spectral_cuda));
+  m.impl("afno_mlp", AMD_DFT_TRACED("amd_dft::afno_mlp", amd_dft::afno_mlp_cuda));
+  m.impl("afno_mlp_out", AMD_DFT_TRACED("amd_dft::afno_mlp_out", amd_dft::afno_mlp_out_cuda));
   m.impl("layer_norm", AMD_DFT_TRACED("amd_dft::layer_norm", amd_dft::layer_norm_cuda));
   m.impl("ln_stats", AMD_DFT_TRACED("amd_dft::ln_stats", amd_dft::ln_stats_cuda));
   m.impl("ln_stats_merge", AMD_DFT_TRACED("amd_dft::ln_stats_merge", amd_dft::ln_stats_merge_cuda));
@@ -647,6 +769,8 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
 
 TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("afno_spectral", AMD_DFT_TRACED("amd_dft::afno_spectral", amd_dft::afno_spectral_cpu));
+  m.impl("afno_mlp", AMD_DFT_TRACED("amd_dft::afno_mlp", amd_dft::afno_mlp_cpu));
+  m.impl("afno_mlp_out", AMD_DFT_TRACED("amd_dft::afno_mlp_out", amd_dft::afno_mlp_out_cpu));
   m.impl("layer_norm", AMD_DFT_TRACED("amd_dft::layer_norm", amd_dft::layer_norm_cpu));
   m.impl("ln_stats", AMD_DFT_TRACED("amd_dft::ln_stats", amd_dft::ln_stats_cpu));
   m.impl("ln_stats_merge", AMD_DFT_TRACED("amd_dft::ln_stats_merge", amd_dft::ln_stats_merge_cpu));
@@ -659,6 +783,8 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
 
 TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("afno_spectral", &amd_dft::afno_spectral_meta);
+  m.impl("afno_mlp", &amd_dft::afno_mlp_meta);
+  m.impl("afno_mlp_out", &amd_dft::afno_mlp_out_meta);
   m.impl("layer_norm", &amd_dft::layer_norm_meta);
   m.impl("ln_stats", &amd_dft::ln_stats_meta);
   m.impl("ln_stats_merge", &amd_dft::ln_stats_merge_meta);

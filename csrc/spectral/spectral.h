@@ -29,6 +29,58 @@ std::vector<std::pair<int, int>> afno_spectral_shapes();  // instantiated (H, bl
 int64_t afno_spectral_lds_bytes(int H, int block_size, bool x3);
 void launch_afno_spectral(const AfnoLaunch& p, void* stream);
 
+// ---- AFNO block-diagonal complex MLP on an already-transformed spectrum (afno_mlp.hip): no H limit,
+// the block size is a runtime loop bound
+struct AfnoMlpLaunch {
+  const float* x;       // [T, C, 2] fp32, (c, re/im) interleaved rows
+  float* y;             // same shape
+  const uint16_t* w1t;  // [NB][2*BS][2*BS] bf16 ([n][k]), or x3: [NB][2*BS][2 * 2*BS] k32-interleaved hi|lo
+  const uint16_t* w2t;
+  const float* b1;      // [NB][2*BS] = [b_re | b_im]
+  const float* b2;
+  int64_t T;            // tokens (rows)
+  int C, NB;
+  int x3 = 0;           // 3-product bf16 split GEMMs (split weights)
+  float lambda;
+};
+// Which kernel afno_mlp runs (host only; launch_afno_mlp and the afno_mlp_info op both answer from here).
+// ok: 16 <= BS <= 256 and BS % 16 == 0 (the split layout's 32-column groups over K = 2 BS).  The token tile
+// is the largest of 64 / 32 / 16 rows whose LDS image -- the [tok][2 BS + 8] bf16 operand and hidden
+// tiles, hi (and lo) planes each -- stays within 80 KB (two workgroups per CU), halved further while it
+// would be at least twice the token count.
+constexpr int64_t kAfnoMlpLdsBudget = 80 * 1024;
+struct AfnoMlpRoute {
+  bool ok;
+  const char* why;   // !ok: the reason
+  int tok;           // token rows per workgroup
+  int ksteps;        // 32-deep k-steps of each GEMM (BS / 16)
+  int64_t lds;       // dynamic LDS bytes per workgroup
+  int64_t tiles;     // token tiles (workgroups = tiles * NB)
+};
+inline int64_t afno_mlp_lds_bytes(int bs, bool split, int tok) {
+  return 2LL * (split ? 2 : 1) * tok * (2 * bs + 8) * 2;
+}
+inline AfnoMlpRoute afno_mlp_route(int64_t bs, bool split, int64_t tokens) {
+  AfnoMlpRoute r{};
+  if (bs < 16 || bs > 256) {
+    r.why = "block size outside 16..256";
+    return r;
+  }
+  if (bs % 16 != 0) {
+    r.why = "block size is not a multiple of 16";
+    return r;
+  }
+  r.ok = true;
+  r.tok = 64;
+  while (r.tok > 16 && afno_mlp_lds_bytes(static_cast<int>(bs), split, r.tok) > kAfnoMlpLdsBudget) r.tok /= 2;
+  while (r.tok > 16 && r.tok / 2 >= tokens) r.tok /= 2;
+  r.ksteps = static_cast<int>(bs / 16);
+  r.lds = afno_mlp_lds_bytes(static_cast<int>(bs), split, r.tok);
+  r.tiles = tokens > 0 ? (tokens + r.tok - 1) / r.tok : 0;
+  return r;
+}
+void launch_afno_mlp(const AfnoMlpLaunch& p, void* stream);
+
 // ---- FNO: per-mode complex channel mixing out[b,o,m] = sum_i x[b,i,m] * w[i,o,m]
 struct FnoMixLaunch {
   const float* x;   // [B, Cin, M, 2] fp32 (M = kept modes, flattened)

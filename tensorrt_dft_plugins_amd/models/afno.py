@@ -156,11 +156,29 @@ class AFNO2D(nn.Module):
                           c.hard_thresholding_fraction, owner=self)
 
 
+def afno_mlp_aten(xf, w1, b1, w2, b2, num_blocks, sparsity_threshold):
+    """Block MLP + softshrink of the generic route on torch GEMMs: spectrum window ``xf`` [B, R, km, C, 2]
+    (fp32) -> same shape.  Permutes into a [nb, M, 2bs] copy, two ``torch.baddbmm``, permutes back."""
+    C = xf.shape[3]
+    bs = C // num_blocks
+    M = xf.shape[0] * xf.shape[1] * xf.shape[2]
+    z = xf.reshape(M, num_blocks, bs, 2).permute(1, 0, 3, 2).reshape(num_blocks, M, 2 * bs)  # [nb, M, (re|im)*bs]
+    w1, b1, w2, b2 = w1.float(), b1.float(), w2.float(), b2.float()  # fp32 spectrum math for any model dtype
+    W1 = torch.cat([torch.cat([w1[0], w1[1]], dim=2), torch.cat([-w1[1], w1[0]], dim=2)], dim=1)  # [nb, 2bs, 2bs]
+    W2 = torch.cat([torch.cat([w2[0], w2[1]], dim=2), torch.cat([-w2[1], w2[0]], dim=2)], dim=1)
+    h = torch.relu(torch.baddbmm(torch.cat([b1[0], b1[1]], 1).unsqueeze(1), z, W1))
+    o = torch.baddbmm(torch.cat([b2[0], b2[1]], 1).unsqueeze(1), h, W2)
+    o = F.softshrink(o, sparsity_threshold)
+    return o.reshape(num_blocks, M, 2, bs).permute(1, 0, 3, 2).reshape(xf.shape[0], xf.shape[1], xf.shape[2], C, 2)
+
+
 def afno2d_amd(x, w1, b1, w2, b2, num_blocks, sparsity_threshold, hard_thresholding_fraction, residual=None,
                owner=None):
     """MI355X AFNO2D: pruned R2C along W (only kept W-modes), fused [FFT_H -> block MLP ->
     softshrink -> IFFT_H] spectral kernel, pruned C2R along W with the filter bias fused.
-    Falls back to pruned FFTs + torch GEMMs when the fused kernel does not apply."""
+    Shapes outside the fused kernel's instances (any H, any mode window) run pruned 2-D FFTs around
+    the ``afno_mlp`` kernel; block sizes that kernel does not take fall back to torch GEMMs
+    (``afno_mlp_aten``)."""
     from ..ops import spectral as S
 
     B, H, W, C = x.shape
@@ -175,19 +193,16 @@ def afno2d_amd(x, w1, b1, w2, b2, num_blocks, sparsity_threshold, hard_threshold
         yw = S.afno_spectral_h(xw, w1, b1, w2, b2, num_blocks, sparsity_threshold, owner=owner)
         # C2R along W from km stored modes, + bias (filter input) fused
         return S.c2r_w_add(yw, x, W, 1.0 / math.sqrt(H * W), residual)
-    # generic path: pruned 2-D R2C/C2R + batched real-block GEMMs
-    S.note_fallback("afno_spectral", "no fused AFNO kernel for this (H, block size) / mode window: torch.baddbmm", x)
-    xf = D._ops().r2c(x, [1, 2], scale_f, [H, 0, km, 0], torch.float32)[:, r0:r1]
-    bs = C // num_blocks
-    M = xf.shape[0] * xf.shape[1] * xf.shape[2]
-    z = xf.reshape(M, num_blocks, bs, 2).permute(1, 0, 3, 2).reshape(num_blocks, M, 2 * bs)  # [nb, M, (re|im)*bs]
-    w1, b1, w2, b2 = w1.float(), b1.float(), w2.float(), b2.float()  # fp32 spectrum math for any model dtype
-    W1 = torch.cat([torch.cat([w1[0], w1[1]], dim=2), torch.cat([-w1[1], w1[0]], dim=2)], dim=1)  # [nb, 2bs, 2bs]
-    W2 = torch.cat([torch.cat([w2[0], w2[1]], dim=2), torch.cat([-w2[1], w2[0]], dim=2)], dim=1)
-    h = torch.relu(torch.baddbmm(torch.cat([b1[0], b1[1]], 1).unsqueeze(1), z, W1))
-    o = torch.baddbmm(torch.cat([b2[0], b2[1]], 1).unsqueeze(1), h, W2)
-    o = F.softshrink(o, sparsity_threshold)
-    o = o.reshape(num_blocks, M, 2, bs).permute(1, 0, 3, 2).reshape(xf.shape[0], r1 - r0, km, C, 2)
+    if S.afno_mlp_available(x, num_blocks):
+        # any H / mode window: pruned 2-D R2C, the block MLP on the afno_mlp kernel straight on the
+        # (c, re/im)-interleaved window (bf16 MFMA operands; bf16x3 split GEMMs for fp32 models)
+        xf = D._ops().r2c(x, [1, 2], scale_f, [H, 0, km, 0], torch.float32)[:, r0:r1]
+        o = S.afno_spectral_mlp(xf, w1, b1, w2, b2, sparsity_threshold, x.dtype == torch.float32, owner=owner)
+    else:
+        # generic path: pruned 2-D R2C/C2R + batched real-block GEMMs
+        S.note_fallback("afno_spectral", "no fused AFNO kernel for this (H, block size) / mode window: torch.baddbmm", x)
+        xf = D._ops().r2c(x, [1, 2], scale_f, [H, 0, km, 0], torch.float32)[:, r0:r1]
+        o = afno_mlp_aten(xf, w1, b1, w2, b2, num_blocks, sparsity_threshold)
     if r0 > 0 or r1 < H:
         full = o.new_zeros(o.shape[0], H, km, C, 2)
         full[:, r0:r1] = o
@@ -223,7 +238,8 @@ class Block(nn.Module):
             from ..ops import spectral as S
 
             x, y = S.afno_block_amd(self, x)
-            return x + S.pending_bias(y)
+            p = S.pending_bias(y)  # None: the block's hand GEMM already added everything
+            return x if p is None else x + p
         residual = x
         x = self.filter(self.norm1(x))
         x = x + residual  # double skip

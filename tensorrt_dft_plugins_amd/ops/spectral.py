@@ -30,6 +30,7 @@ from .._loader import load_plugins
 from . import dft as D
 
 __all__ = ["pack_afno_weights", "afno_fused_available", "afno_spectral_h", "c2r_w_add", "layer_norm",
+           "afno_mlp_available", "afno_mlp_block_size_ok", "afno_spectral_mlp", "afno_block_mlp_hand",
            "afno_block_amd", "afno_block_fused", "afno_block_fused_f32",
            "afno_block_spectral", "afno_block_mlp", "fno_spectral_mix", "split_bf16", "module_cached",
            "fallback_counts", "fallback_reset", "note_fallback", "unsplit_bf16", "LnCarry", "pending_bias", "SplitRows"]
@@ -127,6 +128,35 @@ def afno_fused_available(x: torch.Tensor, num_blocks: int) -> bool:
     return (H, C // int(num_blocks)) in AFNO_FUSED_SHAPES
 
 
+def afno_mlp_block_size_ok(bs: int) -> bool:
+    """Block sizes the ``afno_mlp`` kernel takes; mirrors afno_mlp_route() in csrc/spectral/spectral.h
+    (checked equal against ``afno_mlp_info`` in tests/test_afno_mlp.py).  A Python constant for the same
+    reason as ``AFNO_FUSED_SHAPES``."""
+    return 16 <= bs <= 256 and bs % 16 == 0
+
+
+def afno_mlp_available(x: torch.Tensor, num_blocks: int) -> bool:
+    """The generic AFNO route (any H, any mode window) can run its block MLP on ``afno_mlp``: a GPU
+    tensor [..., C] whose block size the kernel takes."""
+    if not x.is_cuda or torch.jit.is_tracing():  # exported graphs keep the ops the exporter knows
+        return False
+    C, nb = int(x.shape[-1]), int(num_blocks)
+    return nb >= 1 and C % nb == 0 and afno_mlp_block_size_ok(C // nb)
+
+
+def afno_spectral_mlp(xf: torch.Tensor, w1, b1, w2, b2, lam: float, split: bool, owner=None) -> torch.Tensor:
+    """Block-diagonal complex MLP + softshrink on a transformed fp32 spectrum ``xf`` [..., C, 2]
+    (``afno_mlp``): bf16 MFMA operands, or the bf16x3 split GEMMs with ``split`` (fp32 models).  The
+    packed weights are the fused filter's (same cache entries on ``owner``)."""
+    if owner is not None:
+        packed = module_cached(owner, f"afno_w{'3' if split else ''}", (w1, b1, w2, b2),
+                               lambda: pack_afno_weights(w1, b1, w2, b2, split))
+    else:
+        packed = pack_afno_weights(w1, b1, w2, b2, split)
+    w1t, w2t, b1p, b2p = packed
+    return _ops().afno_mlp(xf, w1t, w2t, b1p, b2p, float(lam))
+
+
 def afno_spectral_h(xw: torch.Tensor, w1, b1, w2, b2, num_blocks: int, lam: float, owner=None) -> torch.Tensor:
     """Fused H-filter on the W half spectrum ``xw`` [B, H, KM, C, 2]: bf16 MFMA operands for a
     bf16 spectrum, the bf16x3 split GEMMs for an fp32 spectrum."""
@@ -199,6 +229,8 @@ def afno_block_amd(blk, x: torch.Tensor, pending=None, split_out: bool = False):
             return afno_block_fused_f32(blk, x, pending, part, split_out)
         return afno_block_fused(blk, x, pending, part)
     x, yn = afno_block_spectral(blk, x, pending)
+    if _mlp_hand_ok(blk, x):
+        return afno_block_mlp_hand(blk, x, yn), None
     return x, afno_block_mlp(blk, yn)
 
 
@@ -432,6 +464,34 @@ def afno_block_mlp(blk, yn: torch.Tensor) -> torch.Tensor:
     hid = _gelu_linear(yn.reshape(-1, C), m.fc1)
     note_fallback("mlp_fc2", "ATen / hipBLASLt fc2 (generic AFNO shape)", yn)
     y = F.linear(hid, m.fc2.weight, m.fc2.bias)
+    return y.reshape(B, H, W, C)
+
+
+def _mlp_hand_ok(blk, x: torch.Tensor) -> bool:
+    """Generic-shape block whose filter runs on ``afno_mlp`` and whose MLP widths fit the hand GEMM:
+    the MLP leaves ATen too (:func:`afno_block_mlp_hand`)."""
+    if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)) or torch.jit.is_tracing():
+        return False
+    return afno_mlp_available(x, blk.filter.cfg.num_blocks) and _mlp_gemm_ok(blk.mlp, x.dtype == torch.float32)
+
+
+def afno_block_mlp_hand(blk, x: torch.Tensor, yn: torch.Tensor) -> torch.Tensor:
+    """x + fc2(GELU(fc1(yn))) on the hand MFMA GEMM for the generic-shape block (``yn`` = LN2(x) from
+    the LayerNorm op; LN folding stays with the fused blocks), called as the fused blocks call it:
+    bf16 ``linear`` with cfg.bf16_gelu's activation, fp32 ``split_bf16`` + ``linear3`` with the exact
+    erf GELU; bias and residual in the fc2 epilogue."""
+    m = blk.mlp
+    B, H, W, C = (int(d) for d in x.shape)
+    ops = _ops()
+    if x.dtype == torch.float32:
+        w1s = module_cached(m, "fc1_split", (m.fc1.weight,), lambda: split_bf16(m.fc1.weight))
+        w2s = module_cached(m, "fc2_split", (m.fc2.weight,), lambda: split_bf16(m.fc2.weight))
+        hid = ops.linear3(split_bf16(yn.reshape(-1, C)), w1s, m.fc1.bias, 1, None, True)
+        y = ops.linear3(hid, w2s, m.fc2.bias, 0, x.reshape(-1, C), False)
+    else:
+        act = _BF16_GELU_ACT[getattr(blk.filter.cfg, "bf16_gelu", "erf")]
+        hid = ops.linear(yn.reshape(-1, C), m.fc1.weight, m.fc1.bias, act, None)
+        y = ops.linear(hid, m.fc2.weight, m.fc2.bias, 0, x.reshape(-1, C))
     return y.reshape(B, H, W, C)
 
 
