@@ -526,6 +526,109 @@ at::Tensor fno_c2r_meta(const at::Tensor& yw, int64_t W, std::optional<at::Scala
   return at::empty({yw.size(0), yw.size(1), yw.size(2), W}, yw.options().dtype(out_dtype.has_value() ? *out_dtype : at::kFloat));
 }
 
+// ------------------------------------------------------------------ Legendre transform (latitude half of an SHT)
+// x [..., Q, M, 2] fp32 (complex as trailing re/im), table [M, R, Q] fp32 -> y [..., R, M, 2] fp32:
+//   y[n, r, m, :] = sum_q table[m, r, q] x[n, q, m, :]
+// tri declares the structurally zero part of the table (1: rows r < m, 2: columns q < m), which every
+// implementation treats as zero.  table_split: the table as the kernel reads it, split_bf16(rows=False) of the
+// table zero-padded to [M, ceil16(R), ceil32(Q)] -> bf16 [2, M, Rp, Qp]; built per call when absent.
+void check_legendre(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
+  TORCH_CHECK(x.scalar_type() == at::kFloat && table.scalar_type() == at::kFloat,
+              "legendre: x and table must be float32 (other precisions of the spherical transforms are not built), got ",
+              x.scalar_type(), " and ", table.scalar_type());
+  TORCH_CHECK(x.dim() >= 3 && x.size(-1) == 2 && table.dim() == 3, "legendre: x [..., Q, M, 2], table [M, R, Q]");
+  TORCH_CHECK(x.size(-3) == table.size(2), "legendre: x has ", x.size(-3), " points along the transformed dim, the table ",
+              table.size(2));
+  TORCH_CHECK(x.size(-2) == table.size(0), "legendre: mode counts differ: x has ", x.size(-2), ", the table ",
+              table.size(0));
+  TORCH_CHECK(tri >= 0 && tri <= 2, "legendre: tri must be 0, 1 or 2");
+  TORCH_CHECK(table.size(0) < (1 << 30) && table.size(1) < (1 << 30) && table.size(2) >= 1 && table.size(2) < (1 << 30),
+              "legendre: bad table size");
+  if (present(ts)) {
+    const int64_t Rp = (table.size(1) + 15) / 16 * 16, Qp = (table.size(2) + 31) / 32 * 32;
+    TORCH_CHECK(ts->scalar_type() == at::kBFloat16 && ts->sizes() == at::IntArrayRef({2, table.size(0), Rp, Qp}) &&
+                    ts->device() == x.device(),
+                "legendre: table_split must be bfloat16 [2, M, ceil16(R), ceil32(Q)] on the device of x");
+  }
+}
+
+std::vector<int64_t> legendre_out_shape(const at::Tensor& x, const at::Tensor& table) {
+  std::vector<int64_t> shape = x.sizes().vec();
+  shape[shape.size() - 3] = table.size(1);
+  return shape;
+}
+
+at::Tensor legendre_cpu(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
+  check_legendre(x, table, ts, tri);
+  const int64_t M = table.size(0), R = table.size(1), Q = table.size(2);
+  at::Tensor t = table;
+  if (tri != 0) {
+    at::Tensor m = at::arange(M, table.options().dtype(at::kLong)).unsqueeze(1);
+    at::Tensor k = at::arange(tri == 1 ? R : Q, table.options().dtype(at::kLong)).unsqueeze(0);
+    at::Tensor keep = k.ge(m).to(at::kFloat);  // [M, R] or [M, Q]
+    t = table * (tri == 1 ? keep.unsqueeze(2) : keep.unsqueeze(1));
+  }
+  at::Tensor y = at::einsum("mrq,nqmc->nrmc", {t, x.reshape({-1, Q, M, 2})});
+  return y.reshape(legendre_out_shape(x, table)).contiguous();
+}
+
+at::Tensor legendre_cuda(const at::Tensor& x_, const at::Tensor& table_, const c10::optional<at::Tensor>& ts_,
+                         int64_t tri) {
+  check_legendre(x_, table_, ts_, tri);
+  const c10::DeviceGuard guard(x_.device());
+  const int64_t M = table_.size(0), R = table_.size(1), Q = table_.size(2);
+  const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
+  auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
+  at::Tensor x = x_.contiguous();
+  // 8-byte loads of one mode's (re, im): a view at an odd float offset gets its own copy
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 != 0) x = x.clone();
+  at::Tensor ts;
+  if (present(ts_)) {
+    ts = ts_->contiguous();
+  } else {
+    TORCH_CHECK(table_.device() == x.device(), "legendre: table must be on the device of x");
+    at::Tensor tp = at::constant_pad_nd(table_, {0, Qp - Q, 0, Rp - R}).contiguous();
+    ts = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
+    if (tp.numel() > 0)
+      launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
+                        static_cast<int>(Qp), false, stream);
+  }
+  at::Tensor y = at::empty(legendre_out_shape(x, table_), x.options());
+  if (y.numel() == 0) return y;
+  const int64_t N = x.numel() / (Q * M * 2);
+  TORCH_CHECK(N < (int64_t(1) << 31) / 16, "legendre: too many fields");
+  LegendreLaunch p;
+  p.x = x.data_ptr<float>();
+  p.th = reinterpret_cast<const uint16_t*>(ts.data_ptr());
+  p.tl = p.th + M * Rp * Qp;
+  p.y = y.data_ptr<float>();
+  p.N = N;
+  p.Q = static_cast<int>(Q);
+  p.R = static_cast<int>(R);
+  p.M = static_cast<int>(M);
+  p.tri = static_cast<int>(tri);
+  launch_legendre(p, stream);
+  return checked(y, "legendre");
+}
+
+at::Tensor legendre_meta(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>&, int64_t) {
+  return at::empty(legendre_out_shape(x, table), x.options());
+}
+
+// Which tiling legendre runs for (Q, R, M, real columns = 2 x fields, tri) -- host only, no device (the companion
+// of fno_pointwise_info): "mfma MT=8 CT=2 slabs=23 rtiles=4 rgroups=1 mgroups=8 ctiles=3 lds=41472 wgs=24 tri=1"
+std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri) {
+  TORCH_CHECK(Q >= 1 && R >= 1 && M >= 1 && cols >= 2 && cols % 2 == 0 && Q < (1 << 30) && R < (1 << 30) &&
+                  M < (1 << 30) && cols < (int64_t(1) << 31) / 8,
+              "amd_dft.legendre_info: Q, R, M must be >= 1 and cols a positive even count");
+  TORCH_CHECK(tri >= 0 && tri <= 2, "amd_dft.legendre_info: tri must be 0, 1 or 2");
+  const LegendreRoute r = legendre_route(Q, R, M, cols, static_cast<int>(tri));
+  return "mfma MT=" + std::to_string(r.mt) + " CT=" + std::to_string(r.ct) + " slabs=" + std::to_string(r.slabs) +
+         " rtiles=" + std::to_string(r.rtiles) + " rgroups=" + std::to_string(r.rgroups) +
+         " mgroups=" + std::to_string(r.mgroups) + " ctiles=" + std::to_string(r.ctiles) +
+         " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri);
+}
+
 // ------------------------------------------------------------------ LayerNorm (+ residual)
 std::tuple<at::Tensor, at::Tensor> layer_norm_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                   double eps, const std::optional<at::Tensor>& residual) {
@@ -751,6 +854,8 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("fno_c2r_pw(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor");
   m.def("fno_c2r_pw_info(int cin, int cout, int m, int W, bool bf16) -> str", &amd_dft::fno_c2r_pw_info);
   m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
+  m.def("legendre(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor");
+  m.def("legendre_info(int Q, int R, int M, int cols, int tri) -> str", &amd_dft::legendre_info);
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
@@ -765,6 +870,7 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cuda));
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cuda));
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cuda));
+  m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cuda));
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
@@ -779,6 +885,7 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cpu));
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cpu));
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cpu));
+  m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cpu));
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
@@ -793,4 +900,5 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("fno_pointwise", &amd_dft::fno_pointwise_meta);
   m.impl("fno_c2r_pw", &amd_dft::fno_c2r_pw_meta);
   m.impl("fno_c2r", &amd_dft::fno_c2r_meta);
+  m.impl("legendre", &amd_dft::legendre_meta);
 }

@@ -1,0 +1,258 @@
+// Legendre transform along latitude, per longitudinal mode, on MFMA -- the second half of a spherical
+// harmonic transform (the first is the truncated real FFT along longitude, csrc/fft):
+//   y[n, r, m, :] = sum_q T[m, r, q] * x[n, q, m, :]
+// x [N, Q, M, 2] fp32 (complex as trailing re/im), T [M, R, Q] real, y [N, R, M, 2] fp32; n runs over
+// batch x channels.  Forward: Q = nlat, R = lmax, T = w_k P_l^m(cos theta_k); inverse: Q = lmax, R = nlat,
+// T = P transposed.  One kernel serves both.
+//
+// Precision: the project's bf16x3 form, A.B = Ah.Bh + Al.Bh + Ah.Bl on v_mfma_f32_16x16x32_bf16 with fp32
+// accumulation.  T arrives split on the host side as two bf16 planes (hi, lo), zero-padded to
+// [M, Rp = ceil16(R), Qp = ceil32(Q)], so every A fragment is one aligned 16-byte global load that cannot
+// leave the table; x is split as it is staged into LDS.
+//
+// GEMM orientation per mode m: C[r][col] with the 2 N real columns col = 2 n + (re | im).
+//   A = T[m][r][q]: lane holds T[r0 + l15][q0 + 8 lq + 0..7] of both planes, straight from global memory
+//       (waves own different modes, so a table element is read by one wave of the workgroup);
+//   B = x[q][col]: from the LDS slab image [plane][mode][col][32 q] bf16, column pitch 80 B (16-byte reads
+//       of 16 consecutive columns touch all 64 banks once), modes 256 / MT bytes further apart so the
+//       staging stores of a wave (modes x q pairs) touch 64 different banks.
+// A workgroup (4 waves) owns MT = 4 MW consecutive modes (wave w: modes m0 + w MW + 0..MW-1), NT = 8 CT
+// fields n (CT 16-column tiles) and one group of 4 row tiles (64 rows r; grid z walks the groups), and loops
+// over Q in 32-deep slabs.  Global reads of x: every (n, q) row is one contiguous run of 8 MT bytes; global
+// writes of y go through LDS one 16-row tile at a time so every (n, r) row is one contiguous run of 8 MT bytes.
+//   Edges: q >= Q, n >= N and m >= M are WRITTEN as zeros into the slab image (the padded table is zero
+//   there too, but 0 * stale-NaN is NaN); nothing is loaded or stored outside x, the padded table or y.
+//   The mode count M is a run-time value without a limit.
+//   tri = 1 (rows r < m of T are zero, the forward transform): 16-row tiles entirely below m issue no table
+//   loads and no MFMAs, a row group entirely below the workgroup's first mode reads nothing at all, and
+//   rows r < m are stored as exact zeros.  tri = 2 (columns q < m are zero, the inverse transform): slabs
+//   entirely below the workgroup's first mode are skipped, a wave skips the slabs below its own mode, and
+//   x[q < m] is staged as zero.  Either way the result is the dense product with that part of T zero.
+// The next slab's x values are loaded into registers before the current slab's MFMAs; the table fragments
+// of a slab are requested before the slab is written to LDS.  No atomics: bit-reproducible run to run.
+//
+// LDS per workgroup (legendre_lds_bytes): 41472 B at MT = 8, CT = 2; 20992 B at 4 x 2; 10752 B at 4 x 1.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "spectral.h"
+
+namespace amd_dft {
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  bf16x2 v;
+  v[0] = static_cast<__bf16>(a);
+  v[1] = static_cast<__bf16>(b);
+  return __builtin_bit_cast(uint32_t, v);
+}
+// hi = bf16(a, b); lo = bf16(a - hi.a, b - hi.b)
+__device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_t& lo) {
+  hi = pk_bf16(a, b);
+  lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
+}
+
+template <int CT, int MW>
+__global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__ x, const uint16_t* __restrict__ th,
+                                                       const uint16_t* __restrict__ tl, float* __restrict__ y,
+                                                       int64_t N, int Q, int R, int M, int Rp, int Qp, int tri) {
+  constexpr int MT = 4 * MW;                       // modes per workgroup
+  constexpr int NT = 8 * CT;                       // fields n per workgroup
+  constexpr int NC = 16 * CT;                      // real columns per workgroup
+  constexpr int RT = kLegRowTiles;
+  constexpr int MLS = NC * kLegXPitch + 256 / MT;  // bytes per mode of a slab plane
+  constexpr int PLANE = MT * MLS;                  // bytes per plane (hi, lo)
+  constexpr int XI = NT * MT / 16;                 // staged (n, q pair, mode) items per thread and slab
+  constexpr int YP = 2 * MT + 2;                   // floats per (r, n) row of the output image
+  constexpr int YR = NT * YP + 4;                  // floats per r of the output image
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int m0 = blockIdx.x * MT;
+  const int64_t n0 = static_cast<int64_t>(blockIdx.y) * NT;
+  const int r0 = blockIdx.z * 16 * RT;
+  const float2* x2 = reinterpret_cast<const float2*>(x);
+  float2* y2 = reinterpret_cast<float2*>(y);
+
+  const int nslab = (Q + kLegSlab - 1) / kLegSlab;
+  // tri = 2: all columns q < m0 are zero for every mode here; tri = 1: a row group below m0 is all zero
+  int s0 = tri == 2 ? m0 / kLegSlab : 0;
+  if (tri == 1 && r0 + 16 * RT <= m0) s0 = nslab;
+
+  // which (mode, row tile) pairs of this wave are live (wave-uniform)
+  bool live[MW][RT];
+#pragma unroll
+  for (int j = 0; j < MW; ++j) {
+    const int m = m0 + wv * MW + j;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int rg = r0 + 16 * rt;
+      live[j][rt] = m < M && rg < R && !(tri == 1 && rg + 15 < m);
+    }
+  }
+
+  float xr[XI][4];
+  auto load_slab = [&](int s) {
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int idx = tid + 256 * i;
+      const int ml = idx % MT, qp = (idx / MT) & 15, nl = idx / (MT * 16);
+      const int m = m0 + ml, q = s * kLegSlab + 2 * qp;
+      const int64_t n = n0 + nl;
+      float2 a = make_float2(0.f, 0.f), b = a;
+      if (m < M && n < N) {
+        const float2* src = x2 + ((n * Q + q) * M + m);
+        const int qmin = tri == 2 ? m : 0;
+        if (q < Q && q >= qmin) a = src[0];
+        if (q + 1 < Q && q + 1 >= qmin) b = src[M];
+      }
+      xr[i][0] = a.x;
+      xr[i][1] = a.y;
+      xr[i][2] = b.x;
+      xr[i][3] = b.y;
+    }
+  };
+
+  f32x4 acc[MW][RT][CT];
+#pragma unroll
+  for (int j = 0; j < MW; ++j)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) acc[j][rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (s0 < nslab) load_slab(s0);
+  for (int s = s0; s < nslab; ++s) {
+    // ---- this slab's table fragments (global, both planes): lane = T[m][rg + l15][32 s + 8 lq + 0..7]
+    uint4 ah[MW][RT], al[MW][RT];
+#pragma unroll
+    for (int j = 0; j < MW; ++j) {
+      const int m = m0 + wv * MW + j;
+      const bool mode_live = !(tri == 2 && s * kLegSlab + kLegSlab - 1 < m);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        if (live[j][rt] && mode_live) {
+          const int64_t off = (static_cast<int64_t>(m) * Rp + r0 + 16 * rt + l15) * Qp + s * kLegSlab + 8 * lq;
+          ah[j][rt] = *reinterpret_cast<const uint4*>(th + off);
+          al[j][rt] = *reinterpret_cast<const uint4*>(tl + off);
+        }
+      }
+    }
+    __syncthreads();  // every wave is done reading the previous slab
+    // ---- the slab image: x split into bf16 (hi, lo), q pairs packed, zeros outside x
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int idx = tid + 256 * i;
+      const int ml = idx % MT, qp = (idx / MT) & 15, nl = idx / (MT * 16);
+      char* dst = smem + ml * MLS + 2 * nl * kLegXPitch + 4 * qp;
+      uint32_t hr, lr, hi, li;
+      split_pk(xr[i][0], xr[i][2], hr, lr);
+      split_pk(xr[i][1], xr[i][3], hi, li);
+      *reinterpret_cast<uint32_t*>(dst) = hr;
+      *reinterpret_cast<uint32_t*>(dst + kLegXPitch) = hi;
+      *reinterpret_cast<uint32_t*>(dst + PLANE) = lr;
+      *reinterpret_cast<uint32_t*>(dst + PLANE + kLegXPitch) = li;
+    }
+    __syncthreads();
+    // ---- the next slab's global loads, in flight during the MFMAs
+    if (s + 1 < nslab) load_slab(s + 1);
+    // ---- MFMAs: live (mode, row tile) pairs only
+#pragma unroll
+    for (int j = 0; j < MW; ++j) {
+      const int ml = wv * MW + j;
+      const bool mode_live = !(tri == 2 && s * kLegSlab + kLegSlab - 1 < m0 + ml);
+      if (!mode_live) continue;
+      bf16x8 bh[CT], bl[CT];
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const char* src = smem + ml * MLS + (16 * ct + l15) * kLegXPitch + 16 * lq;
+        bh[ct] = *reinterpret_cast<const bf16x8*>(src);
+        bl[ct] = *reinterpret_cast<const bf16x8*>(src + PLANE);
+      }
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        if (live[j][rt]) {
+          const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[j][rt]), Al = __builtin_bit_cast(bf16x8, al[j][rt]);
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct) {
+            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bh[ct], acc[j][rt][ct], 0, 0, 0);
+            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, bh[ct], acc[j][rt][ct], 0, 0, 0);
+            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bl[ct], acc[j][rt][ct], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+
+  // ---- store, one 16-row tile at a time through LDS: image [r][n][mode][re | im], so a thread writes one
+  // mode's (re, im) and consecutive threads consecutive modes of one (n, r) row of y
+  float* ys = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    const int rg0 = r0 + 16 * rt;
+    if (rg0 >= R) break;  // block-uniform
+    __syncthreads();      // the slab image (rt = 0) or the previous tile's image has been read
+#pragma unroll
+    for (int j = 0; j < MW; ++j) {
+      const int ml = wv * MW + j;
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const int col = 16 * ct + l15;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          ys[(4 * lq + i) * YR + (col >> 1) * YP + 2 * ml + (col & 1)] = acc[j][rt][ct][i];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int idx = tid + 256 * i;
+      const int ml = idx % MT, r = (idx / MT) & 15, nl = idx / (MT * 16);
+      const int m = m0 + ml, rg = rg0 + r;
+      const int64_t n = n0 + nl;
+      if (m < M && rg < R && n < N) {
+        float2 v = *reinterpret_cast<const float2*>(ys + r * YR + nl * YP + 2 * ml);
+        if (tri == 1 && rg < m) v = make_float2(0.f, 0.f);
+        y2[(n * R + rg) * M + m] = v;
+      }
+    }
+  }
+}
+
+template <int CT, int MW>
+void launch_inst(const LegendreLaunch& p, const LegendreRoute& r, hipStream_t st) {
+  const dim3 grid(r.mgroups, r.ctiles, r.rgroups);
+  hipLaunchKernelGGL((legendre_kernel<CT, MW>), grid, dim3(256), static_cast<size_t>(r.lds), st, p.x, p.th, p.tl, p.y,
+                     p.N, p.Q, p.R, p.M, r.rtiles * 16, r.slabs * kLegSlab, p.tri);
+}
+
+}  // namespace
+
+void launch_legendre(const LegendreLaunch& p, void* stream) {
+  if (p.N == 0 || p.R == 0 || p.M == 0) return;
+  if (p.Q < 1) throw std::runtime_error("amd_dft: legendre: Q must be >= 1");
+  if (p.tri < 0 || p.tri > 2) throw std::runtime_error("amd_dft: legendre: tri must be 0, 1 or 2");
+  const LegendreRoute r = legendre_route(p.Q, p.R, p.M, 2 * p.N, p.tri);
+  if (r.ctiles > 65535 || r.rgroups > 65535) throw std::runtime_error("amd_dft: legendre: tensor too large");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (r.mt == 8) {
+    if (r.ct == 2) launch_inst<2, 2>(p, r, st);
+    else launch_inst<1, 2>(p, r, st);
+  } else {
+    if (r.ct == 2) launch_inst<2, 1>(p, r, st);
+    else launch_inst<1, 1>(p, r, st);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: legendre launch: ") + hipGetErrorString(e));
+}
+
+}  // namespace amd_dft

@@ -138,6 +138,63 @@ inline FnoPointwiseRoute fno_pointwise_route(int cin, int cout, bool bf16, int64
   return r;
 }
 
+// ---- Legendre transform (the latitude half of a spherical harmonic transform, legendre.hip):
+//   y[n, r, m, :] = sum_q T[m, r, q] * x[n, q, m, :]      (x complex as trailing re/im, T real, per mode m)
+// forward: Q = nlat, R = lmax, T = w_k P_l^m(cos theta_k); inverse: Q = lmax, R = nlat, T = P transposed.
+struct LegendreLaunch {
+  const float* x;      // [N, Q, M, 2] fp32
+  const uint16_t* th;  // [M, Rp, Qp] bf16, hi plane of T zero-padded to Rp = ceil16(R), Qp = ceil32(Q)
+  const uint16_t* tl;  // the lo plane, bf16(T - hi)
+  float* y;            // [N, R, M, 2] fp32
+  int64_t N;
+  int Q, R, M;
+  int tri = 0;         // 0: dense; 1: rows r < m are zero; 2: columns q < m are zero
+};
+// Which tiling a call takes (host only; launch_legendre and the legendre_info op both answer from here).
+// A workgroup (4 waves) owns mt consecutive modes (a wave mt / 4 of them), 8 ct fields n (ct 16-column
+// MFMA tiles of the 2 N real columns) and one group of up to 64 rows r; it walks Q in 32-deep slabs.
+// The tile starts at 8 modes x 16 fields and shrinks -- first to 4 modes, then to 8 fields -- while the grid
+// would leave most of the 256 CUs without a workgroup (or the shape has nothing to fill the larger tile).
+constexpr int kLegSlab = 32;        // q per K slab
+constexpr int kLegRowTiles = 4;     // 16-row tiles per row group (64 x 16 ct accumulators per mode)
+constexpr int kLegXPitch = 80;      // bytes per LDS column of a slab: 32 bf16 + 16 B (conflict-free 16-byte reads)
+constexpr int64_t kLegFillWgs = 256;
+struct LegendreRoute {
+  int mt;          // modes per workgroup: 8 or 4
+  int ct;          // 16-column tiles per workgroup: 2 or 1
+  int slabs;       // ceil(Q / 32)
+  int rtiles;      // ceil(R / 16)
+  int rgroups;     // ceil(rtiles / 4) (grid z)
+  int mgroups;     // ceil(M / mt)     (grid x)
+  int ctiles;      // ceil(cols / (16 ct)) (grid y)
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t wgs;     // workgroups
+};
+inline int64_t legendre_lds_bytes(int mt, int ct) {
+  // slab image: 2 planes x mt modes x (16 ct columns x 80 B + a pad that spreads the modes over the banks);
+  // output image (one 16-row tile, modes innermost): 16 x (8 ct x (2 mt + 2) + 4) floats -- they share the space
+  const int64_t xs = 2LL * mt * (16 * ct * kLegXPitch + 256 / mt);
+  const int64_t ys = 16LL * (8 * ct * (2 * mt + 2) + 4) * 4;
+  return xs > ys ? xs : ys;
+}
+inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/) {
+  LegendreRoute r{};
+  r.slabs = static_cast<int>((Q + kLegSlab - 1) / kLegSlab);
+  r.rtiles = static_cast<int>((R + 15) / 16);
+  r.rgroups = (r.rtiles + kLegRowTiles - 1) / kLegRowTiles;
+  auto count = [&](int mt, int ct) { return ((M + mt - 1) / mt) * ((cols + 16 * ct - 1) / (16 * ct)) * r.rgroups; };
+  r.mt = 8;
+  r.ct = 2;
+  if (M <= 4 || count(r.mt, r.ct) < kLegFillWgs) r.mt = 4;
+  if (cols <= 16 || count(r.mt, r.ct) < kLegFillWgs) r.ct = 1;
+  r.mgroups = static_cast<int>((M + r.mt - 1) / r.mt);
+  r.ctiles = static_cast<int>((cols + 16 * r.ct - 1) / (16 * r.ct));
+  r.lds = legendre_lds_bytes(r.mt, r.ct);
+  r.wgs = count(r.mt, r.ct);
+  return r;
+}
+void launch_legendre(const LegendreLaunch& p, void* stream);
+
 // ---- LayerNorm over the last dim (bf16/fp32 I/O, fp32 statistics)
 struct LayerNormLaunch {
   const void* x;

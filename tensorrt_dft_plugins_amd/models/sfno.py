@@ -1,0 +1,168 @@
+"""Spherical FNO (SFNO, Bonev et al. 2023; FourCastNet v2) layers on the MI355X spherical harmonic transform.
+
+An SFNO layer is an FNO layer with the 2-D FFT replaced by a spherical harmonic transform (SHT): a real FFT along
+longitude followed by a Legendre transform along latitude (conventions: :mod:`..ops.sht`).
+
+* ``RealSHT`` / ``InverseRealSHT``: the torch-harmonics modules by name and argument order, complex tensors in and
+  out, so they drop into code written against that package.
+* ``SphericalConv2d``: the SFNO "diagonal" spectral operator y[b,o,l,m] = sum_i x[b,i,l,m] w[i,o,l].
+* ``SFNOBlock``: ``act(SphericalConv2d(x) + Conv1x1(x))``.
+
+Backends: ``"amd"`` (the default: ``sht`` -> ``fno_mix`` -> ``isht`` and the ``fno_pointwise`` tail, hand kernels
+on a GPU, their ATen counterparts on CPU tensors) and ``"torch"`` (torch.fft + einsum on a table built in fp64: the
+numerics oracle; it follows the input's precision, so an fp64 input gives an fp64 reference).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..ops import sht as S
+
+__all__ = ["RealSHT", "InverseRealSHT", "SphericalConv2d", "SFNOBlock"]
+
+# SphericalConv2d expands its [Cin, Cout, lmax] weights over m for fno_mix; beyond this many bytes it does not
+EXPAND_LIMIT_BYTES = 256 << 20
+
+
+def _check_backend(backend: str) -> str:
+    if backend not in ("torch", "amd"):
+        raise ValueError(f"backend must be 'torch' or 'amd', got {backend!r}")
+    return backend
+
+
+class _SHTBase(nn.Module):
+    def __init__(self, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None,
+                 grid: str = "equiangular", backend: str = "amd"):
+        super().__init__()
+        self.nlat, self.nlon, self.grid = int(nlat), int(nlon), grid
+        self.lmax, self.mmax = S._defaults(self.nlat, self.nlon, lmax, mmax)
+        self.backend = _check_backend(backend)
+        _, w, P = S.legendre_tables(self.nlat, self.lmax, self.mmax, grid)
+        self._table64 = self._make_table(w, P)  # fp64, host: the "torch" backend casts it to the input's precision
+
+    def _table(self, ref: torch.Tensor) -> torch.Tensor:
+        return self._table64.to(device=ref.device, dtype=ref.real.dtype if ref.is_complex() else ref.dtype)
+
+    def extra_repr(self) -> str:
+        return (f"nlat={self.nlat}, nlon={self.nlon}, lmax={self.lmax}, mmax={self.mmax}, grid={self.grid!r}, "
+                f"backend={self.backend!r}")
+
+
+class RealSHT(_SHTBase):
+    """Forward real SHT: real [..., nlat, nlon] -> complex [..., lmax, mmax]."""
+
+    @staticmethod
+    def _make_table(w, P):
+        return torch.from_numpy(P * w[None, None, :])  # [mmax, lmax, nlat]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.shape[-2] != self.nlat or x.shape[-1] != self.nlon:
+            raise ValueError(f"RealSHT: expected a [..., {self.nlat}, {self.nlon}] grid, got {tuple(x.shape)}")
+        if self.backend == "amd":
+            return torch.view_as_complex(S.sht(x, self.lmax, self.mmax, self.grid))
+        xf = 2.0 * np.pi * torch.fft.rfft(x, dim=-1, norm="forward")[..., :self.mmax]
+        c = torch.einsum("mlk,...kmc->...lmc", self._table(x), torch.view_as_real(xf))
+        return torch.view_as_complex(c.contiguous())
+
+
+class InverseRealSHT(_SHTBase):
+    """Inverse real SHT: complex [..., lmax, mmax] -> real [..., nlat, nlon]."""
+
+    @staticmethod
+    def _make_table(w, P):
+        return torch.from_numpy(np.ascontiguousarray(P.transpose(0, 2, 1)))  # [mmax, nlat, lmax]
+
+    def forward(self, c: torch.Tensor) -> torch.Tensor:
+        if c.shape[-2] != self.lmax or c.shape[-1] != self.mmax:
+            raise ValueError(f"InverseRealSHT: expected [..., {self.lmax}, {self.mmax}] coefficients, got {tuple(c.shape)}")
+        if self.backend == "amd":
+            return S.isht(c, self.nlat, self.nlon, self.grid)
+        xf = torch.einsum("mkl,...lmc->...kmc", self._table(c), torch.view_as_real(c))
+        return torch.fft.irfft(torch.view_as_complex(xf.contiguous()), n=self.nlon, dim=-1, norm="forward")
+
+
+class SphericalConv2d(nn.Module):
+    """The SFNO "diagonal" spectral operator: one complex weight per (in, out, degree l), shared by all orders m:
+    ``y = isht(mix(sht(x)))`` with ``mix[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l]``; ``weight`` is [Cin, Cout, lmax, 2].
+
+    The amd backend runs ``sht`` -> ``fno_mix`` -> ``isht``.  ``fno_mix`` takes one weight per mode, so the weights
+    are expanded over m once and cached on the module ([Cin, Cout, lmax * mmax, 2] fp32).  Where that expansion
+    would exceed 256 MiB the layer does not build it: it counts a ``sfno_mix`` fallback (``fallback_counts()``,
+    an error under strict mode) and mixes with ``torch.einsum``.  A mixing kernel that reads the per-degree
+    weights directly is left to a later change."""
+
+    def __init__(self, in_ch: int, out_ch: int, nlat: int, nlon: int, lmax: Optional[int] = None,
+                 mmax: Optional[int] = None, grid: str = "equiangular", backend: str = "amd"):
+        super().__init__()
+        self.in_ch, self.out_ch = in_ch, out_ch
+        self.sht = RealSHT(nlat, nlon, lmax, mmax, grid, backend)
+        self.isht = InverseRealSHT(nlat, nlon, self.sht.lmax, self.sht.mmax, grid, backend)
+        self.backend = _check_backend(backend)
+        scale = 1.0 / (in_ch * out_ch)
+        self.weight = nn.Parameter(scale * torch.rand(in_ch, out_ch, self.sht.lmax, 2))
+
+    def set_backend(self, backend: str) -> "SphericalConv2d":
+        self.backend = self.sht.backend = self.isht.backend = _check_backend(backend)
+        return self
+
+    def expanded_bytes(self) -> int:
+        return self.in_ch * self.out_ch * self.sht.lmax * self.sht.mmax * 2 * 4
+
+    def _expanded_weight(self) -> torch.Tensor:
+        from ..ops.spectral import module_cached
+
+        L, M = self.sht.lmax, self.sht.mmax
+
+        def build():
+            w = self.weight.detach().float()
+            return w[:, :, :, None, :].expand(-1, -1, -1, M, -1).reshape(self.in_ch, self.out_ch, L * M, 2).contiguous()
+
+        return module_cached(self, "w_expanded", (self.weight,), build)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.backend == "torch":
+            wc = torch.view_as_complex(self.weight.to(x.dtype).contiguous())
+            return self.isht(torch.einsum("bilm,iol->bolm", self.sht(x), wc))
+        from ..ops.spectral import fno_spectral_mix, note_fallback
+
+        B = x.shape[0]
+        L, M = self.sht.lmax, self.sht.mmax
+        c = S.sht(x, L, M, self.sht.grid)  # [B, Cin, L, M, 2]
+        if self.expanded_bytes() > EXPAND_LIMIT_BYTES:
+            note_fallback("sfno_mix", "per-degree weights too large to expand over m for fno_mix: torch.einsum", x)
+            wc = torch.view_as_complex(self.weight.float().contiguous())
+            y = torch.view_as_real(torch.einsum("bilm,iol->bolm", torch.view_as_complex(c), wc)).contiguous()
+        else:
+            y = fno_spectral_mix(c.reshape(B, self.in_ch, L * M, 2), self._expanded_weight())
+        return S.isht(y.reshape(B, self.out_ch, L, M, 2), self.sht.nlat, self.sht.nlon, self.sht.grid)
+
+
+class SFNOBlock(nn.Module):
+    """One SFNO layer: ``act(SphericalConv2d(x) + Conv1x1(x))``.  On the amd backend the tail (1x1 convolution,
+    bias, the spectral addend and the GELU) is one ``fno_pointwise`` call."""
+
+    def __init__(self, width: int, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None,
+                 grid: str = "equiangular", activation: bool = True, backend: str = "amd"):
+        super().__init__()
+        self.spectral = SphericalConv2d(width, width, nlat, nlon, lmax, mmax, grid, backend)
+        self.w = nn.Conv2d(width, width, 1)
+        self.activation = activation
+        self.backend = _check_backend(backend)
+
+    def set_backend(self, backend: str) -> "SFNOBlock":
+        self.backend = _check_backend(backend)
+        self.spectral.set_backend(backend)
+        return self
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        spec = self.spectral(x)
+        if self.backend == "amd":
+            return torch.ops.amd_dft.fno_pointwise(spec, x, self.w.weight.reshape(self.w.out_channels, -1).float(),
+                                                   self.w.bias.float(), self.activation)
+        y = spec.to(x.dtype) + self.w(x)
+        return F.gelu(y) if self.activation else y

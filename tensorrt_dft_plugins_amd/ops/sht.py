@@ -1,0 +1,164 @@
+"""Spherical harmonic transforms (SHT) for spherical FNO / FourCastNet-v2 style models.
+
+A real SHT is a truncated real FFT along longitude followed by a Legendre transform along latitude.  The first
+half is the pruned ``r2c`` / ``c2r`` of :mod:`.dft`; the second is the ``legendre`` op
+(``csrc/spectral/legendre.hip``: a per-mode real matrix applied along latitude to the complex spectrum, bf16x3 on
+MFMA, fp32 in and out).
+
+Conventions (the torch-harmonics "ortho" ones, so weights trained there carry over):
+
+* grid: ``nlat`` colatitudes theta_k, north to south, and ``nlon`` longitudes phi_j = 2 pi j / nlon.
+  ``"legendre-gauss"``: cos theta_k are the Gauss-Legendre nodes; ``"equiangular"``: theta_k = pi k / (nlat - 1),
+  poles included, Clenshaw-Curtis weights.  Both sets of weights sum to 2.
+* basis: the associated Legendre functions Pb_l^m with the Condon-Shortley phase, normalised so that
+  2 pi int Pb_l^m Pb_l'^m dx = delta_ll' (Pb_0^0 = 1 / sqrt(4 pi)).
+* forward: F[k, m] = (2 pi / nlon) sum_j f[k, j] exp(-i m phi_j) for 0 <= m < mmax, then
+  c[l, m] = sum_k w_k Pb_l^m(cos theta_k) F[k, m] for 0 <= l < lmax (zero where l < m) -> ``[..., lmax, mmax, 2]``.
+* inverse: F[k, m] = sum_l Pb_l^m(cos theta_k) c[l, m], then the Hermitian-completed sum over m: an unnormalised
+  C2R from ``mmax`` stored modes (``torch.fft.irfft(..., n=nlon, norm="forward")``).
+* defaults: ``lmax = nlat``, ``mmax = min(lmax, nlon // 2 + 1)``.
+
+Precision is fp32 (the tables are built in fp64 on the host and rounded once).
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .._loader import load_plugins
+from .dft import _from_complex
+
+__all__ = ["legendre_tables", "sht", "isht", "sht_tables", "legendre_split", "GRIDS"]
+
+GRIDS = ("equiangular", "legendre-gauss")
+
+
+def _ops():
+    load_plugins()
+    return torch.ops.amd_dft
+
+
+def _clenshaw_curtis(n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """cos theta_k at theta_k = pi k / (n - 1) and the Clenshaw-Curtis weights, closed form:
+    w_k = c_k / N (1 - sum_{j=1}^{N/2} b_j / (4 j^2 - 1) cos(2 j theta_k)), N = n - 1, c = 1 at the poles else 2,
+    b_j = 1 at j = N / 2 else 2."""
+    if n < 2:
+        raise ValueError("the equiangular grid needs nlat >= 2")
+    N = n - 1
+    theta = np.pi * np.arange(n, dtype=np.float64) / N
+    w = np.ones(n, dtype=np.float64)
+    for j in range(1, N // 2 + 1):
+        b = 1.0 if 2 * j == N else 2.0
+        w -= b / (4.0 * j * j - 1.0) * np.cos(2.0 * j * theta)
+    c = np.full(n, 2.0)
+    c[0] = c[-1] = 1.0
+    return np.cos(theta), c * w / N
+
+
+def legendre_tables(nlat: int, lmax: int, mmax: int, grid: str = "equiangular"):
+    """(nodes cos theta_k [nlat], north to south; weights w_k [nlat]; Pb [mmax, lmax, nlat]), all float64 numpy.
+
+    Pb[m, l, k] = Pb_l^m(cos theta_k), zero where l < m, by the standard recurrences carried in fp64:
+    Pb_m^m = -sqrt((2m + 1) / (2m)) sin(theta) Pb_{m-1}^{m-1}, then in l
+    Pb_l^m = sqrt((4 l^2 - 1) / (l^2 - m^2)) (x Pb_{l-1}^m - sqrt(((l - 1)^2 - m^2) / (4 (l - 1)^2 - 1)) Pb_{l-2}^m)."""
+    if grid == "legendre-gauss":
+        x, w = np.polynomial.legendre.leggauss(nlat)
+        x, w = x[::-1].copy(), w[::-1].copy()
+    elif grid == "equiangular":
+        x, w = _clenshaw_curtis(nlat)
+    else:
+        raise ValueError(f"grid must be one of {GRIDS}, got {grid!r}")
+    if lmax < 1 or mmax < 1:
+        raise ValueError("lmax and mmax must be >= 1")
+    s = np.sqrt(np.maximum(0.0, 1.0 - x * x))
+    P = np.zeros((mmax, lmax, nlat), dtype=np.float64)
+    pmm = np.full(nlat, 1.0 / math.sqrt(4.0 * math.pi))
+    for m in range(min(mmax, lmax)):
+        if m > 0:
+            pmm = -math.sqrt((2.0 * m + 1.0) / (2.0 * m)) * s * pmm
+        P[m, m] = pmm
+        for l in range(m + 1, lmax):
+            a = math.sqrt((4.0 * l * l - 1.0) / (l * l - m * m))
+            b = math.sqrt(((l - 1.0) ** 2 - m * m) / (4.0 * (l - 1.0) ** 2 - 1.0)) if l > m + 1 else 0.0
+            P[m, l] = a * (x * P[m, l - 1] - (b * P[m, l - 2] if l > m + 1 else 0.0))
+    return x, w, P
+
+
+def legendre_split(table: torch.Tensor) -> torch.Tensor:
+    """A Legendre table [M, R, Q] as the kernel reads it: zero-padded to [M, ceil16(R), ceil32(Q)] and split into
+    bf16 (hi, lo) planes -> [2, M, Rp, Qp] (``split_bf16(rows=False)``)."""
+    M, R, Q = table.shape
+    tp = F.pad(table.float(), (0, -Q % 32, 0, -R % 16)).contiguous()
+    return _ops().split_bf16(tp, False)
+
+
+class _Tables:
+    """The fp32 operands of one (grid, truncation) on one device: ``fwd`` [mmax, lmax, nlat] = w_k Pb,
+    ``inv`` [mmax, nlat, lmax] = Pb transposed, and on a GPU their split forms."""
+
+    def __init__(self, nlat, nlon, lmax, mmax, grid, device):
+        _, w, P = legendre_tables(nlat, lmax, mmax, grid)
+        self.fwd = torch.from_numpy(P * w[None, None, :]).float().contiguous().to(device)
+        self.inv = torch.from_numpy(np.ascontiguousarray(P.transpose(0, 2, 1))).float().to(device)
+        cuda = torch.device(device).type == "cuda"
+        self.fwd_split = legendre_split(self.fwd) if cuda else None
+        self.inv_split = legendre_split(self.inv) if cuda else None
+
+
+_CACHE: dict = {}
+
+
+def sht_tables(nlat: int, nlon: int, lmax: int, mmax: int, grid: str, device) -> _Tables:
+    """Tables cached per (nlat, nlon, lmax, mmax, grid, device); they live as long as the process, so a captured
+    hipGraph that reads them stays valid."""
+    key = (int(nlat), int(nlon), int(lmax), int(mmax), grid, str(torch.device(device)))
+    t = _CACHE.get(key)
+    if t is None:
+        t = _CACHE[key] = _Tables(nlat, nlon, lmax, mmax, grid, device)
+    return t
+
+
+def _defaults(nlat: int, nlon: int, lmax: Optional[int], mmax: Optional[int]) -> Tuple[int, int]:
+    lmax = int(lmax) if lmax is not None else nlat
+    mmax = int(mmax) if mmax is not None else min(lmax, nlon // 2 + 1)
+    if not 1 <= mmax <= nlon // 2 + 1:
+        raise ValueError(f"mmax must be in [1, nlon // 2 + 1 = {nlon // 2 + 1}], got {mmax}")
+    if lmax < 1:
+        raise ValueError("lmax must be >= 1")
+    return lmax, mmax
+
+
+def sht(x: torch.Tensor, lmax: Optional[int] = None, mmax: Optional[int] = None,
+        grid: str = "equiangular") -> torch.Tensor:
+    """Forward real SHT of ``x`` [..., nlat, nlon] (fp32) -> coefficients [..., lmax, mmax, 2] (trailing re/im).
+
+    R2C along longitude keeping ``mmax`` modes, scaled by 2 pi / nlon, then the forward Legendre transform
+    (``legendre`` with ``tri=1``: rows l < m are zero).  The same two ops run on CPU tensors (ATen kernels)."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"sht: x must be float32, got {x.dtype}")
+    nlat, nlon = int(x.shape[-2]), int(x.shape[-1])
+    lmax, mmax = _defaults(nlat, nlon, lmax, mmax)
+    t = sht_tables(nlat, nlon, lmax, mmax, grid, x.device)
+    ops = _ops()
+    xf = ops.r2c(x, [x.dim() - 1], 2.0 * math.pi / nlon, [mmax, 0], torch.float32)  # [..., nlat, mmax, 2]
+    return ops.legendre(xf, t.fwd, t.fwd_split, 1)
+
+
+def isht(c: torch.Tensor, nlat: int, nlon: int, grid: str = "equiangular") -> torch.Tensor:
+    """Inverse real SHT of ``c`` [..., lmax, mmax, 2] (or complex [..., lmax, mmax]) -> [..., nlat, nlon] fp32.
+
+    The inverse Legendre transform (``legendre`` with ``tri=2``: columns l < m are zero), then an unnormalised C2R
+    along longitude from the ``mmax`` stored modes."""
+    c = _from_complex(c)
+    if c.dtype != torch.float32:
+        raise TypeError(f"isht: c must be float32 / complex64, got {c.dtype}")
+    lmax, mmax = int(c.shape[-3]), int(c.shape[-2])
+    _defaults(nlat, nlon, lmax, mmax)
+    t = sht_tables(nlat, nlon, lmax, mmax, grid, c.device)
+    ops = _ops()
+    xf = ops.legendre(c, t.inv, t.inv_split, 2)  # [..., nlat, mmax, 2]
+    return ops.c2r(xf, [xf.dim() - 2], [nlon], 1.0, [mmax, 0], torch.float32)
