@@ -629,6 +629,113 @@ std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t
          " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri);
 }
 
+// ------------------------------------------------------------------ SFNO per-degree channel mixing
+// c [B, Cin, L, M, 2] fp32 (spherical harmonic coefficients, complex as trailing re/im), w [Cin, Cout, L, 2] fp32
+// -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
+// tri = 1 declares c zero where l < m (the spectrum of a real field): every implementation ignores c there and
+// returns exact zeros.  w_split: the weights as the kernel reads them (sfno_mix_split); built per call when absent.
+void check_sfno_mix(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
+  TORCH_CHECK(c.scalar_type() == at::kFloat && w.scalar_type() == at::kFloat,
+              "sfno_mix: c and w must be float32 (other precisions of the spherical layers are not built), got ",
+              c.scalar_type(), " and ", w.scalar_type());
+  TORCH_CHECK(c.dim() == 5 && c.size(4) == 2 && w.dim() == 4 && w.size(3) == 2,
+              "sfno_mix: c [B, Cin, L, M, 2], w [Cin, Cout, L, 2]");
+  TORCH_CHECK(c.size(1) == w.size(0) && w.size(0) >= 1, "sfno_mix: c has ", c.size(1), " input channels, w ", w.size(0));
+  TORCH_CHECK(c.size(2) == w.size(2), "sfno_mix: degree counts differ: c has ", c.size(2), ", w ", w.size(2));
+  TORCH_CHECK(tri == 0 || tri == 1, "sfno_mix: tri must be 0 or 1");
+  TORCH_CHECK(w.size(0) < (1 << 28) && w.size(1) < (1 << 21) && c.size(2) <= 65535 &&
+                  c.size(0) * c.size(3) < (int64_t(1) << 30),
+              "sfno_mix: tensor too large");
+  if (present(ws)) {
+    const int64_t Op = (w.size(1) + 15) / 16 * 16, Kp = (2 * w.size(0) + 31) / 32 * 32;
+    TORCH_CHECK(ws->scalar_type() == at::kBFloat16 && ws->sizes() == at::IntArrayRef({2, w.size(2), Op, Kp}) &&
+                    ws->device() == c.device(),
+                "sfno_mix: w_split must be bfloat16 [2, L, ceil16(Cout), ceil32(2 Cin)] on the device of c");
+  } else {
+    TORCH_CHECK(w.device() == c.device(), "sfno_mix: w must be on the device of c");
+  }
+}
+
+// w [Cin, Cout, L, 2] fp32 -> bf16 [2, L, ceil16(Cout), ceil32(2 Cin)]: the (hi, lo) planes of the degree-major real
+// form W[l][o][2 i] = Wr[i, o, l], W[l][o][2 i + 1] = Wi[i, o, l], zero-padded.  Any device.
+at::Tensor sfno_mix_split(const at::Tensor& w) {
+  TORCH_CHECK(w.scalar_type() == at::kFloat, "sfno_mix_split: w must be float32, got ", w.scalar_type());
+  TORCH_CHECK(w.dim() == 4 && w.size(3) == 2 && w.size(0) >= 1, "sfno_mix_split: w [Cin, Cout, L, 2]");
+  const int64_t Cin = w.size(0), Cout = w.size(1), L = w.size(2);
+  const int64_t Op = (Cout + 15) / 16 * 16, Kp = (2 * Cin + 31) / 32 * 32;
+  at::Tensor wp = at::constant_pad_nd(w.detach().permute({2, 1, 0, 3}).reshape({L, Cout, 2 * Cin}),
+                                      {0, Kp - 2 * Cin, 0, Op - Cout})
+                      .contiguous();
+  if (wp.is_cuda()) {
+    const c10::DeviceGuard guard(wp.device());
+    at::Tensor ts = at::empty({2, L, Op, Kp}, wp.options().dtype(at::kBFloat16));
+    if (wp.numel() > 0)
+      launch_split_bf16(wp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), wp.numel(),
+                        static_cast<int>(Kp), false, c10::hip::getCurrentHIPStream(wp.device().index()).stream());
+    return ts;
+  }
+  at::Tensor hi = wp.to(at::kBFloat16);
+  at::Tensor lo = (wp - hi.to(at::kFloat)).to(at::kBFloat16);
+  return at::stack({hi, lo}, 0).contiguous();
+}
+
+at::Tensor sfno_mix_cpu(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
+  check_sfno_mix(c, w, ws, tri);
+  at::Tensor y = at::view_as_real(at::einsum("bilm,iol->bolm", {at::view_as_complex(c.contiguous()),
+                                                               at::view_as_complex(w.contiguous())}))
+                     .contiguous();
+  if (tri == 1) {
+    at::Tensor l = at::arange(c.size(2), c.options().dtype(at::kLong)).unsqueeze(1);
+    at::Tensor m = at::arange(c.size(3), c.options().dtype(at::kLong)).unsqueeze(0);
+    y.masked_fill_(l.lt(m).unsqueeze(-1), 0.0);
+  }
+  return y;
+}
+
+at::Tensor sfno_mix_cuda(const at::Tensor& c_, const at::Tensor& w_, const c10::optional<at::Tensor>& ws_, int64_t tri) {
+  check_sfno_mix(c_, w_, ws_, tri);
+  const c10::DeviceGuard guard(c_.device());
+  const int64_t B = c_.size(0), Cin = c_.size(1), L = c_.size(2), M = c_.size(3), Cout = w_.size(1);
+  at::Tensor c = c_.contiguous();
+  // 8-byte loads of one order's (re, im): a view at an odd float offset gets its own copy
+  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 != 0) c = c.clone();
+  at::Tensor ws = present(ws_) ? ws_->contiguous() : sfno_mix_split(w_);
+  at::Tensor y = at::empty({B, Cout, L, M, 2}, c.options());
+  if (y.numel() == 0) return y;
+  const int64_t plane = ws.numel() / 2;
+  SfnoMixLaunch p;
+  p.c = c.data_ptr<float>();
+  p.wh = reinterpret_cast<const uint16_t*>(ws.data_ptr());
+  p.wl = p.wh + plane;
+  p.y = y.data_ptr<float>();
+  p.B = static_cast<int>(B);
+  p.Cin = static_cast<int>(Cin);
+  p.Cout = static_cast<int>(Cout);
+  p.L = static_cast<int>(L);
+  p.M = static_cast<int>(M);
+  p.tri = static_cast<int>(tri);
+  launch_sfno_mix(p, c10::hip::getCurrentHIPStream(c.device().index()).stream());
+  return checked(y, "sfno_mix");
+}
+
+at::Tensor sfno_mix_meta(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>&, int64_t) {
+  return at::empty({c.size(0), w.size(1), c.size(2), c.size(3), 2}, c.options());
+}
+
+// The tiling sfno_mix runs for (B, Cin, Cout, L, M, tri) -- host only, no device (the companion of legendre_info):
+// "mfma coltile=64 slabs=4 otiles=4 ogroups=1 ctiles=3 lds=20480 wgs=363 grid=540 tri=1"
+std::string sfno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64_t M, int64_t tri) {
+  TORCH_CHECK(B >= 1 && Cin >= 1 && Cout >= 1 && L >= 1 && M >= 1 && Cin < (1 << 28) && Cout < (1 << 21) &&
+                  L <= 65535 && B * M < (int64_t(1) << 30),
+              "amd_dft.sfno_mix_info: B, Cin, Cout, L, M must be >= 1 (L <= 65535, B * M < 2^30)");
+  TORCH_CHECK(tri == 0 || tri == 1, "amd_dft.sfno_mix_info: tri must be 0 or 1");
+  const SfnoMixRoute r = sfno_mix_route(B, Cin, Cout, L, M, static_cast<int>(tri));
+  return "mfma coltile=" + std::to_string(r.coltile) + " slabs=" + std::to_string(r.slabs) +
+         " otiles=" + std::to_string(r.otiles) + " ogroups=" + std::to_string(r.ogroups) +
+         " ctiles=" + std::to_string(r.ctiles) + " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) +
+         " grid=" + std::to_string(r.grid) + " tri=" + std::to_string(tri);
+}
+
 // ------------------------------------------------------------------ LayerNorm (+ residual)
 std::tuple<at::Tensor, at::Tensor> layer_norm_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                   double eps, const std::optional<at::Tensor>& residual) {
@@ -856,6 +963,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
   m.def("legendre(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor");
   m.def("legendre_info(int Q, int R, int M, int cols, int tri) -> str", &amd_dft::legendre_info);
+  m.def("sfno_mix(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor");
+  m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
+  m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri) -> str", &amd_dft::sfno_mix_info);
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
@@ -871,6 +981,7 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cuda));
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cuda));
   m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cuda));
+  m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cuda));
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
@@ -886,6 +997,7 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cpu));
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cpu));
   m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cpu));
+  m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cpu));
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
@@ -901,4 +1013,5 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("fno_c2r_pw", &amd_dft::fno_c2r_pw_meta);
   m.impl("fno_c2r", &amd_dft::fno_c2r_meta);
   m.impl("legendre", &amd_dft::legendre_meta);
+  m.impl("sfno_mix", &amd_dft::sfno_mix_meta);
 }

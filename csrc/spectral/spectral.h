@@ -195,6 +195,56 @@ inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t col
 }
 void launch_legendre(const LegendreLaunch& p, void* stream);
 
+// ---- SFNO per-degree channel mixing (sfno_mix.hip):
+//   y[b, o, l, m] = sum_i c[b, i, l, m] * w[i, o, l]       (complex; one weight per degree l, shared by all orders m)
+struct SfnoMixLaunch {
+  const float* c;      // [B, Cin, L, M, 2] fp32
+  const uint16_t* wh;  // [L, Op, Kp] bf16, hi plane of the real form of w: row o, k = 2 i -> Wr[i, o, l],
+                       // k = 2 i + 1 -> Wi[i, o, l], zero-padded to Op = ceil16(Cout), Kp = ceil32(2 Cin)
+  const uint16_t* wl;  // the lo plane, bf16(W - hi)
+  float* y;            // [B, Cout, L, M, 2] fp32
+  int B, Cin, Cout, L, M;
+  int tri = 0;         // 0: dense; 1: c is zero where l < m -- orders m > l are not read, y is 0.0 there
+};
+// The tiling of a call (host only; launch_sfno_mix and the sfno_mix_info op both answer from here).  A workgroup
+// (4 waves) owns one degree, one group of up to 64 output channels and one tile of 64 complex (128 real) columns;
+// the columns of a degree are its live orders flattened over the batch, (b, m) -> b Ml + m with Ml = M, or
+// min(M, l + 1) under tri = 1.  One tiling, no fill rule: a degree with fewer columns leaves waves of its last
+// tile idle, which skip their loads and MFMAs.  The grid is (column tiles of the fullest degree, groups, L);
+// workgroups past a degree's last tile only help store the zeros of l < m.
+constexpr int kSfnoSlab = 32;       // k per K slab (16 input channels)
+constexpr int kSfnoRowTiles = 4;    // 16-row tiles per output-channel group
+constexpr int kSfnoColTile = 64;    // complex columns per workgroup (8 16-column MFMA tiles of real columns)
+constexpr int kSfnoXPitch = 80;     // bytes per LDS column of a slab: 32 bf16 + 16 B (conflict-free 16-byte reads)
+struct SfnoMixRoute {
+  int slabs;       // ceil(2 Cin / 32)
+  int otiles;      // ceil(Cout / 16)
+  int ogroups;     // ceil(otiles / 4) (grid y)
+  int coltile;     // complex columns per workgroup
+  int64_t ctiles;  // column tiles of the fullest degree (grid x)
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t wgs;     // workgroups with a non-empty column tile (the ones that load and multiply)
+  int64_t grid;    // workgroups launched
+};
+inline int64_t sfno_mix_lds_bytes() { return 2LL * 2 * kSfnoColTile * kSfnoXPitch; }
+inline SfnoMixRoute sfno_mix_route(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64_t M, int tri) {
+  SfnoMixRoute r{};
+  r.slabs = static_cast<int>((2 * Cin + kSfnoSlab - 1) / kSfnoSlab);
+  r.otiles = static_cast<int>((Cout + 15) / 16);
+  r.ogroups = (r.otiles + kSfnoRowTiles - 1) / kSfnoRowTiles;
+  r.coltile = kSfnoColTile;
+  auto tiles = [&](int64_t ml) { return (B * ml + kSfnoColTile - 1) / kSfnoColTile; };
+  const int64_t full = tri == 1 && L < M ? L : M;  // live orders of the fullest degree
+  r.ctiles = tiles(full);
+  int64_t live = 0;
+  for (int64_t l = 0; l < L; ++l) live += tiles(tri == 1 && l + 1 < M ? l + 1 : M);
+  r.lds = sfno_mix_lds_bytes();
+  r.wgs = live * r.ogroups;
+  r.grid = r.ctiles * r.ogroups * L;
+  return r;
+}
+void launch_sfno_mix(const SfnoMixLaunch& p, void* stream);
+
 // ---- LayerNorm over the last dim (bf16/fp32 I/O, fp32 statistics)
 struct LayerNormLaunch {
   const void* x;

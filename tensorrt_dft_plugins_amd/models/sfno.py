@@ -8,9 +8,14 @@ longitude followed by a Legendre transform along latitude (conventions: :mod:`..
 * ``SphericalConv2d``: the SFNO "diagonal" spectral operator y[b,o,l,m] = sum_i x[b,i,l,m] w[i,o,l].
 * ``SFNOBlock``: ``act(SphericalConv2d(x) + Conv1x1(x))``.
 
-Backends: ``"amd"`` (the default: ``sht`` -> ``fno_mix`` -> ``isht`` and the ``fno_pointwise`` tail, hand kernels
-on a GPU, their ATen counterparts on CPU tensors) and ``"torch"`` (torch.fft + einsum on a table built in fp64: the
+Backends: ``"amd"`` (the default: ``sht`` -> mix -> ``isht`` and the ``fno_pointwise`` tail, hand kernels on a
+GPU, their ATen counterparts on CPU tensors) and ``"torch"`` (torch.fft + einsum on a table built in fp64: the
 numerics oracle; it follows the input's precision, so an fp64 input gives an fp64 reference).
+
+The mix of the amd backend is one of two ops (``mix=`` of the layers): ``fno_mix`` on the weights expanded over
+every order m, or ``sfno_mix`` (csrc/spectral/sfno_mix.hip), which reads the per-degree weights directly -- one
+bf16x3 MFMA GEMM per degree -- and needs no expansion.  ``"auto"`` expands up to ``EXPAND_LIMIT_BYTES`` and runs
+``sfno_mix`` on device tensors above it; ``"degree"`` always runs ``sfno_mix``.
 """
 from __future__ import annotations
 
@@ -25,8 +30,15 @@ from ..ops import sht as S
 
 __all__ = ["RealSHT", "InverseRealSHT", "SphericalConv2d", "SFNOBlock"]
 
-# SphericalConv2d expands its [Cin, Cout, lmax] weights over m for fno_mix; beyond this many bytes it does not
+# SphericalConv2d(mix="auto") expands its [Cin, Cout, lmax] weights over m for fno_mix; beyond this many bytes it
+# does not, and mixes per degree
 EXPAND_LIMIT_BYTES = 256 << 20
+
+
+def _check_mix(mix: str) -> str:
+    if mix not in ("auto", "degree"):
+        raise ValueError(f"mix must be 'auto' or 'degree', got {mix!r}")
+    return mix
 
 
 def _check_backend(backend: str) -> str:
@@ -90,16 +102,22 @@ class SphericalConv2d(nn.Module):
     """The SFNO "diagonal" spectral operator: one complex weight per (in, out, degree l), shared by all orders m:
     ``y = isht(mix(sht(x)))`` with ``mix[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l]``; ``weight`` is [Cin, Cout, lmax, 2].
 
-    The amd backend runs ``sht`` -> ``fno_mix`` -> ``isht``.  ``fno_mix`` takes one weight per mode, so the weights
-    are expanded over m once and cached on the module ([Cin, Cout, lmax * mmax, 2] fp32).  Where that expansion
-    would exceed 256 MiB the layer does not build it: it counts a ``sfno_mix`` fallback (``fallback_counts()``,
-    an error under strict mode) and mixes with ``torch.einsum``.  A mixing kernel that reads the per-degree
-    weights directly is left to a later change."""
+    The amd backend runs ``sht`` -> mix -> ``isht``; ``mix`` picks the middle op:
+
+    * ``"auto"`` (the default).  Up to 256 MiB of expanded weights (``EXPAND_LIMIT_BYTES``): ``fno_mix``, which
+      takes one weight per mode, on the weights expanded over m once and cached on the module
+      ([Cin, Cout, lmax * mmax, 2] fp32).  Above it the expansion is not built: a device tensor runs ``sfno_mix``
+      (the per-degree MFMA kernel, ``tri=1`` since ``sht`` returns zeros where l < m) on the split weight table
+      cached on the module (``w_degree``, as many bytes as the weights; rebuilt when the weights change, kept
+      alive for captured graphs); a CPU tensor notes a ``sfno_mix`` fallback (not counted on CPU tensors) and mixes
+      with ``torch.einsum``.
+    * ``"degree"``: ``sfno_mix`` on every device and at every size; the expansion is never built."""
 
     def __init__(self, in_ch: int, out_ch: int, nlat: int, nlon: int, lmax: Optional[int] = None,
-                 mmax: Optional[int] = None, grid: str = "equiangular", backend: str = "amd"):
+                 mmax: Optional[int] = None, grid: str = "equiangular", backend: str = "amd", mix: str = "auto"):
         super().__init__()
         self.in_ch, self.out_ch = in_ch, out_ch
+        self.mix = _check_mix(mix)
         self.sht = RealSHT(nlat, nlon, lmax, mmax, grid, backend)
         self.isht = InverseRealSHT(nlat, nlon, self.sht.lmax, self.sht.mmax, grid, backend)
         self.backend = _check_backend(backend)
@@ -124,16 +142,24 @@ class SphericalConv2d(nn.Module):
 
         return module_cached(self, "w_expanded", (self.weight,), build)
 
+    def _degree_weight(self) -> torch.Tensor:
+        from ..ops.spectral import module_cached, sfno_mix_split
+
+        return module_cached(self, "w_degree", (self.weight,), lambda: sfno_mix_split(self.weight))
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.backend == "torch":
             wc = torch.view_as_complex(self.weight.to(x.dtype).contiguous())
             return self.isht(torch.einsum("bilm,iol->bolm", self.sht(x), wc))
-        from ..ops.spectral import fno_spectral_mix, note_fallback
+        from ..ops.spectral import fno_spectral_mix, note_fallback, sfno_mix
 
         B = x.shape[0]
         L, M = self.sht.lmax, self.sht.mmax
         c = S.sht(x, L, M, self.sht.grid)  # [B, Cin, L, M, 2]
-        if self.expanded_bytes() > EXPAND_LIMIT_BYTES:
+        above = self.expanded_bytes() > EXPAND_LIMIT_BYTES
+        if self.mix == "degree" or (above and x.is_cuda):
+            y = sfno_mix(c, self.weight.detach().float(), self._degree_weight(), tri=1)
+        elif above:
             note_fallback("sfno_mix", "per-degree weights too large to expand over m for fno_mix: torch.einsum", x)
             wc = torch.view_as_complex(self.weight.float().contiguous())
             y = torch.view_as_real(torch.einsum("bilm,iol->bolm", torch.view_as_complex(c), wc)).contiguous()
@@ -144,12 +170,13 @@ class SphericalConv2d(nn.Module):
 
 class SFNOBlock(nn.Module):
     """One SFNO layer: ``act(SphericalConv2d(x) + Conv1x1(x))``.  On the amd backend the tail (1x1 convolution,
-    bias, the spectral addend and the GELU) is one ``fno_pointwise`` call."""
+    bias, the spectral addend and the GELU) is one ``fno_pointwise`` call.  ``mix`` goes to the ``SphericalConv2d``
+    (``"auto"`` or ``"degree"``)."""
 
     def __init__(self, width: int, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None,
-                 grid: str = "equiangular", activation: bool = True, backend: str = "amd"):
+                 grid: str = "equiangular", activation: bool = True, backend: str = "amd", mix: str = "auto"):
         super().__init__()
-        self.spectral = SphericalConv2d(width, width, nlat, nlon, lmax, mmax, grid, backend)
+        self.spectral = SphericalConv2d(width, width, nlat, nlon, lmax, mmax, grid, backend, mix)
         self.w = nn.Conv2d(width, width, 1)
         self.activation = activation
         self.backend = _check_backend(backend)

@@ -32,7 +32,7 @@ from . import dft as D
 __all__ = ["pack_afno_weights", "afno_fused_available", "afno_spectral_h", "c2r_w_add", "layer_norm",
            "afno_mlp_available", "afno_mlp_block_size_ok", "afno_spectral_mlp", "afno_block_mlp_hand",
            "afno_block_amd", "afno_block_fused", "afno_block_fused_f32",
-           "afno_block_spectral", "afno_block_mlp", "fno_spectral_mix", "split_bf16", "module_cached",
+           "afno_block_spectral", "afno_block_mlp", "fno_spectral_mix", "sfno_mix", "sfno_mix_split", "split_bf16", "module_cached",
            "fallback_counts", "fallback_reset", "note_fallback", "unsplit_bf16", "LnCarry", "pending_bias", "SplitRows"]
 
 
@@ -500,3 +500,19 @@ def fno_spectral_mix(xm: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     xm [B, Cin, M, 2], w [Cin, Cout, M, 2] -> [B, Cout, M, 2] (fp32).  Native op on every device
     (CPU: ATen einsum; GPU: csrc/spectral/fno_mix.hip), so it also exports as one ONNX node."""
     return _ops().fno_mix(xm.contiguous(), w.contiguous())
+
+
+def sfno_mix_split(w: torch.Tensor) -> torch.Tensor:
+    """SFNO weights ``w`` [Cin, Cout, L, 2] (fp32) as the ``sfno_mix`` kernel reads them: the real form repacked
+    degree-major, W[l][o][2i] = Wr[i,o,l] and W[l][o][2i+1] = Wi[i,o,l], zero-padded and split into bf16 (hi, lo)
+    planes -> [2, L, ceil16(Cout), ceil32(2 Cin)].  Any device; as many bytes as ``w`` itself."""
+    return _ops().sfno_mix_split(w.detach().float())
+
+
+def sfno_mix(c: torch.Tensor, w: torch.Tensor, w_split: Optional[torch.Tensor] = None, tri: int = 0) -> torch.Tensor:
+    """SFNO per-degree channel mixing y[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l] on complex-as-pair tensors
+    c [B, Cin, L, M, 2], w [Cin, Cout, L, 2] -> [B, Cout, L, M, 2] (fp32).  ``tri=1``: ``c`` is the spectrum of a real
+    field (zero where l < m); it is not read there and the result is exactly 0.0 there.  ``w_split``: the cached
+    :func:`sfno_mix_split` of ``w`` (built per call when absent).  Native op on every device (CPU: ATen einsum;
+    GPU: csrc/spectral/sfno_mix.hip, bf16x3 on MFMA)."""
+    return _ops().sfno_mix(c, w, w_split, int(tri))
