@@ -16,6 +16,23 @@
 namespace amd_dft {
 namespace {
 
+// ------------------------------------------------------------------ `_out` variants
+// An `_out` op runs the launch path of its allocating op into a caller's tensor.  out must be exactly what the
+// allocating op returns -- shape, dtype, device, contiguous -- and on the device start where the kernel's widest
+// store is aligned.  Anything else is an error, never a copy: a copy would move the result out of the caller's buffer
+// (tests/test_kernel_bounds_gpu.py puts guard bands around it).
+void check_out(const at::Tensor& out, at::IntArrayRef shape, const at::Tensor& like, const char* op) {
+  TORCH_CHECK(out.defined() && out.sizes() == shape && out.scalar_type() == like.scalar_type() &&
+                  out.device() == like.device() && out.is_contiguous(),
+              op, ": out must be a contiguous ", like.scalar_type(), " tensor of shape ", shape, " on ", like.device(),
+              ", got ", out.scalar_type(), " ", out.sizes(), " on ", out.device(),
+              out.is_contiguous() ? "" : " (not contiguous)");
+}
+void check_out_aligned(const at::Tensor& out, uintptr_t bytes, const char* op) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % bytes == 0, op, ": out must start on a ", bytes,
+              "-byte boundary (the kernel's stores)");
+}
+
 // ------------------------------------------------------------------ AFNO spectral filter
 // xw [B, H, KM, C, 2] fp32 (W-direction half spectrum), w1t/w2t [NB, 2BS, 2BS] bf16 ([n][k]),
 // b1/b2 [NB, 2BS] fp32.  Returns [B, H, KM, C, 2] fp32:
@@ -302,9 +319,23 @@ at::Tensor fno_pointwise_cpu(const c10::optional<at::Tensor>& spec, const at::Te
   return y.reshape(shape).to(x.scalar_type());
 }
 
-at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec_, const at::Tensor& x_, const at::Tensor& w,
-                              const c10::optional<at::Tensor>& bias, bool gelu) {
-  const c10::DeviceGuard guard(x_.device());
+std::vector<int64_t> fno_pointwise_out_shape(const at::Tensor& x, const at::Tensor& w) {
+  TORCH_CHECK(x.dim() >= 2 && w.dim() >= 1, "fno_pointwise: x [B, Cin, ...], w [Cout, Cin]");
+  std::vector<int64_t> shape = x.sizes().vec();
+  shape[1] = w.size(0);
+  return shape;
+}
+
+at::Tensor& fno_pointwise_out_cpu(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
+                                  const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
+  check_out(out, fno_pointwise_out_shape(x, w), x, "fno_pointwise_out");
+  out.copy_(fno_pointwise_cpu(spec, x, w, bias, gelu));
+  return out;
+}
+
+// the launch path of fno_pointwise and fno_pointwise_out: y is the contiguous [B, Cout, ...] result in x's dtype
+void fno_pointwise_run(const c10::optional<at::Tensor>& spec_, const at::Tensor& x_, const at::Tensor& w,
+                       const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
   TORCH_CHECK(x_.dim() >= 2, "fno_pointwise: x [B, Cin, ...]");
   TORCH_CHECK(x_.scalar_type() == at::kFloat || x_.scalar_type() == at::kBFloat16,
               "fno_pointwise: x must be float32 or bfloat16");
@@ -323,9 +354,6 @@ at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec_, const at::
     spec = spec_->to(x.scalar_type()).contiguous();
   }
   at::Tensor bf = f32_or_undef(bias);
-  std::vector<int64_t> shape = x.sizes().vec();
-  shape[1] = Cout;
-  at::Tensor y = at::empty(shape, x.options());
   FnoPointwiseLaunch p;
   p.spec = spec.defined() ? spec.data_ptr() : nullptr;
   p.x = x.data_ptr();
@@ -339,7 +367,24 @@ at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec_, const at::
   p.bf16 = x.scalar_type() == at::kBFloat16;
   p.gelu = gelu;
   launch_fno_pointwise(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+}
+
+at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
+                              const c10::optional<at::Tensor>& bias, bool gelu) {
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(fno_pointwise_out_shape(x, w), x.options());
+  fno_pointwise_run(spec, x, w, bias, gelu, y);
   return checked(y, "fno_pointwise");
+}
+
+// out: any element-aligned start -- the kernels fall to per-element I/O off the 4-element boundary
+at::Tensor& fno_pointwise_out_cuda(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
+                                   const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
+  const c10::DeviceGuard guard(x.device());
+  check_out(out, fno_pointwise_out_shape(x, w), x, "fno_pointwise_out");
+  fno_pointwise_run(spec, x, w, bias, gelu, out);
+  checked(out, "fno_pointwise_out");
+  return out;
 }
 
 // Which kernel fno_pointwise runs for (Cin, Cout, dtype, P) on aligned tensors -- host only, no device
@@ -358,6 +403,11 @@ at::Tensor fno_pointwise_meta(const c10::optional<at::Tensor>& spec, const at::T
   std::vector<int64_t> shape = x.sizes().vec();
   shape[1] = w.size(0);
   return at::empty(shape, x.options());
+}
+
+at::Tensor& fno_pointwise_out_meta(const c10::optional<at::Tensor>&, const at::Tensor&, const at::Tensor&,
+                                   const c10::optional<at::Tensor>&, bool, at::Tensor& out) {
+  return out;
 }
 
 // ------------------------------------------------------------------ FNO layer tail (C2R-W + pointwise)
@@ -380,10 +430,21 @@ at::Tensor fno_c2r_pw_cpu(const at::Tensor& yw, const at::Tensor& x, const at::T
   return fno_pointwise_cpu(spec, x, wc.reshape({yw.size(1), x.size(1)}), bias, gelu);
 }
 
-at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at::Tensor& wc_,
-                           const c10::optional<at::Tensor>& bias, bool gelu) {
-  const c10::DeviceGuard guard(x_.device());
-  check_fno_c2r(yw_, x_, wc_);
+std::vector<int64_t> fno_c2r_pw_out_shape(const at::Tensor& yw, const at::Tensor& x) {
+  return {x.size(0), yw.size(1), x.size(2), x.size(3)};
+}
+
+at::Tensor& fno_c2r_pw_out_cpu(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
+                               const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
+  check_fno_c2r(yw, x, wc);
+  check_out(out, fno_c2r_pw_out_shape(yw, x), x, "fno_c2r_pw_out");
+  out.copy_(fno_c2r_pw_cpu(yw, x, wc, bias, gelu));
+  return out;
+}
+
+// the launch path of fno_c2r_pw and fno_c2r_pw_out: y is the contiguous [B, Cout, H, W] result in x's dtype
+void fno_c2r_pw_run(const at::Tensor& yw_, const at::Tensor& x_, const at::Tensor& wc_,
+                    const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
   TORCH_CHECK(x_.scalar_type() == at::kFloat || x_.scalar_type() == at::kBFloat16,
               "fno_c2r_pw: x must be float32 or bfloat16");
   const int64_t B = x_.size(0), Cin = x_.size(1), H = x_.size(2), W = x_.size(3), Cout = yw_.size(1),
@@ -400,7 +461,7 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
                                             at::IntArrayRef, std::optional<at::ScalarType>)>();
     const std::vector<int64_t> dim{3}, out_size{W};
     at::Tensor spec = c2r.call(yw_.to(at::kFloat).contiguous(), dim, out_size, 1.0, {}, x_.scalar_type());
-    return fno_pointwise_cuda(spec, x_, wc_.reshape({Cout, Cin}), bias, gelu);
+    return fno_pointwise_run(spec, x_, wc_.reshape({Cout, Cin}), bias, gelu, y);
   }
   const bool wide = route.kind == FnoTailKind::Wide;  // Cin or Cout > 32: fno_c2r_pw_wide.hip, 64-pixel chunks
   TORCH_CHECK(B * Cin * H * W < (int64_t(1) << 31) && B * Cout * H * W < (int64_t(1) << 31),
@@ -411,7 +472,6 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
   if (reinterpret_cast<uintptr_t>(yw.data_ptr()) % 16 != 0) yw = yw.clone();
   at::Tensor wc = wc_.to(at::kFloat).reshape({Cout, Cin}).contiguous();
   at::Tensor bf = f32_or_undef(bias);
-  at::Tensor y = at::empty({B, Cout, H, W}, x.options());
   auto tabs = get_dft_gemm_tables(is_bf && !wide ? DftTable::C2R_BF16 : DftTable::C2R_F32, static_cast<int>(W),
                                   static_cast<int>(m), x.device());
   FnoC2RPwLaunch p;
@@ -432,12 +492,32 @@ at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw_, const at::Tensor& x_, const at
   p.gelu = gelu;
   if (wide) launch_fno_c2r_pw_wide(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
   else launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+}
+
+at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
+                           const c10::optional<at::Tensor>& bias, bool gelu) {
+  const c10::DeviceGuard guard(x.device());
+  check_fno_c2r(yw, x, wc);
+  at::Tensor y = at::empty(fno_c2r_pw_out_shape(yw, x), x.options());
+  fno_c2r_pw_run(yw, x, wc, bias, gelu, y);
   return checked(y, "fno_c2r_pw");
+}
+
+// out: 16-byte aligned, the store width of both fused kernels in either dtype
+at::Tensor& fno_c2r_pw_out_cuda(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
+                                const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
+  const c10::DeviceGuard guard(x.device());
+  check_fno_c2r(yw, x, wc);
+  check_out(out, fno_c2r_pw_out_shape(yw, x), x, "fno_c2r_pw_out");
+  check_out_aligned(out, 16, "fno_c2r_pw_out");
+  fno_c2r_pw_run(yw, x, wc, bias, gelu, out);
+  checked(out, "fno_c2r_pw_out");
+  return out;
 }
 
 // Which route fno_c2r_pw (cin >= 1) or fno_c2r (cin = 0) takes for a shape -- host only, no device (the
 // companion of fno_pointwise_info): "fused ks=2 co=2 chunk=128", "wide slabs=2 otiles=4 groups=1 ks=2 chunk=64
-// x3=0" or "split"
+// x3=0 wl=1" (wl: the 1x1 weights staged in LDS, the kernel's WL instances) or "split"
 std::string fno_c2r_pw_info(int64_t cin, int64_t cout, int64_t m, int64_t W, bool bf16) {
   TORCH_CHECK(cin >= 0 && cin < (1 << 20) && cout >= 1 && cout < (1 << 20) && m >= 1 && W >= 1 &&
                   W < (int64_t(1) << 31) && m < (int64_t(1) << 31),
@@ -449,13 +529,18 @@ std::string fno_c2r_pw_info(int64_t cin, int64_t cout, int64_t m, int64_t W, boo
   if (r.kind == FnoTailKind::Wide)
     return "wide slabs=" + std::to_string(r.slabs) + " otiles=" + std::to_string(r.otiles) +
            " groups=" + std::to_string(r.groups) + " ks=" + std::to_string(r.ks) + " chunk=" + std::to_string(r.chunk) +
-           " x3=" + std::to_string(r.x3 ? 1 : 0);
+           " x3=" + std::to_string(r.x3 ? 1 : 0) + " wl=" + std::to_string(r.wl ? 1 : 0);
   return "split";
 }
 
 at::Tensor fno_c2r_pw_meta(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
                            const c10::optional<at::Tensor>&, bool) {
   return at::empty({x.size(0), yw.size(1), x.size(2), x.size(3)}, x.options());
+}
+
+at::Tensor& fno_c2r_pw_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                                const c10::optional<at::Tensor>&, bool, at::Tensor& out) {
+  return out;
 }
 
 // ------------------------------------------------------------------ SpectralConv2d tail (C2R-W only)
@@ -530,8 +615,12 @@ at::Tensor fno_c2r_meta(const at::Tensor& yw, int64_t W, std::optional<at::Scala
 // x [..., Q, M, 2] fp32 (complex as trailing re/im), table [M, R, Q] fp32 -> y [..., R, M, 2] fp32:
 //   y[n, r, m, :] = sum_q table[m, r, q] x[n, q, m, :]
 // tri declares the structurally zero part of the table (1: rows r < m, 2: columns q < m), which every
-// implementation treats as zero.  table_split: the table as the kernel reads it, split_bf16(rows=False) of the
+// implementation treats as zero: tri = 1 returns exact zeros in y[.., r < m, m, :], and under tri = 2 every
+// implementation ignores x where q < m -- a NaN or Inf there does not reach the result.  The table itself must be
+// finite everywhere (the kernel multiplies partial tiles of it against staged zeros).
+// table_split: the table as the kernel reads it, split_bf16(rows=False) of the
 // table zero-padded to [M, ceil16(R), ceil32(Q)] -> bf16 [2, M, Rp, Qp]; built per call when absent.
+// legendre_out writes into a given contiguous fp32 tensor of the result's shape.
 void check_legendre(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
   TORCH_CHECK(x.scalar_type() == at::kFloat && table.scalar_type() == at::kFloat,
               "legendre: x and table must be float32 (other precisions of the spherical transforms are not built), got ",
@@ -561,21 +650,30 @@ std::vector<int64_t> legendre_out_shape(const at::Tensor& x, const at::Tensor& t
 at::Tensor legendre_cpu(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
   check_legendre(x, table, ts, tri);
   const int64_t M = table.size(0), R = table.size(1), Q = table.size(2);
-  at::Tensor t = table;
+  at::Tensor t = table, xs = x.reshape({-1, Q, M, 2});
   if (tri != 0) {
     at::Tensor m = at::arange(M, table.options().dtype(at::kLong)).unsqueeze(1);
     at::Tensor k = at::arange(tri == 1 ? R : Q, table.options().dtype(at::kLong)).unsqueeze(0);
-    at::Tensor keep = k.ge(m).to(at::kFloat);  // [M, R] or [M, Q]
-    t = table * (tri == 1 ? keep.unsqueeze(2) : keep.unsqueeze(1));
+    at::Tensor keep = k.ge(m);  // [M, R] or [M, Q]
+    t = at::where(tri == 1 ? keep.unsqueeze(2) : keep.unsqueeze(1), table, at::zeros({}, table.options()));
+    // tri = 2: x[n, q < m, m, :] is not read (a masked table alone would turn a NaN or Inf there into NaN)
+    if (tri == 2) xs = at::where(keep.t().unsqueeze(0).unsqueeze(-1), xs, at::zeros({}, x.options()));
   }
-  at::Tensor y = at::einsum("mrq,nqmc->nrmc", {t, x.reshape({-1, Q, M, 2})});
+  at::Tensor y = at::einsum("mrq,nqmc->nrmc", {t, xs});
   return y.reshape(legendre_out_shape(x, table)).contiguous();
 }
 
-at::Tensor legendre_cuda(const at::Tensor& x_, const at::Tensor& table_, const c10::optional<at::Tensor>& ts_,
-                         int64_t tri) {
-  check_legendre(x_, table_, ts_, tri);
-  const c10::DeviceGuard guard(x_.device());
+at::Tensor& legendre_out_cpu(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
+                             int64_t tri, at::Tensor& out) {
+  check_legendre(x, table, ts, tri);
+  check_out(out, legendre_out_shape(x, table), x, "legendre_out");
+  out.copy_(legendre_cpu(x, table, ts, tri));
+  return out;
+}
+
+// the launch path of legendre and legendre_out: y is the contiguous fp32 result, 8-byte aligned (float2 stores)
+void legendre_run(const at::Tensor& x_, const at::Tensor& table_, const c10::optional<at::Tensor>& ts_, int64_t tri,
+                  const at::Tensor& y) {
   const int64_t M = table_.size(0), R = table_.size(1), Q = table_.size(2);
   const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
   auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
@@ -593,8 +691,7 @@ at::Tensor legendre_cuda(const at::Tensor& x_, const at::Tensor& table_, const c
       launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
                         static_cast<int>(Qp), false, stream);
   }
-  at::Tensor y = at::empty(legendre_out_shape(x, table_), x.options());
-  if (y.numel() == 0) return y;
+  if (y.numel() == 0) return;
   const int64_t N = x.numel() / (Q * M * 2);
   TORCH_CHECK(N < (int64_t(1) << 31) / 16, "legendre: too many fields");
   LegendreLaunch p;
@@ -608,11 +705,35 @@ at::Tensor legendre_cuda(const at::Tensor& x_, const at::Tensor& table_, const c
   p.M = static_cast<int>(M);
   p.tri = static_cast<int>(tri);
   launch_legendre(p, stream);
+}
+
+at::Tensor legendre_cuda(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
+                         int64_t tri) {
+  check_legendre(x, table, ts, tri);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(legendre_out_shape(x, table), x.options());
+  legendre_run(x, table, ts, tri, y);
   return checked(y, "legendre");
+}
+
+at::Tensor& legendre_out_cuda(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
+                              int64_t tri, at::Tensor& out) {
+  check_legendre(x, table, ts, tri);
+  check_out(out, legendre_out_shape(x, table), x, "legendre_out");
+  check_out_aligned(out, 8, "legendre_out");
+  const c10::DeviceGuard guard(x.device());
+  legendre_run(x, table, ts, tri, out);
+  checked(out, "legendre_out");
+  return out;
 }
 
 at::Tensor legendre_meta(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>&, int64_t) {
   return at::empty(legendre_out_shape(x, table), x.options());
+}
+
+at::Tensor& legendre_out_meta(const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&, int64_t,
+                              at::Tensor& out) {
+  return out;
 }
 
 // Which tiling legendre runs for (Q, R, M, real columns = 2 x fields, tri) -- host only, no device (the companion
@@ -692,16 +813,27 @@ at::Tensor sfno_mix_cpu(const at::Tensor& c, const at::Tensor& w, const c10::opt
   return y;
 }
 
-at::Tensor sfno_mix_cuda(const at::Tensor& c_, const at::Tensor& w_, const c10::optional<at::Tensor>& ws_, int64_t tri) {
-  check_sfno_mix(c_, w_, ws_, tri);
-  const c10::DeviceGuard guard(c_.device());
+std::vector<int64_t> sfno_mix_out_shape(const at::Tensor& c, const at::Tensor& w) {
+  return {c.size(0), w.size(1), c.size(2), c.size(3), 2};
+}
+
+at::Tensor& sfno_mix_out_cpu(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri,
+                             at::Tensor& out) {
+  check_sfno_mix(c, w, ws, tri);
+  check_out(out, sfno_mix_out_shape(c, w), c, "sfno_mix_out");
+  out.copy_(sfno_mix_cpu(c, w, ws, tri));
+  return out;
+}
+
+// the launch path of sfno_mix and sfno_mix_out: y is the contiguous fp32 result, 8-byte aligned (float2 stores)
+void sfno_mix_run(const at::Tensor& c_, const at::Tensor& w_, const c10::optional<at::Tensor>& ws_, int64_t tri,
+                  const at::Tensor& y) {
   const int64_t B = c_.size(0), Cin = c_.size(1), L = c_.size(2), M = c_.size(3), Cout = w_.size(1);
   at::Tensor c = c_.contiguous();
   // 8-byte loads of one order's (re, im): a view at an odd float offset gets its own copy
   if (reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 != 0) c = c.clone();
   at::Tensor ws = present(ws_) ? ws_->contiguous() : sfno_mix_split(w_);
-  at::Tensor y = at::empty({B, Cout, L, M, 2}, c.options());
-  if (y.numel() == 0) return y;
+  if (y.numel() == 0) return;
   const int64_t plane = ws.numel() / 2;
   SfnoMixLaunch p;
   p.c = c.data_ptr<float>();
@@ -715,11 +847,34 @@ at::Tensor sfno_mix_cuda(const at::Tensor& c_, const at::Tensor& w_, const c10::
   p.M = static_cast<int>(M);
   p.tri = static_cast<int>(tri);
   launch_sfno_mix(p, c10::hip::getCurrentHIPStream(c.device().index()).stream());
+}
+
+at::Tensor sfno_mix_cuda(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
+  check_sfno_mix(c, w, ws, tri);
+  const c10::DeviceGuard guard(c.device());
+  at::Tensor y = at::empty(sfno_mix_out_shape(c, w), c.options());
+  sfno_mix_run(c, w, ws, tri, y);
   return checked(y, "sfno_mix");
+}
+
+at::Tensor& sfno_mix_out_cuda(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws,
+                              int64_t tri, at::Tensor& out) {
+  check_sfno_mix(c, w, ws, tri);
+  check_out(out, sfno_mix_out_shape(c, w), c, "sfno_mix_out");
+  check_out_aligned(out, 8, "sfno_mix_out");
+  const c10::DeviceGuard guard(c.device());
+  sfno_mix_run(c, w, ws, tri, out);
+  checked(out, "sfno_mix_out");
+  return out;
 }
 
 at::Tensor sfno_mix_meta(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>&, int64_t) {
   return at::empty({c.size(0), w.size(1), c.size(2), c.size(3), 2}, c.options());
+}
+
+at::Tensor& sfno_mix_out_meta(const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&, int64_t,
+                              at::Tensor& out) {
+  return out;
 }
 
 // The tiling sfno_mix runs for (B, Cin, Cout, L, M, tri) -- host only, no device (the companion of legendre_info):
@@ -957,13 +1112,17 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("layer_norm_split(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? pre=None) -> Tensor");
   m.def("fno_mix(Tensor x, Tensor w, int path=0) -> Tensor");
   m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
+  m.def("fno_pointwise_out(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");
   m.def("fno_pointwise_info(int cin, int cout, bool bf16, int P) -> str", &amd_dft::fno_pointwise_info);
   m.def("fno_c2r_pw(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor");
+  m.def("fno_c2r_pw_out(Tensor yw, Tensor x, Tensor wc, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");
   m.def("fno_c2r_pw_info(int cin, int cout, int m, int W, bool bf16) -> str", &amd_dft::fno_c2r_pw_info);
   m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
   m.def("legendre(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor");
+  m.def("legendre_out(Tensor x, Tensor table, Tensor? table_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("legendre_info(int Q, int R, int M, int cols, int tri) -> str", &amd_dft::legendre_info);
   m.def("sfno_mix(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor");
+  m.def("sfno_mix_out(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
   m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri) -> str", &amd_dft::sfno_mix_info);
 }
@@ -978,10 +1137,14 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("layer_norm_split", AMD_DFT_TRACED("amd_dft::layer_norm_split", amd_dft::layer_norm_split_cuda));
   m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cuda));
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cuda));
+  m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cuda));
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cuda));
+  m.impl("fno_c2r_pw_out", AMD_DFT_TRACED("amd_dft::fno_c2r_pw_out", amd_dft::fno_c2r_pw_out_cuda));
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cuda));
   m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cuda));
+  m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cuda));
   m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cuda));
+  m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cuda));
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
@@ -994,10 +1157,14 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("layer_norm_split", AMD_DFT_TRACED("amd_dft::layer_norm_split", amd_dft::layer_norm_split_cpu));
   m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cpu));
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cpu));
+  m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cpu));
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cpu));
+  m.impl("fno_c2r_pw_out", AMD_DFT_TRACED("amd_dft::fno_c2r_pw_out", amd_dft::fno_c2r_pw_out_cpu));
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cpu));
   m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cpu));
+  m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cpu));
   m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cpu));
+  m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cpu));
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
@@ -1010,8 +1177,12 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("layer_norm_split", &amd_dft::layer_norm_split_meta);
   m.impl("fno_mix", &amd_dft::fno_mix_meta);
   m.impl("fno_pointwise", &amd_dft::fno_pointwise_meta);
+  m.impl("fno_pointwise_out", &amd_dft::fno_pointwise_out_meta);
   m.impl("fno_c2r_pw", &amd_dft::fno_c2r_pw_meta);
+  m.impl("fno_c2r_pw_out", &amd_dft::fno_c2r_pw_out_meta);
   m.impl("fno_c2r", &amd_dft::fno_c2r_meta);
   m.impl("legendre", &amd_dft::legendre_meta);
+  m.impl("legendre_out", &amd_dft::legendre_out_meta);
   m.impl("sfno_mix", &amd_dft::sfno_mix_meta);
+  m.impl("sfno_mix_out", &amd_dft::sfno_mix_out_meta);
 }

@@ -58,6 +58,9 @@ void launch_fno_c2r_pw(const FnoC2RPwLaunch& p, void* stream);
 // m <= 64, 2 (m - 1) <= W, W % 8 == 0 and the rotation table (ceil(W / 64) x 16 ceil(m / 16)) fits in LDS
 constexpr int kFnoWideChunk = 64;
 bool fno_c2r_pw_wide_supported(int cin, int cout, int m, int W, bool bf16);
+// whether the kernel stages the whole 1x1 weight matrix in LDS (the WL = true instances) or every wave builds its
+// fragments from global memory per slab (WL = false); false for cin = 0, which has no weights
+bool fno_c2r_pw_wide_weights_in_lds(int cin, int cout, int m, int W, bool bf16);
 void launch_fno_c2r_pw_wide(const FnoC2RPwLaunch& p, void* stream);
 
 // Which kernel(s) a layer tail takes (host only; fno_c2r_pw, fno_c2r and the fno_c2r_pw_info op all answer
@@ -73,6 +76,7 @@ struct FnoTailRoute {
   int otiles;  // wide: ceil(cout / 16) output tiles
   int groups;  // wide: ceil(otiles / 4) accumulator groups
   bool x3;     // wide: fp32 I/O, 3-product bf16 split
+  bool wl;     // wide: the 1x1 weights are staged in LDS once per workgroup
 };
 inline FnoTailRoute fno_c2r_pw_route(int cin, int cout, int m, int W, bool bf16) {
   FnoTailRoute r{};
@@ -95,6 +99,7 @@ inline FnoTailRoute fno_c2r_pw_route(int cin, int cout, int m, int W, bool bf16)
     r.otiles = (cout + 15) / 16;
     r.groups = (r.otiles + 3) / 4;
     r.x3 = !bf16;
+    r.wl = fno_c2r_pw_wide_weights_in_lds(cin, cout, m, W, bf16);
   }
   return r;
 }

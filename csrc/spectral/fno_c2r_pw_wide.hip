@@ -479,7 +479,7 @@ void launch_i(const FnoC2RPwLaunch& p, const WideGeo& g, hipStream_t st) {
 template <bool BF>
 void launch_bf(const FnoC2RPwLaunch& p, const WideGeo& g, hipStream_t st) {
   if (p.x == nullptr) return launch_i<BF, false, false, false>(p, g, st);
-  const bool wl = g.lds_base + g.lds_w <= kWideLdsHalfCu;
+  const bool wl = fno_c2r_pw_wide_weights_in_lds(p.Cin, p.Cout, p.m, p.W, BF);
   if (p.gelu) {
     if (wl) launch_i<BF, true, true, true>(p, g, st);
     else launch_i<BF, true, true, false>(p, g, st);
@@ -495,6 +495,12 @@ bool fno_c2r_pw_wide_supported(int cin, int cout, int m, int W, bool bf16) {
   (void)bf16;  // both dtypes take 64-pixel chunks
   if (!(cin >= 0 && cout >= 1 && m >= 1 && m <= 64 && 2 * (m - 1) <= W && W % 8 == 0)) return false;
   return static_cast<int64_t>((W + kCH - 1) / kCH) * 16 * ((m + 15) / 16) <= kFnoRotMax;
+}
+
+bool fno_c2r_pw_wide_weights_in_lds(int cin, int cout, int m, int W, bool bf16) {
+  if (cin < 1) return false;
+  const WideGeo g = wide_geo(cin, cout, m, W, bf16);
+  return g.lds_base + g.lds_w <= kWideLdsHalfCu;
 }
 
 void launch_fno_c2r_pw_wide(const FnoC2RPwLaunch& p, void* stream) {

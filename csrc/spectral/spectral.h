@@ -245,6 +245,18 @@ inline SfnoMixRoute sfno_mix_route(int64_t B, int64_t Cin, int64_t Cout, int64_t
 }
 void launch_sfno_mix(const SfnoMixLaunch& p, void* stream);
 
+// ---- test support (lds_poison.hip): NaN-fill every CU's LDS, and measure what a following kernel finds there
+constexpr uint32_t kLdsPoisonWord = 0x7fc07fc0u;  // a quiet NaN as fp32 and as two bf16
+constexpr int kLdsPoisonRounds = 4;                // workgroups per CU
+struct LdsPoisonGeo {
+  int64_t wgs;      // workgroups launched (CUs x kLdsPoisonRounds)
+  int threads;      // threads per workgroup
+  int64_t words;    // 32-bit LDS words per workgroup: the largest dynamic LDS the device allows
+};
+LdsPoisonGeo lds_poison_geometry();                  // of the current device
+void launch_lds_poison(void* stream);                // writes no global memory
+void launch_lds_probe(int32_t* hits, void* stream);  // hits [wgs * threads]: matching words seen by each thread
+
 // ---- LayerNorm over the last dim (bf16/fp32 I/O, fp32 statistics)
 struct LayerNormLaunch {
   const void* x;

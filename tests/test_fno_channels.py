@@ -47,6 +47,29 @@ def test_fno_pointwise_info_routes(bf16):
         info(0, 4, bf16, 16)
 
 
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_fno_pointwise_cpu_out_variant(dt):
+    """A NaN-filled ``out`` equals the allocating op's result bit for bit; a wrong-shape, wrong-dtype or
+    non-contiguous ``out`` is an error, never a copy."""
+    op, op_out = torch.ops.amd_dft.fno_pointwise, torch.ops.amd_dft.fno_pointwise_out
+    g = torch.Generator().manual_seed(36)
+    x, s = torch.randn(2, 12, 5, 7, generator=g).to(dt), torch.randn(2, 9, 5, 7, generator=g).to(dt)
+    w, b = torch.randn(9, 12, generator=g), torch.randn(9, generator=g)
+    for spec, bias, gelu in ((s, b, True), (None, None, False)):
+        ref = op(spec, x, w, bias, gelu)
+        out = torch.full(ref.shape, float("nan"), dtype=dt)
+        assert op_out(spec, x, w, bias, gelu, out) is out
+        assert torch.equal(out, ref)
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(s, x, w, b, True, torch.empty(2, 12, 5, 7, dtype=dt))
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(s, x, w, b, True, torch.empty(2, 9, 5, 14, dtype=dt)[..., ::2])
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(s, x, w, b, True, torch.empty(2, 9, 5, 7, dtype=torch.float64))
+    m = op_out(None, x.to("meta"), w.to("meta"), None, True, torch.empty(2, 9, 5, 7, dtype=dt, device="meta"))
+    assert m.device.type == "meta" and m.shape == (2, 9, 5, 7) and m.dtype == dt
+
+
 def _any_channel_cfg(img, width=40):
     return FNOConfig(img_size=img, in_chans=3, out_chans=1, width=width, modes1=4, modes2=5, n_layers=2,
                      proj_hidden=48)

@@ -52,6 +52,40 @@ def test_fno_c2r_pw_info_routes(bf16):
             info(*bad, bf16)
 
 
+def test_fno_c2r_pw_info_reports_where_the_weights_live():
+    """``wl``: the wide kernel stages the 1x1 weights in LDS (its WL instances) while they fit beside the tables."""
+    info = torch.ops.amd_dft.fno_c2r_pw_info
+    for bf16 in (False, True):
+        assert _fields(info(64, 64, 16, 128, bf16))["wl"] == 1
+        assert _fields(info(300, 65, 5, 72, bf16))["wl"] == (1 if bf16 else 0)  # one plane of fragments fits
+        assert _fields(info(521, 65, 8, 64, bf16))["wl"] == 0
+        assert _fields(info(0, 65, 5, 72, bf16))["wl"] == 0  # fno_c2r has no weights
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_fno_c2r_pw_cpu_out_variant(dt):
+    """A NaN-filled ``out`` equals the allocating op's result bit for bit; a wrong-shape, wrong-dtype or
+    non-contiguous ``out`` is an error, never a copy."""
+    op, op_out = torch.ops.amd_dft.fno_c2r_pw, torch.ops.amd_dft.fno_c2r_pw_out
+    g = torch.Generator().manual_seed(44)
+    yw = torch.randn(2, 9, 3, 5, 2, generator=g)
+    x = torch.randn(2, 12, 3, 16, generator=g).to(dt)
+    wc, b = torch.randn(9, 12, generator=g), torch.randn(9, generator=g)
+    for bias, gelu in ((b, True), (None, False)):
+        ref = op(yw, x, wc, bias, gelu)
+        out = torch.full(ref.shape, float("nan"), dtype=dt)
+        assert op_out(yw, x, wc, bias, gelu, out) is out
+        assert torch.equal(out, ref)
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(yw, x, wc, b, True, torch.empty(2, 12, 3, 16, dtype=dt))
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(yw, x, wc, b, True, torch.empty(2, 9, 3, 32, dtype=dt)[..., ::2])
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(yw, x, wc, b, True, torch.empty(2, 9, 3, 16, dtype=torch.float64))
+    m = op_out(yw.to("meta"), x.to("meta"), wc.to("meta"), None, True, torch.empty(2, 9, 3, 16, dtype=dt, device="meta"))
+    assert m.device.type == "meta" and m.shape == (2, 9, 3, 16) and m.dtype == dt
+
+
 # ------------------------------------------------------------------------------------------ GPU tier
 def _chan_err(out, ref):
     """max over output channels of the channel's rel-L2 against the reference."""

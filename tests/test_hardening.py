@@ -26,7 +26,9 @@ def _one_node_model(op_type, domain, attrs=()):
     return m.SerializeToString()
 
 
-@pytest.mark.parametrize("name", ["wrap_host_ptr", "wrap_device_ptr", "plan_cache_clear", "fallback_reset"])
+@pytest.mark.parametrize("name", ["wrap_host_ptr", "wrap_device_ptr", "plan_cache_clear", "fallback_reset",
+                                  "lds_poison", "lds_probe", "lds_poison_info", "afno_mlp_out", "legendre_out",
+                                  "sfno_mix_out", "fno_pointwise_out", "fno_c2r_pw_out"])
 def test_onnx_runtime_helpers_not_dispatchable(name):
     with pytest.raises(NotImplementedError, match="not an exportable tensor operator"):
         OnnxGraph(_one_node_model(name, "com.amd.dft", (("ptr", 4096),)), device="cpu")

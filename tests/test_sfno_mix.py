@@ -43,6 +43,38 @@ def test_sfno_mix_cpu_vs_fp64(case, tri):
         assert rel_l2(y, _mix_ref(c, w, 1)) > 1e-2  # the orders above l were used
 
 
+@pytest.mark.parametrize("poison", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_sfno_mix_cpu_ignores_c_where_l_below_m(poison):
+    """``tri = 1``: c[b, i, l, m > l] is not read -- a NaN or Inf there gives the product of the zeroed spectrum, with
+    exact 0.0 where l < m."""
+    B, Cin, Cout, L, M = 2, 5, 7, 12, 9
+    g = torch.Generator().manual_seed(7)
+    c, w = torch.randn(B, Cin, L, M, 2, generator=g), torch.randn(Cin, Cout, L, 2, generator=g)
+    y = SP.sfno_mix(torch.where(_below(B, Cin, L, M), poison, c), w, tri=1)
+    assert torch.isfinite(y).all()
+    assert rel_l2(y, _mix_ref(c, w, 1)) < 1e-6
+    assert torch.all(y[_below(B, Cout, L, M)] == 0.0)
+
+
+def test_sfno_mix_cpu_out_variant():
+    """A NaN-filled ``out`` equals the allocating op's result bit for bit; a wrong-shape or non-contiguous ``out``
+    is an error, never a copy."""
+    op, op_out = torch.ops.amd_dft.sfno_mix, torch.ops.amd_dft.sfno_mix_out
+    g = torch.Generator().manual_seed(8)
+    c, w = torch.randn(2, 5, 12, 9, 2, generator=g), torch.randn(5, 7, 12, 2, generator=g)
+    for tri in (0, 1):
+        ref = op(c, w, None, tri)
+        out = torch.full_like(ref, float("nan"))
+        assert op_out(c, w, None, tri, out) is out
+        assert torch.equal(out, ref)
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(c, w, None, 0, torch.empty(2, 5, 12, 9, 2))
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(c, w, None, 0, torch.empty(2, 7, 12, 9, 4)[..., ::2])
+    m = op_out(c.to("meta"), w.to("meta"), None, 0, torch.empty(2, 7, 12, 9, 2, device="meta"))
+    assert m.device.type == "meta" and m.shape == (2, 7, 12, 9, 2)
+
+
 def test_sfno_mix_meta():
     c = torch.empty(3, 5, 12, 9, 2, device="meta")
     w = torch.empty(5, 7, 12, 2, device="meta")

@@ -135,6 +135,43 @@ def test_legendre_cpu_vs_fp64(tri):
     assert rel_l2(torch.ops.amd_dft.legendre(x, table, None, tri), ref) < 1e-6
 
 
+@pytest.mark.parametrize("poison", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_legendre_cpu_ignores_x_where_tri2_declares_zero(poison):
+    """``tri = 2``: x[n, q < m, m] is not read -- a NaN or Inf there gives the product of x with that part zeroed
+    (a masked table alone would give 0 * NaN = NaN), as the GPU kernel, which stages that part as zero."""
+    g = torch.Generator().manual_seed(5)
+    N, Q, R, M = 3, 21, 13, 9
+    x = torch.randn(N, Q, M, 2, generator=g)
+    table = torch.randn(M, R, Q, generator=g) / Q ** 0.5
+    below = (torch.arange(Q)[:, None] < torch.arange(M)[None, :])[None, :, :, None].expand(N, Q, M, 2)
+    ref = torch.einsum("mrq,nqmc->nrmc", table.double(), torch.where(below, 0.0, x).double())
+    out = torch.ops.amd_dft.legendre(torch.where(below, poison, x), table, None, 2)
+    assert torch.isfinite(out).all()
+    assert rel_l2(out, ref) < 1e-6
+
+
+def test_legendre_cpu_out_variant():
+    """A NaN-filled ``out`` equals the allocating op's result bit for bit; a wrong-shape or non-contiguous ``out``
+    is an error, never a copy."""
+    op, op_out = torch.ops.amd_dft.legendre, torch.ops.amd_dft.legendre_out
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(2, 3, 21, 9, 2, generator=g)
+    table = torch.randn(9, 13, 21, generator=g)
+    for tri in (0, 1, 2):
+        ref = op(x, table, None, tri)
+        out = torch.full_like(ref, float("nan"))
+        assert op_out(x, table, None, tri, out) is out
+        assert torch.equal(out, ref)
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(x, table, None, 0, torch.empty(2, 3, 13, 8, 2))
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(x, table, None, 0, torch.empty(2, 3, 13, 9, 4)[..., ::2])
+    with pytest.raises(RuntimeError, match="out must be"):
+        op_out(x, table, None, 0, torch.empty(2, 3, 13, 9, 2, dtype=torch.float64))
+    m = op_out(x.to("meta"), table.to("meta"), None, 0, torch.empty(2, 3, 13, 9, 2, device="meta"))
+    assert m.device.type == "meta" and m.shape == (2, 3, 13, 9, 2)
+
+
 def test_legendre_meta_shapes():
     x = torch.empty(2, 5, 45, 13, 2, device="meta")
     t = torch.empty(13, 23, 45, device="meta")

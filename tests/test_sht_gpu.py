@@ -18,10 +18,12 @@ TOL = 1e-5
 
 # (N, Q, R, M): everything ragged, one slab pair | several column tiles, slabs and row tiles | exactly aligned |
 # more than 64 modes, R above Q | ragged last mode group.  All of these run on the 4-mode x 8-field tile (few
-# workgroups); the last two fill the grid and reach the 4-mode x 16-field and the 8-mode x 16-field tiles.
+# workgroups); the next two fill the grid and reach the 4-mode x 16-field and the 8-mode x 16-field tiles; the last
+# one (7 fields = 14 columns, 32 mode groups x 8 row groups = 256 workgroups, ragged in every dimension) reaches the
+# 8-mode x 8-field tile.
 CASES = [(3, 45, 23, 13), (40, 90, 90, 46), (2, 32, 16, 8), (1, 17, 70, 70), (5, 64, 64, 9),
-         (128, 40, 100, 80), (128, 40, 200, 80)]
-TILES = {(128, 40, 100, 80): (4, 2), (128, 40, 200, 80): (8, 2)}
+         (128, 40, 100, 80), (128, 40, 200, 80), (7, 33, 500, 252)]
+TILES = {(3, 45, 23, 13): (4, 1), (128, 40, 100, 80): (4, 2), (128, 40, 200, 80): (8, 2), (7, 33, 500, 252): (8, 1)}
 
 
 def _field_err(out, ref, lead):
