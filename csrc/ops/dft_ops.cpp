@@ -94,6 +94,14 @@ at::Tensor pair_aligned(const at::Tensor& x) {
   return x.clone(at::MemoryFormat::Contiguous);
 }
 
+// The LayerNorm-fused W-transforms (afno_wfft.hip) move 8 or 16 bytes per lane and DMA 16-byte pieces of the
+// residual tile and its statistics into LDS: every tensor they read starts on a 16-byte boundary (a pointer
+// test; allocations are, a contiguous view at an odd element offset is not and is copied).
+at::Tensor vec_aligned(const at::Tensor& x) {
+  if (x.numel() == 0 || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0) return x;
+  return x.clone(at::MemoryFormat::Contiguous);
+}
+
 int64_t lds_limit() {
   static const int64_t lim = max_lds_length();
   return lim;
@@ -724,6 +732,13 @@ bool afno_w_enabled() {
   return on;
 }
 
+// Whether a call of the four LayerNorm-fused ops whose dtypes an instance of afno_wfft.hip covers runs there
+// (the ops and afno_w_info both ask here): the specialised shape, and O = the number of [L, C] planes
+bool afno_w_takes(int64_t L, int64_t C, int64_t KM, int64_t O) {
+  return afno_w_enabled() && L < (int64_t(1) << 31) && C < (int64_t(1) << 31) && KM < (int64_t(1) << 31) &&
+         afno_w_supported(static_cast<int>(L), static_cast<int>(C), static_cast<int>(KM)) && O < (int64_t(1) << 31);
+}
+
 at::Tensor r2c_cpu(const at::Tensor& x, at::IntArrayRef dim, double scale, at::IntArrayRef keep,
                    std::optional<at::ScalarType> out_dtype);
 at::Tensor c2r_cpu(const at::Tensor& x, at::IntArrayRef dim, at::IntArrayRef out_size, double scale,
@@ -735,7 +750,7 @@ at::Tensor r2c_ln_cuda(const at::Tensor& x_, int64_t dim, double scale, int64_t 
   const c10::DeviceGuard guard(x_.device());
   check_ln_args(x_, dim, stats_, g_, b_, pre_, "r2c_ln");
   const int64_t axis = x_.dim() - 2;
-  at::Tensor x = x_.contiguous();
+  at::Tensor x = vec_aligned(x_.contiguous());
   const at::ScalarType odt = out_dtype.value_or(x.scalar_type());
   to_dtype(x.scalar_type());
   to_dtype(odt);
@@ -746,17 +761,15 @@ at::Tensor r2c_ln_cuda(const at::Tensor& x_, int64_t dim, double scale, int64_t 
   nxt[axis] = s.lo;
   at::Tensor out = alloc_complex(nxt, x.options(), odt);
   if (x.numel() == 0) return out.zero_();
-  at::Tensor stats = stats_.to(at::kFloat).contiguous(), g = g_.to(at::kFloat).contiguous(),
-             b = b_.to(at::kFloat).contiguous();
+  at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
+             b = vec_aligned(b_.to(at::kFloat).contiguous());
   at::Tensor pre;
-  if (pre_.has_value()) pre = pre_->to(at::kFloat).contiguous();
+  if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
   LnIO ln{stats.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(),
           pre_.has_value() ? pre.data_ptr<float>() : nullptr};
   const int64_t C = x.size(-1);
   const bool w_f32 = x.scalar_type() == at::kFloat && odt == at::kFloat;
-  if (((x.scalar_type() == at::kBFloat16 && odt == at::kBFloat16) || w_f32) && afno_w_enabled() &&
-      afno_w_supported(static_cast<int>(s.n), static_cast<int>(C), static_cast<int>(s.lo)) &&
-      x.numel() / (s.n * C) < (int64_t(1) << 31)) {
+  if (((x.scalar_type() == at::kBFloat16 && odt == at::kBFloat16) || w_f32) && afno_w_takes(s.n, C, s.lo, x.numel() / (s.n * C))) {
     AfnoWLaunch p;  // 16-byte-lane two-pass kernel (afno_wfft.hip)
     p.x = x.data_ptr();
     p.stats = ln.stats;
@@ -810,21 +823,20 @@ at::Tensor c2r_ln_add_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double 
   const int64_t axis = x_.dim() - 2;
   TORCH_CHECK(X_.dim() == x_.dim() + 1 && X_.size(-1) == 2 && x_.size(axis) == n, "amd_dft.c2r_ln_add: shape mismatch "
               "(X must be [..., km, C, 2] with the leading dims and C of x)");
-  at::Tensor X = X_.contiguous(), x = x_.contiguous();
+  at::Tensor X = vec_aligned(X_.contiguous()), x = vec_aligned(x_.contiguous());
   const int64_t km = X.size(axis);
   const std::vector<int64_t> dv{axis}, nv{n}, kv{km, 0};
-  at::Tensor stats = stats_.to(at::kFloat).contiguous(), g = g_.to(at::kFloat).contiguous(),
-             b = b_.to(at::kFloat).contiguous();
+  at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
+             b = vec_aligned(b_.to(at::kFloat).contiguous());
   at::Tensor pre;
-  if (pre_.has_value()) pre = pre_->to(at::kFloat).contiguous();
+  if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
   TORCH_CHECK(X.sizes().slice(0, axis) == x.sizes().slice(0, axis) && X.size(axis + 1) == x.size(-1) &&
                   X.size(axis) <= n / 2 + 1,
               "amd_dft.c2r_ln_add: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
   const bool w_f32 = X.scalar_type() == at::kFloat && x.scalar_type() == at::kFloat;
   if (w_f32 && X.numel() > 0) {
     const int64_t C = x.size(-1);
-    if (afno_w_enabled() && afno_w_supported(static_cast<int>(n), static_cast<int>(C), static_cast<int>(km)) &&
-        x.numel() / (n * C) < (int64_t(1) << 31)) {
+    if (afno_w_takes(n, C, km, x.numel() / (n * C))) {
       at::Tensor out = at::empty_like(x);
       AfnoWLaunch p;  // fp32 instantiation of the two-pass kernel (afno_wfft.hip)
       p.x = x.data_ptr();
@@ -855,9 +867,7 @@ at::Tensor c2r_ln_add_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double 
     LnIO ln{stats.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(),
             pre_.has_value() ? pre.data_ptr<float>() : nullptr};
     const int64_t C = x.size(-1);
-    if (afno_w_enabled() &&
-        afno_w_supported(static_cast<int>(s.n), static_cast<int>(C), static_cast<int>(km)) &&
-        x.numel() / (s.n * C) < (int64_t(1) << 31)) {
+    if (afno_w_takes(s.n, C, km, x.numel() / (s.n * C))) {
       AfnoWLaunch p;  // 16-byte-lane two-pass kernel (afno_wfft.hip)
       p.x = x.data_ptr();
       p.stats = ln.stats;
@@ -966,14 +976,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_cuda(const at::T
                   X_.sizes().slice(0, axis) == x_.sizes().slice(0, axis) && X_.size(axis + 1) == x_.size(-1) &&
                   X_.size(axis) <= n / 2 + 1,
               "amd_dft.c2r_ln_add_split: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
-  at::Tensor X = X_.contiguous(), x = x_.contiguous();
+  at::Tensor X = vec_aligned(X_.contiguous()), x = vec_aligned(x_.contiguous());
   const int64_t km = X.size(axis), C = x.size(-1);
-  if (X.numel() > 0 && afno_w_enabled() && afno_w_supported(static_cast<int>(n), static_cast<int>(C), static_cast<int>(km)) &&
-      x.numel() / (n * C) < (int64_t(1) << 31)) {
-    at::Tensor stats = stats_.to(at::kFloat).contiguous(), g = g_.to(at::kFloat).contiguous(),
-               b = b_.to(at::kFloat).contiguous();
+  if (X.numel() > 0 && afno_w_takes(n, C, km, x.numel() / (n * C))) {
+    at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
+               b = vec_aligned(b_.to(at::kFloat).contiguous());
     at::Tensor pre;
-    if (pre_.has_value()) pre = pre_->to(at::kFloat).contiguous();
+    if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
     const int64_t M = x.numel() / C;
     // out_mode 1: the fp32 output; 2: instead its bf16 third split term (lo2, [M, C]); 0: neither
     TORCH_CHECK(out_mode >= 0 && out_mode <= 2, "amd_dft.c2r_ln_add_split: out_mode must be 0, 1 or 2");
@@ -1044,14 +1053,13 @@ std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_cuda(const at::Tensor& X_, in
                   X_.sizes().slice(0, axis) == x_.sizes().slice(0, axis) && X_.size(axis + 1) == x_.size(-1) &&
                   X_.size(axis) <= n / 2 + 1,
               "amd_dft.c2r_ln_add_part: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
-  at::Tensor X = X_.contiguous(), x = x_.contiguous();
+  at::Tensor X = vec_aligned(X_.contiguous()), x = vec_aligned(x_.contiguous());
   const int64_t km = X.size(axis), C = x.size(-1);
-  if (X.numel() > 0 && afno_w_enabled() && afno_w_supported(static_cast<int>(n), static_cast<int>(C), static_cast<int>(km)) &&
-      x.numel() / (n * C) < (int64_t(1) << 31)) {
-    at::Tensor stats = stats_.to(at::kFloat).contiguous(), g = g_.to(at::kFloat).contiguous(),
-               b = b_.to(at::kFloat).contiguous();
+  if (X.numel() > 0 && afno_w_takes(n, C, km, x.numel() / (n * C))) {
+    at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
+               b = vec_aligned(b_.to(at::kFloat).contiguous());
     at::Tensor pre;
-    if (pre_.has_value()) pre = pre_->to(at::kFloat).contiguous();
+    if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
     const int64_t M = x.numel() / C;
     at::Tensor out = at::empty_like(x);
     at::Tensor part = at::empty({M, C / 64, 2}, x.options().dtype(at::kFloat));
@@ -1304,6 +1312,66 @@ std::string fft_pass_info(std::string kind_s, at::IntArrayRef shape, int64_t axi
   return os.str();
 }
 
+// Which route an aligned call of a LayerNorm-fused W-transform takes on the device (host only: no device, no
+// allocation), from the functions the ops decide with (afno_w_takes, afno_w_instance, the fixed kernels' selection):
+//   "wfft c2r_bf16_part slabs=3 stage=fp16"                  the two-pass kernels of afno_wfft.hip and the instance
+//   "stockham L=180 TP=15 T=16 cfg=27 pairvec=1"              the fixed Stockham kernels' LayerNorm pass (bf16 only)
+//   "aten <reason>"                                           ATen LayerNorm + the plain transform (counted by
+//                                                             fallback_counts)
+//   "none <reason>"                                           the op raises
+// c2r_ln_add_split / c2r_ln_add_part outside the specialised shape compute their extra outputs with ATen on top of
+// c2r_ln_add: "aten epilogue; c2r_ln_add: <its route>".
+std::string afno_w_info(std::string op, int64_t L, int64_t C, int64_t KM, bool bf16) {
+  const bool r2c = op == "r2c_ln", split = op == "c2r_ln_add_split", part = op == "c2r_ln_add_part";
+  TORCH_CHECK(r2c || split || part || op == "c2r_ln_add",
+              "amd_dft.afno_w_info: op must be r2c_ln, c2r_ln_add, c2r_ln_add_split or c2r_ln_add_part");
+  TORCH_CHECK(L >= 1 && L < (1 << 30) && C >= 1 && C < (1 << 30) && KM >= 1 && KM <= L / 2 + 1,
+              "amd_dft.afno_w_info: needs L, C >= 1 and 1 <= KM <= L / 2 + 1");
+  if (split && bf16) return "none split-pair outputs come with the fp32 residual stream";
+  if (part && !bf16) return "none bf16 spectrum and residual stream (the fp32 block uses c2r_ln_add_split)";
+  if ((split || part) && C % 64 != 0) return "none C must be a multiple of 64";
+  std::ostringstream os;
+  if (afno_w_takes(L, C, KM, 1)) {
+    os << "wfft " << afno_w_instance_name(afno_w_instance(!r2c, !bf16, split, split || part)) << " slabs=" << C / 64
+       << " stage=" << (bf16 ? "fp16" : "fp32");
+    return os.str();
+  }
+  if (split || part) os << "aten epilogue; c2r_ln_add: ";
+  if (!bf16) {
+    os << "aten no LayerNorm-fused fp32 kernel for this shape";
+    return os.str();
+  }
+  if (L <= lds_limit()) {
+    const Kind kind = r2c ? Kind::R2C : Kind::C2R;
+    const std::vector<int64_t> in_shape{1, r2c ? L : KM, C}, out_shape{1, r2c ? KM : L, C};
+    Plan1D plan = make_plan_1d(static_cast<int32_t>(L));
+    PassDesc d;
+    d.kind = kind;
+    apply_plan(d, plan);
+    set_axis_geometry(d, in_shape, out_shape, 1, kind != Kind::R2C, kind != Kind::C2R);
+    d.in_lo = static_cast<int32_t>(r2c ? L : KM);
+    d.in_hi = 0;
+    d.out_lo = static_cast<int32_t>(r2c ? KM : L);
+    d.out_hi = 0;
+    d.inverse = r2c ? 0 : 1;
+    d.tin = d.tout = DType::BF16;
+    FixedLaunchInfo fi;
+    if (choose_tiling(d)) {
+      finalize_vec_flags(d, 2, 2);
+      alignas(16) static const float probe[4] = {0.f, 0.f, 0.f, 0.f};  // non-null, aligned stand-ins: only tested, never read
+      d.ln_stats = d.ln_gamma = d.ln_beta = probe;
+      if (!r2c) d.add1 = probe;
+      if (describe_fft_fixed(d, fi)) {
+        const FixedCfg& c = fixed_configs()[fi.cfg];
+        os << "stockham L=" << c.L << " TP=" << c.TP << " T=" << c.T << " cfg=" << fi.cfg << " pairvec=" << (fi.pairvec ? 1 : 0);
+        return os.str();
+      }
+    }
+  }
+  os << "aten no LayerNorm-fused kernel for this shape";
+  return os.str();
+}
+
 // The compiled fixed configurations, one "L cols TP T r,r,..." entry per table index, ';'-separated.
 std::string fft_fixed_configs() {
   std::ostringstream os;
@@ -1373,6 +1441,7 @@ TORCH_LIBRARY(amd_dft, m) {
   m.def("plan_info(int n) -> str", &amd_dft::plan_info);
   m.def("fft_pass_info(str kind, int[] shape, int axis, int n=-1, bool bf16_in=False, bool bf16_out=False) -> str",
         &amd_dft::fft_pass_info);
+  m.def("afno_w_info(str op, int L, int C, int KM, bool bf16) -> str", &amd_dft::afno_w_info);
   m.def("fft_fixed_configs() -> str", &amd_dft::fft_fixed_configs);
   m.def("fft_fixed_sweep(str kind, int L, bool cols, int I_max, int O_max) -> int[]", &amd_dft::fft_fixed_sweep);
   m.def("plugin_registry() -> str", &amd_dft::plugin_registry);

@@ -19,6 +19,27 @@
 //  * fp32 instantiation (F32, the fp32 FourCastNet path): fp32 residual stream and spectrum,
 //    fp32 LDS staging, addends loaded to registers (the bf16 LDS image of the x tile would not
 //    fit beside an fp32 staging buffer at 3 workgroups per CU).
+//
+// fp16 staging range of the bf16 instantiations (the fp32 ones stage in fp32 and have no such range).
+// The LDS transpose between the passes holds _Float16 (max 65504, normals from 2^-14, subnormal
+// spacing 2^-24); everything else is fp32 registers.
+//  * R2C stages twice: the 12-point sums of pass 0, and the whole unscaled 180-point sums Z[k] of a
+//    packed pair z = h_c + i h_{c+1} (h = the LayerNorm output; `scale` is applied after the last
+//    LDS read).  A component of Z[k] is sum_w h_c cos + h_{c+1} sin <= 180 sqrt(2) max|h|.
+//    Upper bound: max|LN output| <= 65504 / (180 sqrt 2) = 257 keeps every staged value finite
+//    (a channel that is constant along W reaches 180 |h| in mode 0 and overflows from 364).
+//  * C2R stages once: the 12-point sums of the Hermitian-assembled packed spectrum
+//    Z[n] = conj(X_c[n] + i X_{c+1}[n]) (before `scale`).  At KM = 46 at most 6 of a sum's 12 inputs
+//    are independent non-zero modes (the sums with n2 = 0 hold mode 0 and 3 mirrored pairs and stay
+//    below that), each with components up to 2a and modulus up to 2 sqrt(2) a for a = max|spectrum
+//    component|.  Upper bound: max|spectrum component| <= 65504 / (12 sqrt 2) = 3860.
+//  * Lower end: a staged value v below 2^-14 is an fp16 subnormal, resolved to 2^-24; that spacing
+//    exceeds half a bf16 ulp of v (2^-8 of its binade) once |v| < 2^-16 = 1.5e-5.  A lone non-zero
+//    input (one token of a channel, one mode) is staged by itself, times a twiddle, so the amplitude
+//    below which the staging rather than the bf16 output limits the result is 2^-16 for both
+//    |LN output| (R2C) and |spectrum component| (C2R); dense signals sum to more and reach it later.
+//    Below 2^-25 a staged value flushes to zero.
+// tests/test_afno_w.py runs both ends (a quarter of the upper bounds, four times the lower amplitude).
 // Reference: the AFNO filter runs rfft2/irfft2 on the whole [B, C, H, W] tensor after a
 // separate LayerNorm kernel (FourCastNet AFNO2D; this repo's SURVEY.md §2.5 K5/K1e).
 #include <hip/hip_runtime.h>
@@ -583,11 +604,35 @@ void check_launch(const AfnoWLaunch& p, const char* what) {
 
 bool afno_w_supported(int L, int C, int KM) { return L == kL && C % kSlab == 0 && KM == 46; }
 
+AfnoWInstance afno_w_instance(bool c2r, bool f32, bool pairs, bool part) {
+  if (!c2r) {
+    if (pairs || part) throw std::runtime_error("amd_dft: afno_w_r2c_ln: no split-pair or statistics outputs");
+    return f32 ? AfnoWInstance::R2cF32 : AfnoWInstance::R2cBf16;
+  }
+  if (f32 ? pairs != part : pairs)
+    throw std::runtime_error("amd_dft: afno_w_c2r_ln: fp32: split pairs and partial statistics come together; bf16: partials only");
+  if (pairs) return AfnoWInstance::C2rF32Split;
+  if (part) return AfnoWInstance::C2rBf16Part;
+  return f32 ? AfnoWInstance::C2rF32 : AfnoWInstance::C2rBf16;
+}
+
+const char* afno_w_instance_name(AfnoWInstance i) {
+  switch (i) {
+    case AfnoWInstance::R2cBf16: return "r2c_bf16";
+    case AfnoWInstance::R2cF32: return "r2c_f32";
+    case AfnoWInstance::C2rBf16: return "c2r_bf16";
+    case AfnoWInstance::C2rF32: return "c2r_f32";
+    case AfnoWInstance::C2rF32Split: return "c2r_f32_split";
+    case AfnoWInstance::C2rBf16Part: return "c2r_bf16_part";
+  }
+  return "?";
+}
+
 void launch_afno_w_r2c_ln(const AfnoWLaunch& p, void* stream) {
   check_launch(p, "afno_w_r2c_ln");
   const WArgs a = make_args(p);
   const dim3 grid(static_cast<uint32_t>(static_cast<int64_t>(p.O) * a.nslab));
-  if (p.f32) hipLaunchKernelGGL((afno_w_r2c_ln_kernel<46, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  if (afno_w_instance(false, p.f32 != 0, p.pairs != nullptr, p.part != nullptr) == AfnoWInstance::R2cF32) hipLaunchKernelGGL((afno_w_r2c_ln_kernel<46, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   else hipLaunchKernelGGL((afno_w_r2c_ln_kernel<46, false>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: afno_w_r2c_ln launch: ") + hipGetErrorString(e));
@@ -597,11 +642,10 @@ void launch_afno_w_c2r_ln(const AfnoWLaunch& p, void* stream) {
   check_launch(p, "afno_w_c2r_ln");
   const WArgs a = make_args(p);
   const dim3 grid(static_cast<uint32_t>(static_cast<int64_t>(p.O) * a.nslab));
-  if (p.f32 ? (p.pairs != nullptr) != (p.part != nullptr) : p.pairs != nullptr)
-    throw std::runtime_error("amd_dft: afno_w_c2r_ln: fp32: split pairs and partial statistics come together; bf16: partials only");
-  if (p.pairs) hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, true, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-  else if (p.part) hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, false, false, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-  else if (p.f32) hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  const AfnoWInstance inst = afno_w_instance(true, p.f32 != 0, p.pairs != nullptr, p.part != nullptr);
+  if (inst == AfnoWInstance::C2rF32Split) hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, true, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  else if (inst == AfnoWInstance::C2rBf16Part) hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, false, false, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  else if (inst == AfnoWInstance::C2rF32) hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, true>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   else hipLaunchKernelGGL((afno_w_c2r_ln_kernel<46, false>), grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: afno_w_c2r_ln launch: ") + hipGetErrorString(e));

@@ -481,8 +481,9 @@ __global__ void __launch_bounds__(256) split_bf16_kernel(const float* __restrict
 // mean = avg mean_c, M2 = sum M2_c + W sum (mean_c - mean)^2): the statistics the fp32 fc2 GEMM
 // epilogue leaves for the next block's LayerNorm (csrc/nn/gemm.hip, STATS)
 // 256 rows per workgroup: the block's partials ([256][nc] float2, contiguous) are staged in LDS
-// with coalesced 16-byte loads, then every thread merges its own row (Chan: M2 = sum M2_c +
-// width * sum (mean_c - mean)^2).  shift (or nullptr): [rows] float2 whose .x is subtracted from the
+// with coalesced 16-byte loads (any chunk count 1..64: an odd rows x chunks product leaves one float2,
+// copied on its own; even counts never take that step), then every thread merges its own row (Chan:
+// M2 = sum M2_c + width * sum (mean_c - mean)^2).  shift (or nullptr): [rows] float2 whose .x is subtracted from the
 // mean -- the statistics of a split-pair operand that was written relative to that offset
 // (c2r_ln_add_split centres its pairs on the input stream's mean, see afno_wfft.hip)
 constexpr int kMergeMaxNc = 64;  // dynamic LDS 2 KB per chunk: <= 128 KB
@@ -492,7 +493,7 @@ __global__ void __launch_bounds__(256) ln_stats_merge_kernel(const float2* __res
   extern __shared__ float4 tile[];  // [256 rows][nc] float2
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * 256;
   const int nrow = static_cast<int>(rows - r0 < 256 ? rows - r0 : 256);
-  const int n4 = nrow * nc / 2;  // nc is even (checked on the host)
+  const int n2 = nrow * nc, n4 = n2 / 2;  // odd nrow * nc: the last float2 is copied on its own below
   const float4* src = reinterpret_cast<const float4*>(part + r0 * nc);
   // 8 loads in flight per thread before the first store (clamped, unconditional): the plain copy
   // loop waited one memory round trip per iteration (6 for 12 chunks)
@@ -506,6 +507,7 @@ __global__ void __launch_bounds__(256) ln_stats_merge_kernel(const float2* __res
       if (i < n4) tile[i] = v[q];
     }
   }
+  if ((n2 & 1) && threadIdx.x == 0) reinterpret_cast<float2*>(tile)[n2 - 1] = part[r0 * nc + n2 - 1];
   __syncthreads();
   if (static_cast<int>(threadIdx.x) >= nrow) return;
   const float2* pp = reinterpret_cast<const float2*>(tile) + threadIdx.x * nc;
@@ -525,8 +527,8 @@ __global__ void __launch_bounds__(256) ln_stats_merge_kernel(const float2* __res
 void launch_ln_stats_merge(const float* part, float* stats, int64_t rows, int nc, int width, float eps, void* stream,
                            const float* shift) {
   if (rows <= 0) return;
-  if (nc <= 0 || nc % 2 || nc > kMergeMaxNc || width <= 0)
-    throw std::runtime_error("amd_dft: ln_stats_merge: needs an even chunk count <= 64");
+  if (nc <= 0 || nc > kMergeMaxNc || width <= 0)
+    throw std::runtime_error("amd_dft: ln_stats_merge: needs a chunk count in 1..64");
   const dim3 grid(static_cast<uint32_t>((rows + 255) / 256));
   const int lds = 256 * nc * 8;
   if (lds > 64 * 1024) {  // above the default dynamic-LDS limit (per device, like the GEMM's)

@@ -295,6 +295,11 @@ struct AfnoWLaunch {
   uint16_t* lo2 = nullptr;
 };
 bool afno_w_supported(int L, int C, int KM);
+// The kernel instance a launch runs, from the flags the launchers dispatch on (host only; the launchers and the
+// afno_w_info op both answer from here).  Throws for a combination no instance covers.
+enum class AfnoWInstance { R2cBf16, R2cF32, C2rBf16, C2rF32, C2rF32Split, C2rBf16Part };
+AfnoWInstance afno_w_instance(bool c2r, bool f32, bool pairs, bool part);
+const char* afno_w_instance_name(AfnoWInstance i);
 void launch_afno_w_r2c_ln(const AfnoWLaunch& p, void* stream);
 void launch_afno_w_c2r_ln(const AfnoWLaunch& p, void* stream);
 
