@@ -2,10 +2,17 @@
 ``torch.fft.rfft`` / ``irfft`` (rocFFT) and an ``einsum`` on an fp32 Legendre table -- on the same inputs, hipGraph
 timing, the two routes alternated round by round, median of the rounds.
 
-  python bench/bench_sht.py [--rounds 7] [--out profiles/sht_r10.txt]
+  python bench/bench_sht.py [--rounds 7] [--dtype fp32] [--out profiles/sht_r10.txt]
 
 Every shape is checked first: both routes against each other.  The ``legendre`` rows time the forward table
 (``tri = 1``) on the spectrum the forward transform produces.
+
+``--dtype bf16`` times the bf16 transforms instead, against the fp32 ones of the same op in the same process (the
+same fields rounded to bf16), alternated the same way; the check is the bf16 result against the fp32 one.
+profiles/sfno_bf16_r12.txt is this bench and bench_sfno_mix.py, the second appended to the first:
+
+  python bench/bench_sht.py --dtype bf16 --out profiles/sfno_bf16_r12.txt
+  python bench/bench_sfno_mix.py --dtype bf16 --out profiles/sfno_bf16_r12.txt --append
 """
 from __future__ import annotations
 
@@ -35,11 +42,15 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--append", action="store_true", help="append to --out instead of overwriting it")
     a = ap.parse_args(argv)
     tdp.load_plugins()
     ops = torch.ops.amd_dft
     dev = "cuda"
+    if a.dtype == "bf16":
+        return _main_bf16(a, ops, dev)
     lines = [f"Spherical harmonic transforms, fp32, {GRID} grid, hipGraph, median of {a.rounds} alternated rounds x "
              f"{a.iters} calls [min, max]; us per call; torch = torch.fft + einsum on an fp32 table",
              f"device: {torch.cuda.get_device_name(0)}", ""]
@@ -84,8 +95,54 @@ def main(argv=None):
         torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        with open(a.out, "a" if a.append else "w") as f:
+            f.write(("\n" if a.append else "") + "\n".join(lines) + "\n")
+
+
+def _main_bf16(a, ops, dev):
+    bf = torch.bfloat16
+    lines = [f"Spherical harmonic transforms, bf16 against fp32 of the same op, {GRID} grid, hipGraph, median of "
+             f"{a.rounds} alternated rounds x {a.iters} calls [min, max]; us per call",
+             f"device: {torch.cuda.get_device_name(0)}", ""]
+
+    def emit(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    for shape, trunc in SHAPES:
+        torch.manual_seed(0)
+        nlat, nlon = shape[-2:]
+        lmax = trunc or nlat
+        mmax = trunc or min(lmax, nlon // 2 + 1)
+        t32 = sht_tables(nlat, nlon, lmax, mmax, GRID, dev)
+        t16 = sht_tables(nlat, nlon, lmax, mmax, GRID, dev, bf)
+        x16 = torch.randn(*shape, device=dev).to(bf)
+        x32 = x16.float()
+        c32 = tdp.sht(x32, lmax, mmax, GRID)
+        c16 = c32.to(bf)
+        xf32 = ops.r2c(x32, [3], 2.0 * math.pi / nlon, [mmax, 0], torch.float32)
+        xf16 = xf32.to(bf)
+        rows = [("sht", lambda: tdp.sht(x16, lmax, mmax, GRID), lambda: tdp.sht(x32, lmax, mmax, GRID)),
+                ("isht", lambda: tdp.isht(c16, nlat, nlon, GRID), lambda: tdp.isht(c32, nlat, nlon, GRID)),
+                ("legendre", lambda: ops.legendre(xf16, t16.fwd, t16.fwd_split, 1),
+                 lambda: ops.legendre(xf32, t32.fwd, t32.fwd_split, 1))]
+        cols = 2 * shape[0] * shape[1]
+        emit(f"{list(shape)} lmax {lmax} mmax {mmax}   {ops.legendre_info(nlat, lmax, mmax, cols, 1, True)}")
+        for name, new, old in rows:
+            diff = _rel(new(), old())
+            tn, to = [], []
+            for _ in range(a.rounds):
+                to.append(time_graph(old, a.iters))
+                tn.append(time_graph(new, a.iters))
+            mo, mn = statistics.median(to), statistics.median(tn)
+            emit(f"  {name:<9} fp32 {mo:9.1f} us [{min(to):.1f}, {max(to):.1f}] | bf16 {mn:9.1f} us [{min(tn):.1f}, {max(tn):.1f}] | "
+                 f"fp32/bf16 {mo / mn:.2f} | rel diff {diff:.1e}")
+        del x16, x32, c16, c32, xf16, xf32
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a" if a.append else "w") as f:
+            f.write(("\n" if a.append else "") + "\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -614,17 +614,21 @@ at::Tensor fno_c2r_meta(const at::Tensor& yw, int64_t W, std::optional<at::Scala
 // ------------------------------------------------------------------ Legendre transform (latitude half of an SHT)
 // x [..., Q, M, 2] fp32 (complex as trailing re/im), table [M, R, Q] fp32 -> y [..., R, M, 2] fp32:
 //   y[n, r, m, :] = sum_q table[m, r, q] x[n, q, m, :]
+// or all three bfloat16: bf16 operands as they are on one MFMA per fragment pair, fp32 accumulation, one rounding at
+// the store (fp32 runs the bf16x3 split).  x and table of different dtypes raise.
 // tri declares the structurally zero part of the table (1: rows r < m, 2: columns q < m), which every
 // implementation treats as zero: tri = 1 returns exact zeros in y[.., r < m, m, :], and under tri = 2 every
 // implementation ignores x where q < m -- a NaN or Inf there does not reach the result.  The table itself must be
 // finite everywhere (the kernel multiplies partial tiles of it against staged zeros).
 // table_split: the table as the kernel reads it, split_bf16(rows=False) of the
-// table zero-padded to [M, ceil16(R), ceil32(Q)] -> bf16 [2, M, Rp, Qp]; built per call when absent.
-// legendre_out writes into a given contiguous fp32 tensor of the result's shape.
+// table zero-padded to [M, ceil16(R), ceil32(Q)] -> bf16 [2, M, Rp, Qp]; built per call when absent.  For a bf16
+// table it is the padded table itself, [1, M, Rp, Qp].
+// legendre_out writes into a given contiguous tensor of the result's shape and dtype.
 void check_legendre(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
-  TORCH_CHECK(x.scalar_type() == at::kFloat && table.scalar_type() == at::kFloat,
-              "legendre: x and table must be float32 (other precisions of the spherical transforms are not built), got ",
-              x.scalar_type(), " and ", table.scalar_type());
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  TORCH_CHECK((x.scalar_type() == at::kFloat || bf16) && table.scalar_type() == x.scalar_type(),
+              "legendre: x and table must both be float32 or both be bfloat16, got ", x.scalar_type(), " and ",
+              table.scalar_type());
   TORCH_CHECK(x.dim() >= 3 && x.size(-1) == 2 && table.dim() == 3, "legendre: x [..., Q, M, 2], table [M, R, Q]");
   TORCH_CHECK(x.size(-3) == table.size(2), "legendre: x has ", x.size(-3), " points along the transformed dim, the table ",
               table.size(2));
@@ -635,9 +639,10 @@ void check_legendre(const at::Tensor& x, const at::Tensor& table, const c10::opt
               "legendre: bad table size");
   if (present(ts)) {
     const int64_t Rp = (table.size(1) + 15) / 16 * 16, Qp = (table.size(2) + 31) / 32 * 32;
-    TORCH_CHECK(ts->scalar_type() == at::kBFloat16 && ts->sizes() == at::IntArrayRef({2, table.size(0), Rp, Qp}) &&
-                    ts->device() == x.device(),
-                "legendre: table_split must be bfloat16 [2, M, ceil16(R), ceil32(Q)] on the device of x");
+    TORCH_CHECK(ts->scalar_type() == at::kBFloat16 &&
+                    ts->sizes() == at::IntArrayRef({bf16 ? 1 : 2, table.size(0), Rp, Qp}) && ts->device() == x.device(),
+                "legendre: table_split must be bfloat16 [", bf16 ? 1 : 2,
+                ", M, ceil16(R), ceil32(Q)] on the device of x (two planes for a float32 table, one for bfloat16)");
   }
 }
 
@@ -650,6 +655,8 @@ std::vector<int64_t> legendre_out_shape(const at::Tensor& x, const at::Tensor& t
 at::Tensor legendre_cpu(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
   check_legendre(x, table, ts, tri);
   const int64_t M = table.size(0), R = table.size(1), Q = table.size(2);
+  if (x.scalar_type() == at::kBFloat16)  // the bf16 operands as they are, the product in fp32, rounded once
+    return legendre_cpu(x.to(at::kFloat), table.to(at::kFloat), c10::nullopt, tri).to(at::kBFloat16);
   at::Tensor t = table, xs = x.reshape({-1, Q, M, 2});
   if (tri != 0) {
     at::Tensor m = at::arange(M, table.options().dtype(at::kLong)).unsqueeze(1);
@@ -671,34 +678,41 @@ at::Tensor& legendre_out_cpu(const at::Tensor& x, const at::Tensor& table, const
   return out;
 }
 
-// the launch path of legendre and legendre_out: y is the contiguous fp32 result, 8-byte aligned (float2 stores)
+// the launch path of legendre and legendre_out: y is the contiguous result, aligned to one (re, im) pair (8 bytes
+// fp32, 4 bytes bf16: the kernel's stores)
 void legendre_run(const at::Tensor& x_, const at::Tensor& table_, const c10::optional<at::Tensor>& ts_, int64_t tri,
                   const at::Tensor& y) {
   const int64_t M = table_.size(0), R = table_.size(1), Q = table_.size(2);
   const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
   auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
+  const bool bf16 = x_.scalar_type() == at::kBFloat16;
   at::Tensor x = x_.contiguous();
-  // 8-byte loads of one mode's (re, im): a view at an odd float offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 != 0) x = x.clone();
+  // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % (bf16 ? 4 : 8) != 0) x = x.clone();
   at::Tensor ts;
   if (present(ts_)) {
     ts = ts_->contiguous();
   } else {
     TORCH_CHECK(table_.device() == x.device(), "legendre: table must be on the device of x");
     at::Tensor tp = at::constant_pad_nd(table_, {0, Qp - Q, 0, Rp - R}).contiguous();
-    ts = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
-    if (tp.numel() > 0)
-      launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
-                        static_cast<int>(Qp), false, stream);
+    if (bf16) {
+      ts = tp.unsqueeze(0);
+    } else {
+      ts = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
+      if (tp.numel() > 0)
+        launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
+                          static_cast<int>(Qp), false, stream);
+    }
   }
   if (y.numel() == 0) return;
   const int64_t N = x.numel() / (Q * M * 2);
   TORCH_CHECK(N < (int64_t(1) << 31) / 16, "legendre: too many fields");
   LegendreLaunch p;
-  p.x = x.data_ptr<float>();
+  p.x = x.data_ptr();
   p.th = reinterpret_cast<const uint16_t*>(ts.data_ptr());
-  p.tl = p.th + M * Rp * Qp;
-  p.y = y.data_ptr<float>();
+  p.tl = bf16 ? nullptr : p.th + M * Rp * Qp;
+  p.y = y.data_ptr();
+  p.bf16 = bf16 ? 1 : 0;
   p.N = N;
   p.Q = static_cast<int>(Q);
   p.R = static_cast<int>(R);
@@ -720,7 +734,7 @@ at::Tensor& legendre_out_cuda(const at::Tensor& x, const at::Tensor& table, cons
                               int64_t tri, at::Tensor& out) {
   check_legendre(x, table, ts, tri);
   check_out(out, legendre_out_shape(x, table), x, "legendre_out");
-  check_out_aligned(out, 8, "legendre_out");
+  check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 4 : 8, "legendre_out");
   const c10::DeviceGuard guard(x.device());
   legendre_run(x, table, ts, tri, out);
   checked(out, "legendre_out");
@@ -737,17 +751,19 @@ at::Tensor& legendre_out_meta(const at::Tensor&, const at::Tensor&, const c10::o
 }
 
 // Which tiling legendre runs for (Q, R, M, real columns = 2 x fields, tri) -- host only, no device (the companion
-// of fno_pointwise_info): "mfma MT=8 CT=2 slabs=23 rtiles=4 rgroups=1 mgroups=8 ctiles=3 lds=41472 wgs=24 tri=1"
-std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri) {
+// of fno_pointwise_info): "mfma MT=8 CT=2 slabs=23 rtiles=4 rgroups=1 mgroups=8 ctiles=3 lds=41472 wgs=24 tri=1";
+// bf16: the same tiling with the bf16 instances' LDS bytes and a trailing " bf16=1"
+std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
   TORCH_CHECK(Q >= 1 && R >= 1 && M >= 1 && cols >= 2 && cols % 2 == 0 && Q < (1 << 30) && R < (1 << 30) &&
                   M < (1 << 30) && cols < (int64_t(1) << 31) / 8,
               "amd_dft.legendre_info: Q, R, M must be >= 1 and cols a positive even count");
   TORCH_CHECK(tri >= 0 && tri <= 2, "amd_dft.legendre_info: tri must be 0, 1 or 2");
-  const LegendreRoute r = legendre_route(Q, R, M, cols, static_cast<int>(tri));
+  const LegendreRoute r = legendre_route(Q, R, M, cols, static_cast<int>(tri), bf16);
   return "mfma MT=" + std::to_string(r.mt) + " CT=" + std::to_string(r.ct) + " slabs=" + std::to_string(r.slabs) +
          " rtiles=" + std::to_string(r.rtiles) + " rgroups=" + std::to_string(r.rgroups) +
          " mgroups=" + std::to_string(r.mgroups) + " ctiles=" + std::to_string(r.ctiles) +
-         " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri);
+         " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri) +
+         (bf16 ? " bf16=1" : "");
 }
 
 // ------------------------------------------------------------------ SFNO per-degree channel mixing
@@ -755,10 +771,13 @@ std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t
 // -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
 // tri = 1 declares c zero where l < m (the spectrum of a real field): every implementation ignores c there and
 // returns exact zeros.  w_split: the weights as the kernel reads them (sfno_mix_split); built per call when absent.
+// All three bfloat16 instead: bf16 operands as they are on one MFMA per fragment pair, fp32 accumulation, one rounding
+// at the store.  c and w of different dtypes raise.
 void check_sfno_mix(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
-  TORCH_CHECK(c.scalar_type() == at::kFloat && w.scalar_type() == at::kFloat,
-              "sfno_mix: c and w must be float32 (other precisions of the spherical layers are not built), got ",
-              c.scalar_type(), " and ", w.scalar_type());
+  const bool bf16 = c.scalar_type() == at::kBFloat16;
+  TORCH_CHECK((c.scalar_type() == at::kFloat || bf16) && w.scalar_type() == c.scalar_type(),
+              "sfno_mix: c and w must both be float32 or both be bfloat16, got ", c.scalar_type(), " and ",
+              w.scalar_type());
   TORCH_CHECK(c.dim() == 5 && c.size(4) == 2 && w.dim() == 4 && w.size(3) == 2,
               "sfno_mix: c [B, Cin, L, M, 2], w [Cin, Cout, L, 2]");
   TORCH_CHECK(c.size(1) == w.size(0) && w.size(0) >= 1, "sfno_mix: c has ", c.size(1), " input channels, w ", w.size(0));
@@ -769,24 +788,28 @@ void check_sfno_mix(const at::Tensor& c, const at::Tensor& w, const c10::optiona
               "sfno_mix: tensor too large");
   if (present(ws)) {
     const int64_t Op = (w.size(1) + 15) / 16 * 16, Kp = (2 * w.size(0) + 31) / 32 * 32;
-    TORCH_CHECK(ws->scalar_type() == at::kBFloat16 && ws->sizes() == at::IntArrayRef({2, w.size(2), Op, Kp}) &&
-                    ws->device() == c.device(),
-                "sfno_mix: w_split must be bfloat16 [2, L, ceil16(Cout), ceil32(2 Cin)] on the device of c");
+    TORCH_CHECK(ws->scalar_type() == at::kBFloat16 &&
+                    ws->sizes() == at::IntArrayRef({bf16 ? 1 : 2, w.size(2), Op, Kp}) && ws->device() == c.device(),
+                "sfno_mix: w_split must be bfloat16 [", bf16 ? 1 : 2,
+                ", L, ceil16(Cout), ceil32(2 Cin)] on the device of c (two planes for float32 weights, one for bfloat16)");
   } else {
     TORCH_CHECK(w.device() == c.device(), "sfno_mix: w must be on the device of c");
   }
 }
 
 // w [Cin, Cout, L, 2] fp32 -> bf16 [2, L, ceil16(Cout), ceil32(2 Cin)]: the (hi, lo) planes of the degree-major real
-// form W[l][o][2 i] = Wr[i, o, l], W[l][o][2 i + 1] = Wi[i, o, l], zero-padded.  Any device.
+// form W[l][o][2 i] = Wr[i, o, l], W[l][o][2 i + 1] = Wi[i, o, l], zero-padded.  Any device.  bf16 weights: the one
+// plane of the same form, [1, L, Op, Kp].
 at::Tensor sfno_mix_split(const at::Tensor& w) {
-  TORCH_CHECK(w.scalar_type() == at::kFloat, "sfno_mix_split: w must be float32, got ", w.scalar_type());
+  TORCH_CHECK(w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16,
+              "sfno_mix_split: w must be float32 or bfloat16, got ", w.scalar_type());
   TORCH_CHECK(w.dim() == 4 && w.size(3) == 2 && w.size(0) >= 1, "sfno_mix_split: w [Cin, Cout, L, 2]");
   const int64_t Cin = w.size(0), Cout = w.size(1), L = w.size(2);
   const int64_t Op = (Cout + 15) / 16 * 16, Kp = (2 * Cin + 31) / 32 * 32;
   at::Tensor wp = at::constant_pad_nd(w.detach().permute({2, 1, 0, 3}).reshape({L, Cout, 2 * Cin}),
                                       {0, Kp - 2 * Cin, 0, Op - Cout})
                       .contiguous();
+  if (w.scalar_type() == at::kBFloat16) return wp.unsqueeze(0);
   if (wp.is_cuda()) {
     const c10::DeviceGuard guard(wp.device());
     at::Tensor ts = at::empty({2, L, Op, Kp}, wp.options().dtype(at::kBFloat16));
@@ -802,6 +825,8 @@ at::Tensor sfno_mix_split(const at::Tensor& w) {
 
 at::Tensor sfno_mix_cpu(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
   check_sfno_mix(c, w, ws, tri);
+  if (c.scalar_type() == at::kBFloat16)  // the bf16 operands as they are, the product in fp32, rounded once
+    return sfno_mix_cpu(c.to(at::kFloat), w.to(at::kFloat), c10::nullopt, tri).to(at::kBFloat16);
   at::Tensor y = at::view_as_real(at::einsum("bilm,iol->bolm", {at::view_as_complex(c.contiguous()),
                                                                at::view_as_complex(w.contiguous())}))
                      .contiguous();
@@ -825,21 +850,23 @@ at::Tensor& sfno_mix_out_cpu(const at::Tensor& c, const at::Tensor& w, const c10
   return out;
 }
 
-// the launch path of sfno_mix and sfno_mix_out: y is the contiguous fp32 result, 8-byte aligned (float2 stores)
+// the launch path of sfno_mix and sfno_mix_out: y is the contiguous result, aligned to one (re, im) pair (8 bytes
+// fp32, 4 bytes bf16: the kernel's stores)
 void sfno_mix_run(const at::Tensor& c_, const at::Tensor& w_, const c10::optional<at::Tensor>& ws_, int64_t tri,
                   const at::Tensor& y) {
   const int64_t B = c_.size(0), Cin = c_.size(1), L = c_.size(2), M = c_.size(3), Cout = w_.size(1);
+  const bool bf16 = c_.scalar_type() == at::kBFloat16;
   at::Tensor c = c_.contiguous();
-  // 8-byte loads of one order's (re, im): a view at an odd float offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 != 0) c = c.clone();
+  // one load per order's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
+  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % (bf16 ? 4 : 8) != 0) c = c.clone();
   at::Tensor ws = present(ws_) ? ws_->contiguous() : sfno_mix_split(w_);
   if (y.numel() == 0) return;
-  const int64_t plane = ws.numel() / 2;
   SfnoMixLaunch p;
-  p.c = c.data_ptr<float>();
+  p.c = c.data_ptr();
   p.wh = reinterpret_cast<const uint16_t*>(ws.data_ptr());
-  p.wl = p.wh + plane;
-  p.y = y.data_ptr<float>();
+  p.wl = bf16 ? nullptr : p.wh + ws.numel() / 2;  // fp32: the lo plane follows the hi plane
+  p.y = y.data_ptr();
+  p.bf16 = bf16 ? 1 : 0;
   p.B = static_cast<int>(B);
   p.Cin = static_cast<int>(Cin);
   p.Cout = static_cast<int>(Cout);
@@ -861,7 +888,7 @@ at::Tensor& sfno_mix_out_cuda(const at::Tensor& c, const at::Tensor& w, const c1
                               int64_t tri, at::Tensor& out) {
   check_sfno_mix(c, w, ws, tri);
   check_out(out, sfno_mix_out_shape(c, w), c, "sfno_mix_out");
-  check_out_aligned(out, 8, "sfno_mix_out");
+  check_out_aligned(out, c.scalar_type() == at::kBFloat16 ? 4 : 8, "sfno_mix_out");
   const c10::DeviceGuard guard(c.device());
   sfno_mix_run(c, w, ws, tri, out);
   checked(out, "sfno_mix_out");
@@ -878,17 +905,18 @@ at::Tensor& sfno_mix_out_meta(const at::Tensor&, const at::Tensor&, const c10::o
 }
 
 // The tiling sfno_mix runs for (B, Cin, Cout, L, M, tri) -- host only, no device (the companion of legendre_info):
-// "mfma coltile=64 slabs=4 otiles=4 ogroups=1 ctiles=3 lds=20480 wgs=363 grid=540 tri=1"
-std::string sfno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64_t M, int64_t tri) {
+// "mfma coltile=64 slabs=4 otiles=4 ogroups=1 ctiles=3 lds=20480 wgs=363 grid=540 tri=1"; bf16: the same tiling with
+// the bf16 instance's LDS bytes and a trailing " bf16=1"
+std::string sfno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64_t M, int64_t tri, bool bf16) {
   TORCH_CHECK(B >= 1 && Cin >= 1 && Cout >= 1 && L >= 1 && M >= 1 && Cin < (1 << 28) && Cout < (1 << 21) &&
                   L <= 65535 && B * M < (int64_t(1) << 30),
               "amd_dft.sfno_mix_info: B, Cin, Cout, L, M must be >= 1 (L <= 65535, B * M < 2^30)");
   TORCH_CHECK(tri == 0 || tri == 1, "amd_dft.sfno_mix_info: tri must be 0 or 1");
-  const SfnoMixRoute r = sfno_mix_route(B, Cin, Cout, L, M, static_cast<int>(tri));
+  const SfnoMixRoute r = sfno_mix_route(B, Cin, Cout, L, M, static_cast<int>(tri), bf16);
   return "mfma coltile=" + std::to_string(r.coltile) + " slabs=" + std::to_string(r.slabs) +
          " otiles=" + std::to_string(r.otiles) + " ogroups=" + std::to_string(r.ogroups) +
          " ctiles=" + std::to_string(r.ctiles) + " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) +
-         " grid=" + std::to_string(r.grid) + " tri=" + std::to_string(tri);
+         " grid=" + std::to_string(r.grid) + " tri=" + std::to_string(tri) + (bf16 ? " bf16=1" : "");
 }
 
 // ------------------------------------------------------------------ LayerNorm (+ residual)
@@ -1120,11 +1148,12 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
   m.def("legendre(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor");
   m.def("legendre_out(Tensor x, Tensor table, Tensor? table_split, int tri, Tensor(a!) out) -> Tensor(a!)");
-  m.def("legendre_info(int Q, int R, int M, int cols, int tri) -> str", &amd_dft::legendre_info);
+  m.def("legendre_info(int Q, int R, int M, int cols, int tri, bool bf16=False) -> str", &amd_dft::legendre_info);
   m.def("sfno_mix(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor");
   m.def("sfno_mix_out(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
-  m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri) -> str", &amd_dft::sfno_mix_info);
+  m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri, bool bf16=False) -> str",
+        &amd_dft::sfno_mix_info);
 }
 
 TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {

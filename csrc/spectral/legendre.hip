@@ -31,7 +31,13 @@
 // The next slab's x values are loaded into registers before the current slab's MFMAs; the table fragments
 // of a slab are requested before the slab is written to LDS.  No atomics: bit-reproducible run to run.
 //
-// LDS per workgroup (legendre_lds_bytes): 41472 B at MT = 8, CT = 2; 20992 B at 4 x 2; 10752 B at 4 x 1.
+// bf16 instances (BF): x and y are bf16, T is the one plane bf16(T) (the hi plane alone), so a fragment pair is one
+// MFMA instead of three; accumulation stays fp32 and the result is rounded once, at the store.  A (re, im) pair is
+// one 4-byte load or store (global rows are runs of 4 MT bytes), staging packs the q pairs of the bf16 values as
+// they are, and the slab image is the one plane.  Tiling, tri, the edge zeros and the prefetch are the same code.
+//
+// LDS per workgroup (legendre_lds_bytes): 41472 B at MT = 8, CT = 2; 20992 B at 4 x 2; 10752 B at 4 x 1
+// (bf16: 20736, 10496, 5376).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -60,9 +66,9 @@ __device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_
   lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
 }
 
-template <int CT, int MW>
-__global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__ x, const uint16_t* __restrict__ th,
-                                                       const uint16_t* __restrict__ tl, float* __restrict__ y,
+template <int CT, int MW, bool BF>
+__global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ x, const uint16_t* __restrict__ th,
+                                                       const uint16_t* __restrict__ tl, void* __restrict__ y,
                                                        int64_t N, int Q, int R, int M, int Rp, int Qp, int tri) {
   constexpr int MT = 4 * MW;                       // modes per workgroup
   constexpr int NT = 8 * CT;                       // fields n per workgroup
@@ -80,8 +86,8 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
   const int m0 = blockIdx.x * MT;
   const int64_t n0 = static_cast<int64_t>(blockIdx.y) * NT;
   const int r0 = blockIdx.z * 16 * RT;
-  const float2* x2 = reinterpret_cast<const float2*>(x);
-  float2* y2 = reinterpret_cast<float2*>(y);
+  const float2* x2 = reinterpret_cast<const float2*>(x);      // fp32: one (re, im) pair
+  const uint32_t* xb2 = reinterpret_cast<const uint32_t*>(x);  // bf16: one (re, im) pair
 
   const int nslab = (Q + kLegSlab - 1) / kLegSlab;
   // tri = 2: all columns q < m0 are zero for every mode here; tri = 1: a row group below m0 is all zero
@@ -100,7 +106,8 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
     }
   }
 
-  float xr[XI][4];
+  float xr[BF ? 1 : XI][4];      // fp32: (re, im) of q and q + 1
+  uint32_t xb[BF ? XI : 1][2];   // bf16: the packed (re, im) of q and of q + 1
   auto load_slab = [&](int s) {
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
@@ -108,17 +115,29 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
       const int ml = idx % MT, qp = (idx / MT) & 15, nl = idx / (MT * 16);
       const int m = m0 + ml, q = s * kLegSlab + 2 * qp;
       const int64_t n = n0 + nl;
-      float2 a = make_float2(0.f, 0.f), b = a;
-      if (m < M && n < N) {
-        const float2* src = x2 + ((n * Q + q) * M + m);
-        const int qmin = tri == 2 ? m : 0;
-        if (q < Q && q >= qmin) a = src[0];
-        if (q + 1 < Q && q + 1 >= qmin) b = src[M];
+      if constexpr (BF) {
+        uint32_t a = 0u, b = 0u;
+        if (m < M && n < N) {
+          const uint32_t* src = xb2 + ((n * Q + q) * M + m);
+          const int qmin = tri == 2 ? m : 0;
+          if (q < Q && q >= qmin) a = src[0];
+          if (q + 1 < Q && q + 1 >= qmin) b = src[M];
+        }
+        xb[i][0] = a;
+        xb[i][1] = b;
+      } else {
+        float2 a = make_float2(0.f, 0.f), b = a;
+        if (m < M && n < N) {
+          const float2* src = x2 + ((n * Q + q) * M + m);
+          const int qmin = tri == 2 ? m : 0;
+          if (q < Q && q >= qmin) a = src[0];
+          if (q + 1 < Q && q + 1 >= qmin) b = src[M];
+        }
+        xr[i][0] = a.x;
+        xr[i][1] = a.y;
+        xr[i][2] = b.x;
+        xr[i][3] = b.y;
       }
-      xr[i][0] = a.x;
-      xr[i][1] = a.y;
-      xr[i][2] = b.x;
-      xr[i][3] = b.y;
     }
   };
 
@@ -133,7 +152,7 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
   if (s0 < nslab) load_slab(s0);
   for (int s = s0; s < nslab; ++s) {
     // ---- this slab's table fragments (global, both planes): lane = T[m][rg + l15][32 s + 8 lq + 0..7]
-    uint4 ah[MW][RT], al[MW][RT];
+    uint4 ah[MW][RT], al[BF ? 1 : MW][BF ? 1 : RT];
 #pragma unroll
     for (int j = 0; j < MW; ++j) {
       const int m = m0 + wv * MW + j;
@@ -143,24 +162,30 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
         if (live[j][rt] && mode_live) {
           const int64_t off = (static_cast<int64_t>(m) * Rp + r0 + 16 * rt + l15) * Qp + s * kLegSlab + 8 * lq;
           ah[j][rt] = *reinterpret_cast<const uint4*>(th + off);
-          al[j][rt] = *reinterpret_cast<const uint4*>(tl + off);
+          if constexpr (!BF) al[j][rt] = *reinterpret_cast<const uint4*>(tl + off);
         }
       }
     }
     __syncthreads();  // every wave is done reading the previous slab
-    // ---- the slab image: x split into bf16 (hi, lo), q pairs packed, zeros outside x
+    // ---- the slab image: x split into bf16 (hi, lo) (bf16: as it is), q pairs packed, zeros outside x
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
       const int idx = tid + 256 * i;
       const int ml = idx % MT, qp = (idx / MT) & 15, nl = idx / (MT * 16);
       char* dst = smem + ml * MLS + 2 * nl * kLegXPitch + 4 * qp;
-      uint32_t hr, lr, hi, li;
-      split_pk(xr[i][0], xr[i][2], hr, lr);
-      split_pk(xr[i][1], xr[i][3], hi, li);
-      *reinterpret_cast<uint32_t*>(dst) = hr;
-      *reinterpret_cast<uint32_t*>(dst + kLegXPitch) = hi;
-      *reinterpret_cast<uint32_t*>(dst + PLANE) = lr;
-      *reinterpret_cast<uint32_t*>(dst + PLANE + kLegXPitch) = li;
+      if constexpr (BF) {
+        const uint32_t a = xb[i][0], b = xb[i][1];  // (re | im << 16) of q and of q + 1
+        *reinterpret_cast<uint32_t*>(dst) = (a & 0xffffu) | (b << 16);
+        *reinterpret_cast<uint32_t*>(dst + kLegXPitch) = (a >> 16) | (b & 0xffff0000u);
+      } else {
+        uint32_t hr, lr, hi, li;
+        split_pk(xr[i][0], xr[i][2], hr, lr);
+        split_pk(xr[i][1], xr[i][3], hi, li);
+        *reinterpret_cast<uint32_t*>(dst) = hr;
+        *reinterpret_cast<uint32_t*>(dst + kLegXPitch) = hi;
+        *reinterpret_cast<uint32_t*>(dst + PLANE) = lr;
+        *reinterpret_cast<uint32_t*>(dst + PLANE + kLegXPitch) = li;
+      }
     }
     __syncthreads();
     // ---- the next slab's global loads, in flight during the MFMAs
@@ -171,22 +196,25 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
       const int ml = wv * MW + j;
       const bool mode_live = !(tri == 2 && s * kLegSlab + kLegSlab - 1 < m0 + ml);
       if (!mode_live) continue;
-      bf16x8 bh[CT], bl[CT];
+      bf16x8 bh[CT], bl[BF ? 1 : CT];
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         const char* src = smem + ml * MLS + (16 * ct + l15) * kLegXPitch + 16 * lq;
         bh[ct] = *reinterpret_cast<const bf16x8*>(src);
-        bl[ct] = *reinterpret_cast<const bf16x8*>(src + PLANE);
+        if constexpr (!BF) bl[ct] = *reinterpret_cast<const bf16x8*>(src + PLANE);
       }
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
         if (live[j][rt]) {
-          const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[j][rt]), Al = __builtin_bit_cast(bf16x8, al[j][rt]);
+          const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[j][rt]);
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct) {
             acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bh[ct], acc[j][rt][ct], 0, 0, 0);
-            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, bh[ct], acc[j][rt][ct], 0, 0, 0);
-            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bl[ct], acc[j][rt][ct], 0, 0, 0);
+            if constexpr (!BF) {
+              const bf16x8 Al = __builtin_bit_cast(bf16x8, al[j][rt]);
+              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, bh[ct], acc[j][rt][ct], 0, 0, 0);
+              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bl[ct], acc[j][rt][ct], 0, 0, 0);
+            }
           }
         }
       }
@@ -222,17 +250,23 @@ __global__ void __launch_bounds__(256) legendre_kernel(const float* __restrict__
       if (m < M && rg < R && n < N) {
         float2 v = *reinterpret_cast<const float2*>(ys + r * YR + nl * YP + 2 * ml);
         if (tri == 1 && rg < m) v = make_float2(0.f, 0.f);
-        y2[(n * R + rg) * M + m] = v;
+        if constexpr (BF) reinterpret_cast<uint32_t*>(y)[(n * R + rg) * M + m] = pk_bf16(v.x, v.y);
+        else reinterpret_cast<float2*>(y)[(n * R + rg) * M + m] = v;
       }
     }
   }
 }
 
+template <int CT, int MW, bool BF>
+void launch_prec(const LegendreLaunch& p, const LegendreRoute& r, hipStream_t st) {
+  const dim3 grid(r.mgroups, r.ctiles, r.rgroups);
+  hipLaunchKernelGGL((legendre_kernel<CT, MW, BF>), grid, dim3(256), static_cast<size_t>(r.lds), st, p.x, p.th, p.tl,
+                     p.y, p.N, p.Q, p.R, p.M, r.rtiles * 16, r.slabs * kLegSlab, p.tri);
+}
 template <int CT, int MW>
 void launch_inst(const LegendreLaunch& p, const LegendreRoute& r, hipStream_t st) {
-  const dim3 grid(r.mgroups, r.ctiles, r.rgroups);
-  hipLaunchKernelGGL((legendre_kernel<CT, MW>), grid, dim3(256), static_cast<size_t>(r.lds), st, p.x, p.th, p.tl, p.y,
-                     p.N, p.Q, p.R, p.M, r.rtiles * 16, r.slabs * kLegSlab, p.tri);
+  if (p.bf16) launch_prec<CT, MW, true>(p, r, st);
+  else launch_prec<CT, MW, false>(p, r, st);
 }
 
 }  // namespace
@@ -241,7 +275,7 @@ void launch_legendre(const LegendreLaunch& p, void* stream) {
   if (p.N == 0 || p.R == 0 || p.M == 0) return;
   if (p.Q < 1) throw std::runtime_error("amd_dft: legendre: Q must be >= 1");
   if (p.tri < 0 || p.tri > 2) throw std::runtime_error("amd_dft: legendre: tri must be 0, 1 or 2");
-  const LegendreRoute r = legendre_route(p.Q, p.R, p.M, 2 * p.N, p.tri);
+  const LegendreRoute r = legendre_route(p.Q, p.R, p.M, 2 * p.N, p.tri, p.bf16 != 0);
   if (r.ctiles > 65535 || r.rgroups > 65535) throw std::runtime_error("amd_dft: legendre: tensor too large");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (r.mt == 8) {

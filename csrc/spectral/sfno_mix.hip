@@ -33,12 +33,20 @@
 // The next slab's spectrum values are loaded into registers before the current slab's MFMAs; the table fragments
 // of a slab are requested before the slab is written to LDS.  No atomics: bit-reproducible run to run.
 //
-// LDS per workgroup (sfno_mix_lds_bytes): 2 planes x 128 columns x 80 B = 20480 B.
+// bf16 instance (BF): c and y are bf16, the weights the one plane bf16(W) (the hi plane alone), so a fragment pair
+// is one MFMA instead of three; accumulation stays fp32 and the result is rounded once, at the store.  A (re, im)
+// pair is one 4-byte load or store: staging builds (re, -im) and (im, re) from the packed pair with a sign flip and
+// a rotate, the slab image is the one plane, and at the store the two lanes of an order exchange halves of their
+// rows so that each writes packed pairs.  Column flattening, tri, the empty-tile exit and the edge zeros are the
+// same code.
+//
+// LDS per workgroup (sfno_mix_lds_bytes): 2 planes x 128 columns x 80 B = 20480 B (bf16: 1 plane, 10240 B).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "spectral.h"
 
@@ -62,8 +70,9 @@ __device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_
   lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
 }
 
-__global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__ c, const uint16_t* __restrict__ wh,
-                                                       const uint16_t* __restrict__ wl, float* __restrict__ y, int B,
+template <bool BF>
+__global__ void __launch_bounds__(256) sfno_mix_kernel(const void* __restrict__ c, const uint16_t* __restrict__ wh,
+                                                       const uint16_t* __restrict__ wl, void* __restrict__ y, int B,
                                                        int Cin, int Cout, int L, int M, int Op, int Kp, int tri) {
   constexpr int NJ = kSfnoColTile;              // complex columns per workgroup
   constexpr int RT = kSfnoRowTiles;
@@ -77,8 +86,14 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
   const int Ml = tri == 1 && l + 1 < M ? l + 1 : M;  // live orders of this degree
   const int64_t ncols = static_cast<int64_t>(B) * Ml;
   const int64_t j0 = static_cast<int64_t>(blockIdx.x) * NJ;
-  const float2* c2 = reinterpret_cast<const float2*>(c);
-  float2* y2 = reinterpret_cast<float2*>(y);
+  // one (re, im) pair: a float2, or a packed bf16 pair
+  using Pair = typename std::conditional<BF, uint32_t, float2>::type;
+  const Pair* c2 = reinterpret_cast<const Pair*>(c);
+  Pair* y2 = reinterpret_cast<Pair*>(y);
+  const auto zero = [] {
+    if constexpr (BF) return 0u;
+    else return make_float2(0.f, 0.f);
+  };
 
   // ---- the structurally zero part y[b, o0.., l, Ml..M-1]: shared by the workgroups of this (degree, group)
   if (Ml < M) {
@@ -89,7 +104,7 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
       const int mz = static_cast<int>(idx % zr);
       const int64_t t = idx / zr;
       const int ol = static_cast<int>(t % no), b = static_cast<int>(t / no);
-      y2[((static_cast<int64_t>(b) * Cout + o0 + ol) * L + l) * M + Ml + mz] = make_float2(0.f, 0.f);
+      y2[((static_cast<int64_t>(b) * Cout + o0 + ol) * L + l) * M + Ml + mz] = zero();
     }
   }
   if (j0 >= ncols) return;  // empty column tile (block-uniform): no loads
@@ -97,8 +112,8 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
   // ---- the column this lane stages, slab after slab: complex column 16 wv + l15 of the tile, channels 4 q + lq
   const int jl = 16 * wv + l15;
   const bool col_ok = j0 + jl < ncols;
-  const int64_t chs = static_cast<int64_t>(L) * M;  // float2 stride between input channels
-  const float2* src = c2;
+  const int64_t chs = static_cast<int64_t>(L) * M;  // pair stride between input channels
+  const Pair* src = c2;
   if (col_ok) {
     const int64_t j = j0 + jl;
     const int b = static_cast<int>(j / Ml), m = static_cast<int>(j % Ml);
@@ -110,12 +125,12 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) live[rt] = wave_live && o0 + 16 * rt < Cout;
 
-  float2 xr[XI];
+  Pair xr[XI];
   auto load_slab = [&](int s) {
 #pragma unroll
     for (int q = 0; q < XI; ++q) {
       const int i = s * (kSfnoSlab / 2) + 4 * q + lq;
-      xr[q] = col_ok && i < Cin ? src[i * chs] : make_float2(0.f, 0.f);
+      xr[q] = col_ok && i < Cin ? src[i * chs] : zero();
     }
   };
 
@@ -129,13 +144,13 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
   load_slab(0);
   for (int s = 0; s < nslab; ++s) {
     // ---- this slab's weight fragments (global, both planes): lane = W[l][o0 + 16 rt + l15][32 s + 8 lq + 0..7]
-    uint4 ah[RT], al[RT];
+    uint4 ah[RT], al[BF ? 1 : RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       if (live[rt]) {
         const int64_t off = (static_cast<int64_t>(l) * Op + o0 + 16 * rt + l15) * Kp + s * kSfnoSlab + 8 * lq;
         ah[rt] = *reinterpret_cast<const uint4*>(wh + off);
-        al[rt] = *reinterpret_cast<const uint4*>(wl + off);
+        if constexpr (!BF) al[rt] = *reinterpret_cast<const uint4*>(wl + off);
       }
     }
     __syncthreads();  // every wave is done reading the previous slab
@@ -143,35 +158,44 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
 #pragma unroll
     for (int q = 0; q < XI; ++q) {
       char* dst = smem + 2 * jl * kSfnoXPitch + 4 * (4 * q + lq);
-      uint32_t hr, lr, hi, li;
-      split_pk(xr[q].x, -xr[q].y, hr, lr);  // real column: (re, -im)
-      split_pk(xr[q].y, xr[q].x, hi, li);   // imaginary column: (im, re)
-      *reinterpret_cast<uint32_t*>(dst) = hr;
-      *reinterpret_cast<uint32_t*>(dst + kSfnoXPitch) = hi;
-      *reinterpret_cast<uint32_t*>(dst + PLANE) = lr;
-      *reinterpret_cast<uint32_t*>(dst + PLANE + kSfnoXPitch) = li;
+      if constexpr (BF) {
+        const uint32_t v = xr[q];  // re | im << 16
+        *reinterpret_cast<uint32_t*>(dst) = v ^ 0x80000000u;                  // real column: (re, -im)
+        *reinterpret_cast<uint32_t*>(dst + kSfnoXPitch) = (v >> 16) | (v << 16);  // imaginary column: (im, re)
+      } else {
+        uint32_t hr, lr, hi, li;
+        split_pk(xr[q].x, -xr[q].y, hr, lr);  // real column: (re, -im)
+        split_pk(xr[q].y, xr[q].x, hi, li);   // imaginary column: (im, re)
+        *reinterpret_cast<uint32_t*>(dst) = hr;
+        *reinterpret_cast<uint32_t*>(dst + kSfnoXPitch) = hi;
+        *reinterpret_cast<uint32_t*>(dst + PLANE) = lr;
+        *reinterpret_cast<uint32_t*>(dst + PLANE + kSfnoXPitch) = li;
+      }
     }
     __syncthreads();
     // ---- the next slab's global loads, in flight during the MFMAs
     if (s + 1 < nslab) load_slab(s + 1);
     // ---- MFMAs: live row tiles of a live wave only
     if (wave_live) {
-      bf16x8 bh[2], bl[2];
+      bf16x8 bh[2], bl[BF ? 1 : 2];
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
         const char* bs = smem + (32 * wv + 16 * ct + l15) * kSfnoXPitch + 16 * lq;
         bh[ct] = *reinterpret_cast<const bf16x8*>(bs);
-        bl[ct] = *reinterpret_cast<const bf16x8*>(bs + PLANE);
+        if constexpr (!BF) bl[ct] = *reinterpret_cast<const bf16x8*>(bs + PLANE);
       }
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
         if (live[rt]) {
-          const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[rt]), Al = __builtin_bit_cast(bf16x8, al[rt]);
+          const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[rt]);
 #pragma unroll
           for (int ct = 0; ct < 2; ++ct) {
             acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bh[ct], acc[rt][ct], 0, 0, 0);
-            acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, bh[ct], acc[rt][ct], 0, 0, 0);
-            acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bl[ct], acc[rt][ct], 0, 0, 0);
+            if constexpr (!BF) {
+              const bf16x8 Al = __builtin_bit_cast(bf16x8, al[rt]);
+              acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, bh[ct], acc[rt][ct], 0, 0, 0);
+              acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bl[ct], acc[rt][ct], 0, 0, 0);
+            }
           }
         }
       }
@@ -186,13 +210,32 @@ __global__ void __launch_bounds__(256) sfno_mix_kernel(const float* __restrict__
     const int64_t j = j0 + 16 * wv + 8 * ct + (l15 >> 1);
     if (j >= ncols) continue;
     const int b = static_cast<int>(j / Ml), m = static_cast<int>(j % Ml);
-    float* dst = y + (((static_cast<int64_t>(b) * Cout + o0) * L + l) * M + m) * 2 + (l15 & 1);
+    if constexpr (BF) {
+      // the even lane of an order holds re, the odd lane im, of rows i = 0..3: the even lane takes rows 0 and 2, the
+      // odd lane rows 1 and 3, each sending the other the half it does not store (both lanes of a pair are live here:
+      // j depends on l15 >> 1 alone)
+      uint32_t* dst = reinterpret_cast<uint32_t*>(y) + ((static_cast<int64_t>(b) * Cout + o0) * L + l) * M + m;
+      const bool odd = l15 & 1;
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
+      for (int rt = 0; rt < RT; ++rt) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ol = 16 * rt + 4 * lq + i;
-        if (o0 + ol < Cout) dst[ol * chs * 2] = acc[rt][ct][i];
+        for (int i = 0; i < 4; i += 2) {
+          const float own0 = acc[rt][ct][i], own1 = acc[rt][ct][i + 1];
+          const float got = __shfl_xor(odd ? own0 : own1, 1);
+          const int ol = 16 * rt + 4 * lq + i + (odd ? 1 : 0);
+          const uint32_t v = odd ? pk_bf16(got, own1) : pk_bf16(own0, got);
+          if (o0 + ol < Cout) dst[ol * chs] = v;
+        }
+      }
+    } else {
+      float* dst = reinterpret_cast<float*>(y) + (((static_cast<int64_t>(b) * Cout + o0) * L + l) * M + m) * 2 + (l15 & 1);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int ol = 16 * rt + 4 * lq + i;
+          if (o0 + ol < Cout) dst[ol * chs * 2] = acc[rt][ct][i];
+        }
       }
     }
   }
@@ -204,12 +247,18 @@ void launch_sfno_mix(const SfnoMixLaunch& p, void* stream) {
   if (p.B == 0 || p.Cout == 0 || p.L == 0 || p.M == 0) return;
   if (p.Cin < 1) throw std::runtime_error("amd_dft: sfno_mix: Cin must be >= 1");
   if (p.tri < 0 || p.tri > 1) throw std::runtime_error("amd_dft: sfno_mix: tri must be 0 or 1");
-  const SfnoMixRoute r = sfno_mix_route(p.B, p.Cin, p.Cout, p.L, p.M, p.tri);
+  const SfnoMixRoute r = sfno_mix_route(p.B, p.Cin, p.Cout, p.L, p.M, p.tri, p.bf16 != 0);
   if (r.ogroups > 65535 || p.L > 65535 || static_cast<int64_t>(p.B) * p.M >= (int64_t(1) << 30))
     throw std::runtime_error("amd_dft: sfno_mix: tensor too large");
   const dim3 grid(static_cast<unsigned>(r.ctiles), r.ogroups, p.L);
-  hipLaunchKernelGGL(sfno_mix_kernel, grid, dim3(256), static_cast<size_t>(r.lds), static_cast<hipStream_t>(stream),
-                     p.c, p.wh, p.wl, p.y, p.B, p.Cin, p.Cout, p.L, p.M, r.otiles * 16, r.slabs * kSfnoSlab, p.tri);
+  if (p.bf16)
+    hipLaunchKernelGGL(sfno_mix_kernel<true>, grid, dim3(256), static_cast<size_t>(r.lds),
+                       static_cast<hipStream_t>(stream), p.c, p.wh, p.wl, p.y, p.B, p.Cin, p.Cout, p.L, p.M,
+                       r.otiles * 16, r.slabs * kSfnoSlab, p.tri);
+  else
+    hipLaunchKernelGGL(sfno_mix_kernel<false>, grid, dim3(256), static_cast<size_t>(r.lds),
+                       static_cast<hipStream_t>(stream), p.c, p.wh, p.wl, p.y, p.B, p.Cin, p.Cout, p.L, p.M,
+                       r.otiles * 16, r.slabs * kSfnoSlab, p.tri);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: sfno_mix launch: ") + hipGetErrorString(e));
 }

@@ -142,13 +142,14 @@ inline FnoPointwiseRoute fno_pointwise_route(int cin, int cout, bool bf16, int64
 //   y[n, r, m, :] = sum_q T[m, r, q] * x[n, q, m, :]      (x complex as trailing re/im, T real, per mode m)
 // forward: Q = nlat, R = lmax, T = w_k P_l^m(cos theta_k); inverse: Q = lmax, R = nlat, T = P transposed.
 struct LegendreLaunch {
-  const float* x;      // [N, Q, M, 2] fp32
+  const void* x;       // [N, Q, M, 2] fp32 (bf16 if bf16)
   const uint16_t* th;  // [M, Rp, Qp] bf16, hi plane of T zero-padded to Rp = ceil16(R), Qp = ceil32(Q)
-  const uint16_t* tl;  // the lo plane, bf16(T - hi)
-  float* y;            // [N, R, M, 2] fp32
+  const uint16_t* tl;  // the lo plane, bf16(T - hi); not read if bf16
+  void* y;             // [N, R, M, 2] fp32 (bf16 if bf16)
   int64_t N;
   int Q, R, M;
   int tri = 0;         // 0: dense; 1: rows r < m are zero; 2: columns q < m are zero
+  int bf16 = 0;        // 1: bf16 x and y, one table plane (th = bf16(T)), one MFMA per fragment pair
 };
 // Which tiling a call takes (host only; launch_legendre and the legendre_info op both answer from here).
 // A workgroup (4 waves) owns mt consecutive modes (a wave mt / 4 of them), 8 ct fields n (ct 16-column
@@ -170,14 +171,14 @@ struct LegendreRoute {
   int64_t lds;     // dynamic LDS bytes per workgroup
   int64_t wgs;     // workgroups
 };
-inline int64_t legendre_lds_bytes(int mt, int ct) {
-  // slab image: 2 planes x mt modes x (16 ct columns x 80 B + a pad that spreads the modes over the banks);
+inline int64_t legendre_lds_bytes(int mt, int ct, bool bf16 = false) {
+  // slab image: 2 planes (bf16: 1) x mt modes x (16 ct columns x 80 B + a pad that spreads the modes over the banks);
   // output image (one 16-row tile, modes innermost): 16 x (8 ct x (2 mt + 2) + 4) floats -- they share the space
-  const int64_t xs = 2LL * mt * (16 * ct * kLegXPitch + 256 / mt);
+  const int64_t xs = (bf16 ? 1LL : 2LL) * mt * (16 * ct * kLegXPitch + 256 / mt);
   const int64_t ys = 16LL * (8 * ct * (2 * mt + 2) + 4) * 4;
   return xs > ys ? xs : ys;
 }
-inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/) {
+inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/, bool bf16 = false) {
   LegendreRoute r{};
   r.slabs = static_cast<int>((Q + kLegSlab - 1) / kLegSlab);
   r.rtiles = static_cast<int>((R + 15) / 16);
@@ -189,7 +190,7 @@ inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t col
   if (cols <= 16 || count(r.mt, r.ct) < kLegFillWgs) r.ct = 1;
   r.mgroups = static_cast<int>((M + r.mt - 1) / r.mt);
   r.ctiles = static_cast<int>((cols + 16 * r.ct - 1) / (16 * r.ct));
-  r.lds = legendre_lds_bytes(r.mt, r.ct);
+  r.lds = legendre_lds_bytes(r.mt, r.ct, bf16);
   r.wgs = count(r.mt, r.ct);
   return r;
 }
@@ -198,13 +199,14 @@ void launch_legendre(const LegendreLaunch& p, void* stream);
 // ---- SFNO per-degree channel mixing (sfno_mix.hip):
 //   y[b, o, l, m] = sum_i c[b, i, l, m] * w[i, o, l]       (complex; one weight per degree l, shared by all orders m)
 struct SfnoMixLaunch {
-  const float* c;      // [B, Cin, L, M, 2] fp32
+  const void* c;       // [B, Cin, L, M, 2] fp32 (bf16 if bf16)
   const uint16_t* wh;  // [L, Op, Kp] bf16, hi plane of the real form of w: row o, k = 2 i -> Wr[i, o, l],
                        // k = 2 i + 1 -> Wi[i, o, l], zero-padded to Op = ceil16(Cout), Kp = ceil32(2 Cin)
-  const uint16_t* wl;  // the lo plane, bf16(W - hi)
-  float* y;            // [B, Cout, L, M, 2] fp32
+  const uint16_t* wl;  // the lo plane, bf16(W - hi); not read if bf16
+  void* y;             // [B, Cout, L, M, 2] fp32 (bf16 if bf16)
   int B, Cin, Cout, L, M;
   int tri = 0;         // 0: dense; 1: c is zero where l < m -- orders m > l are not read, y is 0.0 there
+  int bf16 = 0;        // 1: bf16 c and y, one weight plane (wh = bf16(W)), one MFMA per fragment pair
 };
 // The tiling of a call (host only; launch_sfno_mix and the sfno_mix_info op both answer from here).  A workgroup
 // (4 waves) owns one degree, one group of up to 64 output channels and one tile of 64 complex (128 real) columns;
@@ -226,8 +228,9 @@ struct SfnoMixRoute {
   int64_t wgs;     // workgroups with a non-empty column tile (the ones that load and multiply)
   int64_t grid;    // workgroups launched
 };
-inline int64_t sfno_mix_lds_bytes() { return 2LL * 2 * kSfnoColTile * kSfnoXPitch; }
-inline SfnoMixRoute sfno_mix_route(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64_t M, int tri) {
+inline int64_t sfno_mix_lds_bytes(bool bf16 = false) { return (bf16 ? 1LL : 2LL) * 2 * kSfnoColTile * kSfnoXPitch; }
+inline SfnoMixRoute sfno_mix_route(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64_t M, int tri,
+                                   bool bf16 = false) {
   SfnoMixRoute r{};
   r.slabs = static_cast<int>((2 * Cin + kSfnoSlab - 1) / kSfnoSlab);
   r.otiles = static_cast<int>((Cout + 15) / 16);
@@ -238,7 +241,7 @@ inline SfnoMixRoute sfno_mix_route(int64_t B, int64_t Cin, int64_t Cout, int64_t
   r.ctiles = tiles(full);
   int64_t live = 0;
   for (int64_t l = 0; l < L; ++l) live += tiles(tri == 1 && l + 1 < M ? l + 1 : M);
-  r.lds = sfno_mix_lds_bytes();
+  r.lds = sfno_mix_lds_bytes(bf16);
   r.wgs = live * r.ogroups;
   r.grid = r.ctiles * r.ogroups * L;
   return r;

@@ -16,6 +16,11 @@ The mix of the amd backend is one of two ops (``mix=`` of the layers): ``fno_mix
 every order m, or ``sfno_mix`` (csrc/spectral/sfno_mix.hip), which reads the per-degree weights directly -- one
 bf16x3 MFMA GEMM per degree -- and needs no expansion.  ``"auto"`` expands up to ``EXPAND_LIMIT_BYTES`` and runs
 ``sfno_mix`` on device tensors above it; ``"degree"`` always runs ``sfno_mix``.
+
+Precision of the amd backend follows the input: fp32, or bf16 end to end (``sht``, ``sfno_mix``, ``isht`` and the
+``fno_pointwise`` tail all take and return bf16; the bf16 mix is the per-degree kernel under both ``mix`` values,
+since ``fno_mix`` has no bf16 kernel; the weights are cast and repacked once per dtype and cached on the module).  ``RealSHT`` / ``InverseRealSHT`` have complex tensors at one end, and complex bf16 does not exist: they stay
+fp32 / complex64, and bf16 callers use ``ops.sht.sht`` / ``isht`` (coefficients with a trailing re/im dim).
 """
 from __future__ import annotations
 
@@ -66,7 +71,8 @@ class _SHTBase(nn.Module):
 
 
 class RealSHT(_SHTBase):
-    """Forward real SHT: real [..., nlat, nlon] -> complex [..., lmax, mmax]."""
+    """Forward real SHT: real [..., nlat, nlon] -> complex [..., lmax, mmax].  amd backend: fp32 only -- there is no
+    complex bf16, so a bf16 field raises ``TypeError``; call ``sht`` (trailing re/im) instead."""
 
     @staticmethod
     def _make_table(w, P):
@@ -76,6 +82,9 @@ class RealSHT(_SHTBase):
         if x.shape[-2] != self.nlat or x.shape[-1] != self.nlon:
             raise ValueError(f"RealSHT: expected a [..., {self.nlat}, {self.nlon}] grid, got {tuple(x.shape)}")
         if self.backend == "amd":
+            if x.dtype == torch.bfloat16:
+                raise TypeError("RealSHT: complex bfloat16 does not exist; for a bfloat16 field call sht() "
+                                "(ops.sht.sht), which returns the coefficients with a trailing re/im dim")
             return torch.view_as_complex(S.sht(x, self.lmax, self.mmax, self.grid))
         xf = 2.0 * np.pi * torch.fft.rfft(x, dim=-1, norm="forward")[..., :self.mmax]
         c = torch.einsum("mlk,...kmc->...lmc", self._table(x), torch.view_as_real(xf))
@@ -83,13 +92,17 @@ class RealSHT(_SHTBase):
 
 
 class InverseRealSHT(_SHTBase):
-    """Inverse real SHT: complex [..., lmax, mmax] -> real [..., nlat, nlon]."""
+    """Inverse real SHT: complex [..., lmax, mmax] -> real [..., nlat, nlon].  amd backend: complex64 only -- bf16
+    coefficients (a real tensor with a trailing re/im dim) raise ``TypeError``; call ``isht`` instead."""
 
     @staticmethod
     def _make_table(w, P):
         return torch.from_numpy(np.ascontiguousarray(P.transpose(0, 2, 1)))  # [mmax, nlat, lmax]
 
     def forward(self, c: torch.Tensor) -> torch.Tensor:
+        if self.backend == "amd" and c.dtype == torch.bfloat16:
+            raise TypeError("InverseRealSHT: complex bfloat16 does not exist; for bfloat16 coefficients with a "
+                            "trailing re/im dim call isht() (ops.sht.isht)")
         if c.shape[-2] != self.lmax or c.shape[-1] != self.mmax:
             raise ValueError(f"InverseRealSHT: expected [..., {self.lmax}, {self.mmax}] coefficients, got {tuple(c.shape)}")
         if self.backend == "amd":
@@ -111,7 +124,13 @@ class SphericalConv2d(nn.Module):
       cached on the module (``w_degree``, as many bytes as the weights; rebuilt when the weights change, kept
       alive for captured graphs); a CPU tensor notes a ``sfno_mix`` fallback (not counted on CPU tensors) and mixes
       with ``torch.einsum``.
-    * ``"degree"``: ``sfno_mix`` on every device and at every size; the expansion is never built."""
+    * ``"degree"``: ``sfno_mix`` on every device and at every size; the expansion is never built.
+
+    A bf16 ``x`` runs bf16 end to end: ``sht`` -> ``sfno_mix`` -> ``isht`` on bf16 tensors, under both ``mix`` values,
+    on every device and at every size.  ``fno_mix`` has no bf16 kernel (it would upcast the spectrum and the whole
+    expansion, mix in fp32 and round back), so the bf16 ``"auto"`` never takes it and never builds the expansion; the
+    per-degree kernel reads the bf16 weights directly.  Its tables (``w_bf16``, ``w_degree_bf16``: the weights rounded
+    to bf16 once, and their one-plane repacked form) are cached beside the fp32 ones."""
 
     def __init__(self, in_ch: int, out_ch: int, nlat: int, nlon: int, lmax: Optional[int] = None,
                  mmax: Optional[int] = None, grid: str = "equiangular", backend: str = "amd", mix: str = "auto"):
@@ -142,10 +161,20 @@ class SphericalConv2d(nn.Module):
 
         return module_cached(self, "w_expanded", (self.weight,), build)
 
-    def _degree_weight(self) -> torch.Tensor:
+    def _degree_weight(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
         from ..ops.spectral import module_cached, sfno_mix_split
 
-        return module_cached(self, "w_degree", (self.weight,), lambda: sfno_mix_split(self.weight))
+        if dtype == torch.float32:
+            return module_cached(self, "w_degree", (self.weight,), lambda: sfno_mix_split(self.weight))
+        return module_cached(self, "w_degree_bf16", (self.weight,),
+                             lambda: sfno_mix_split(self.weight.detach().to(torch.bfloat16)))
+
+    def _weight_as(self, dtype: torch.dtype) -> torch.Tensor:
+        from ..ops.spectral import module_cached
+
+        if dtype == torch.float32:
+            return self.weight.detach().float()
+        return module_cached(self, "w_bf16", (self.weight,), lambda: self.weight.detach().to(torch.bfloat16))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.backend == "torch":
@@ -155,10 +184,12 @@ class SphericalConv2d(nn.Module):
 
         B = x.shape[0]
         L, M = self.sht.lmax, self.sht.mmax
-        c = S.sht(x, L, M, self.sht.grid)  # [B, Cin, L, M, 2]
+        c = S.sht(x, L, M, self.sht.grid)  # [B, Cin, L, M, 2], fp32 or bf16 as x
+        dt = c.dtype
         above = self.expanded_bytes() > EXPAND_LIMIT_BYTES
-        if self.mix == "degree" or (above and x.is_cuda):
-            y = sfno_mix(c, self.weight.detach().float(), self._degree_weight(), tri=1)
+        # bf16: always the per-degree kernel (fno_mix has no bf16 kernel; it would mix in fp32 between two casts)
+        if self.mix == "degree" or dt == torch.bfloat16 or (above and x.is_cuda):
+            y = sfno_mix(c, self._weight_as(dt), self._degree_weight(dt), tri=1)
         elif above:
             note_fallback("sfno_mix", "per-degree weights too large to expand over m for fno_mix: torch.einsum", x)
             wc = torch.view_as_complex(self.weight.float().contiguous())
@@ -171,7 +202,8 @@ class SphericalConv2d(nn.Module):
 class SFNOBlock(nn.Module):
     """One SFNO layer: ``act(SphericalConv2d(x) + Conv1x1(x))``.  On the amd backend the tail (1x1 convolution,
     bias, the spectral addend and the GELU) is one ``fno_pointwise`` call.  ``mix`` goes to the ``SphericalConv2d``
-    (``"auto"`` or ``"degree"``)."""
+    (``"auto"`` or ``"degree"``).  A bf16 ``x`` gives a bf16 layer: the bf16 ``SphericalConv2d`` and the bf16
+    ``fno_pointwise``."""
 
     def __init__(self, width: int, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None,
                  grid: str = "equiangular", activation: bool = True, backend: str = "amd", mix: str = "auto"):

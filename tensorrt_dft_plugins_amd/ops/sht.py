@@ -2,8 +2,8 @@
 
 A real SHT is a truncated real FFT along longitude followed by a Legendre transform along latitude.  The first
 half is the pruned ``r2c`` / ``c2r`` of :mod:`.dft`; the second is the ``legendre`` op
-(``csrc/spectral/legendre.hip``: a per-mode real matrix applied along latitude to the complex spectrum, bf16x3 on
-MFMA, fp32 in and out).
+(``csrc/spectral/legendre.hip``: a per-mode real matrix applied along latitude to the complex spectrum on MFMA:
+bf16x3 with fp32 in and out, or plain bf16 operands with bf16 in and out).
 
 Conventions (the torch-harmonics "ortho" ones, so weights trained there carry over):
 
@@ -18,7 +18,11 @@ Conventions (the torch-harmonics "ortho" ones, so weights trained there carry ov
   C2R from ``mmax`` stored modes (``torch.fft.irfft(..., n=nlon, norm="forward")``).
 * defaults: ``lmax = nlat``, ``mmax = min(lmax, nlon // 2 + 1)``.
 
-Precision is fp32 (the tables are built in fp64 on the host and rounded once).
+Precision follows the input: fp32 (the tables are built in fp64 on the host and rounded once to fp32; the Legendre
+kernel runs the bf16x3 split, ~1e-6) or bf16 (the tables are ``bf16(fp32 table)``, the spectrum between the longitude
+FFT and ``legendre`` is bf16, the kernel multiplies the bf16 operands as they are with fp32 accumulation and rounds
+once at the store; a transform is good to about 3e-3 per field, bound 2e-2).  Complex bf16 does not exist, so bf16
+coefficients are always real tensors with a trailing re/im dim.
 """
 from __future__ import annotations
 
@@ -90,20 +94,27 @@ def legendre_tables(nlat: int, lmax: int, mmax: int, grid: str = "equiangular"):
 
 def legendre_split(table: torch.Tensor) -> torch.Tensor:
     """A Legendre table [M, R, Q] as the kernel reads it: zero-padded to [M, ceil16(R), ceil32(Q)] and split into
-    bf16 (hi, lo) planes -> [2, M, Rp, Qp] (``split_bf16(rows=False)``)."""
+    bf16 (hi, lo) planes -> [2, M, Rp, Qp] (``split_bf16(rows=False)``).  A bf16 table is its own single plane:
+    zero-padded -> [1, M, Rp, Qp]."""
     M, R, Q = table.shape
+    if table.dtype == torch.bfloat16:
+        return F.pad(table, (0, -Q % 32, 0, -R % 16)).contiguous().unsqueeze(0)
     tp = F.pad(table.float(), (0, -Q % 32, 0, -R % 16)).contiguous()
     return _ops().split_bf16(tp, False)
 
 
 class _Tables:
-    """The fp32 operands of one (grid, truncation) on one device: ``fwd`` [mmax, lmax, nlat] = w_k Pb,
-    ``inv`` [mmax, nlat, lmax] = Pb transposed, and on a GPU their split forms."""
+    """The operands of one (grid, truncation) on one device in one precision: ``fwd`` [mmax, lmax, nlat] = w_k Pb,
+    ``inv`` [mmax, nlat, lmax] = Pb transposed, and on a GPU their split forms.  ``like``: the fp32 tables to round
+    to bf16 (the bf16 operands are ``bf16(fp32 table)``)."""
 
-    def __init__(self, nlat, nlon, lmax, mmax, grid, device):
-        _, w, P = legendre_tables(nlat, lmax, mmax, grid)
-        self.fwd = torch.from_numpy(P * w[None, None, :]).float().contiguous().to(device)
-        self.inv = torch.from_numpy(np.ascontiguousarray(P.transpose(0, 2, 1))).float().to(device)
+    def __init__(self, nlat, nlon, lmax, mmax, grid, device, like: "Optional[_Tables]" = None):
+        if like is not None:
+            self.fwd, self.inv = like.fwd.to(torch.bfloat16), like.inv.to(torch.bfloat16)
+        else:
+            _, w, P = legendre_tables(nlat, lmax, mmax, grid)
+            self.fwd = torch.from_numpy(P * w[None, None, :]).float().contiguous().to(device)
+            self.inv = torch.from_numpy(np.ascontiguousarray(P.transpose(0, 2, 1))).float().to(device)
         cuda = torch.device(device).type == "cuda"
         self.fwd_split = legendre_split(self.fwd) if cuda else None
         self.inv_split = legendre_split(self.inv) if cuda else None
@@ -112,13 +123,21 @@ class _Tables:
 _CACHE: dict = {}
 
 
-def sht_tables(nlat: int, nlon: int, lmax: int, mmax: int, grid: str, device) -> _Tables:
-    """Tables cached per (nlat, nlon, lmax, mmax, grid, device); they live as long as the process, so a captured
-    hipGraph that reads them stays valid."""
+def sht_tables(nlat: int, nlon: int, lmax: int, mmax: int, grid: str, device,
+               dtype: torch.dtype = torch.float32) -> _Tables:
+    """Tables cached per (nlat, nlon, lmax, mmax, grid, device) and dtype (fp32 or bf16; the bf16 entry is the fp32
+    one rounded); they live as long as the process, so a captured hipGraph that reads them stays valid."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"sht_tables: dtype must be float32 or bfloat16, got {dtype}")
     key = (int(nlat), int(nlon), int(lmax), int(mmax), grid, str(torch.device(device)))
     t = _CACHE.get(key)
     if t is None:
         t = _CACHE[key] = _Tables(nlat, nlon, lmax, mmax, grid, device)
+    if dtype == torch.bfloat16:
+        key, t32 = key + (dtype,), t
+        t = _CACHE.get(key)
+        if t is None:
+            t = _CACHE[key] = _Tables(nlat, nlon, lmax, mmax, grid, device, like=t32)
     return t
 
 
@@ -134,31 +153,33 @@ def _defaults(nlat: int, nlon: int, lmax: Optional[int], mmax: Optional[int]) ->
 
 def sht(x: torch.Tensor, lmax: Optional[int] = None, mmax: Optional[int] = None,
         grid: str = "equiangular") -> torch.Tensor:
-    """Forward real SHT of ``x`` [..., nlat, nlon] (fp32) -> coefficients [..., lmax, mmax, 2] (trailing re/im).
+    """Forward real SHT of ``x`` [..., nlat, nlon] (fp32 or bf16) -> coefficients [..., lmax, mmax, 2] (trailing
+    re/im) of the same dtype.
 
     R2C along longitude keeping ``mmax`` modes, scaled by 2 pi / nlon, then the forward Legendre transform
     (``legendre`` with ``tri=1``: rows l < m are zero).  The same two ops run on CPU tensors (ATen kernels)."""
-    if x.dtype != torch.float32:
-        raise TypeError(f"sht: x must be float32, got {x.dtype}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"sht: x must be float32 or bfloat16, got {x.dtype}")
     nlat, nlon = int(x.shape[-2]), int(x.shape[-1])
     lmax, mmax = _defaults(nlat, nlon, lmax, mmax)
-    t = sht_tables(nlat, nlon, lmax, mmax, grid, x.device)
+    t = sht_tables(nlat, nlon, lmax, mmax, grid, x.device, x.dtype)
     ops = _ops()
-    xf = ops.r2c(x, [x.dim() - 1], 2.0 * math.pi / nlon, [mmax, 0], torch.float32)  # [..., nlat, mmax, 2]
+    xf = ops.r2c(x, [x.dim() - 1], 2.0 * math.pi / nlon, [mmax, 0], x.dtype)  # [..., nlat, mmax, 2]
     return ops.legendre(xf, t.fwd, t.fwd_split, 1)
 
 
 def isht(c: torch.Tensor, nlat: int, nlon: int, grid: str = "equiangular") -> torch.Tensor:
-    """Inverse real SHT of ``c`` [..., lmax, mmax, 2] (or complex [..., lmax, mmax]) -> [..., nlat, nlon] fp32.
+    """Inverse real SHT of ``c`` [..., lmax, mmax, 2] (fp32 or bf16; or complex64 [..., lmax, mmax]) ->
+    [..., nlat, nlon] of the same real dtype.
 
     The inverse Legendre transform (``legendre`` with ``tri=2``: columns l < m are zero), then an unnormalised C2R
     along longitude from the ``mmax`` stored modes."""
     c = _from_complex(c)
-    if c.dtype != torch.float32:
-        raise TypeError(f"isht: c must be float32 / complex64, got {c.dtype}")
+    if c.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"isht: c must be float32 / complex64 or bfloat16 (trailing re/im), got {c.dtype}")
     lmax, mmax = int(c.shape[-3]), int(c.shape[-2])
     _defaults(nlat, nlon, lmax, mmax)
-    t = sht_tables(nlat, nlon, lmax, mmax, grid, c.device)
+    t = sht_tables(nlat, nlon, lmax, mmax, grid, c.device, c.dtype)
     ops = _ops()
     xf = ops.legendre(c, t.inv, t.inv_split, 2)  # [..., nlat, mmax, 2]
-    return ops.c2r(xf, [xf.dim() - 2], [nlon], 1.0, [mmax, 0], torch.float32)
+    return ops.c2r(xf, [xf.dim() - 2], [nlon], 1.0, [mmax, 0], c.dtype)

@@ -505,14 +505,18 @@ def fno_spectral_mix(xm: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def sfno_mix_split(w: torch.Tensor) -> torch.Tensor:
     """SFNO weights ``w`` [Cin, Cout, L, 2] (fp32) as the ``sfno_mix`` kernel reads them: the real form repacked
     degree-major, W[l][o][2i] = Wr[i,o,l] and W[l][o][2i+1] = Wi[i,o,l], zero-padded and split into bf16 (hi, lo)
-    planes -> [2, L, ceil16(Cout), ceil32(2 Cin)].  Any device; as many bytes as ``w`` itself."""
-    return _ops().sfno_mix_split(w.detach().float())
+    planes -> [2, L, ceil16(Cout), ceil32(2 Cin)].  Any device; as many bytes as ``w`` itself.  bf16 weights give
+    the one plane of the same form, [1, L, ceil16(Cout), ceil32(2 Cin)] (what the bf16 ``sfno_mix`` reads); every other
+    dtype is taken as fp32."""
+    w = w.detach()
+    return _ops().sfno_mix_split(w if w.dtype == torch.bfloat16 else w.float())
 
 
 def sfno_mix(c: torch.Tensor, w: torch.Tensor, w_split: Optional[torch.Tensor] = None, tri: int = 0) -> torch.Tensor:
     """SFNO per-degree channel mixing y[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l] on complex-as-pair tensors
-    c [B, Cin, L, M, 2], w [Cin, Cout, L, 2] -> [B, Cout, L, M, 2] (fp32).  ``tri=1``: ``c`` is the spectrum of a real
-    field (zero where l < m); it is not read there and the result is exactly 0.0 there.  ``w_split``: the cached
-    :func:`sfno_mix_split` of ``w`` (built per call when absent).  Native op on every device (CPU: ATen einsum;
-    GPU: csrc/spectral/sfno_mix.hip, bf16x3 on MFMA)."""
+    c [B, Cin, L, M, 2], w [Cin, Cout, L, 2] -> [B, Cout, L, M, 2], all fp32 or all bf16.  ``tri=1``: ``c`` is the
+    spectrum of a real field (zero where l < m); it is not read there and the result is exactly 0.0 there.
+    ``w_split``: the cached :func:`sfno_mix_split` of ``w`` (built per call when absent).  Native op on every device
+    (CPU: ATen einsum; GPU: csrc/spectral/sfno_mix.hip on MFMA -- bf16x3 for fp32, the bf16 operands as they are with
+    fp32 accumulation and one rounding at the store for bf16)."""
     return _ops().sfno_mix(c, w, w_split, int(tri))
