@@ -8,6 +8,7 @@
 #include <c10/hip/HIPGraphsC10Utils.h>
 
 #include <atomic>
+#include <cstdint>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -69,6 +70,16 @@ inline bool present(const c10::optional<at::Tensor>& t) { return t.has_value() &
 // the tensor as contiguous fp32 (what the kernels read for bias, c1, stats and pre), undefined when absent
 inline at::Tensor f32_or_undef(const c10::optional<at::Tensor>& t) {
   return present(t) ? t->to(at::kFloat).contiguous() : at::Tensor();
+}
+
+// ---- 16-byte alignment of kernel inputs
+// The LayerNorm-fused W-transforms (afno_wfft.hip) and the LayerNorm kernels (layernorm.hip) move 8 or 16 bytes
+// per lane, and the former DMA 16-byte pieces of the residual tile and its statistics into LDS: every tensor they
+// read starts on a 16-byte boundary (a pointer test; allocations are, a contiguous view at an odd element offset
+// into a larger buffer is not and is copied).
+inline at::Tensor vec_aligned(const at::Tensor& x) {
+  if (!x.defined() || x.numel() == 0 || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0) return x;
+  return x.clone(at::MemoryFormat::Contiguous);
 }
 
 }  // namespace amd_dft

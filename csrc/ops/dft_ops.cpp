@@ -94,14 +94,6 @@ at::Tensor pair_aligned(const at::Tensor& x) {
   return x.clone(at::MemoryFormat::Contiguous);
 }
 
-// The LayerNorm-fused W-transforms (afno_wfft.hip) move 8 or 16 bytes per lane and DMA 16-byte pieces of the
-// residual tile and its statistics into LDS: every tensor they read starts on a 16-byte boundary (a pointer
-// test; allocations are, a contiguous view at an odd element offset is not and is copied).
-at::Tensor vec_aligned(const at::Tensor& x) {
-  if (x.numel() == 0 || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0) return x;
-  return x.clone(at::MemoryFormat::Contiguous);
-}
-
 int64_t lds_limit() {
   static const int64_t lim = max_lds_length();
   return lim;

@@ -438,7 +438,7 @@ at::Tensor split_bf16_cuda(const at::Tensor& x_, bool rows) {
   const c10::DeviceGuard guard(x_.device());
   TORCH_CHECK(x_.scalar_type() == at::kFloat, "amd_dft.split_bf16: x must be float32");
   TORCH_CHECK(x_.dim() >= 1, "amd_dft.split_bf16: x must have at least one dim");
-  at::Tensor x = x_.contiguous();
+  at::Tensor x = vec_aligned(x_.contiguous());
   const int64_t cols = x.size(-1);
   TORCH_CHECK(x.numel() % 8 == 0 && (!rows || cols % 32 == 0),
               "amd_dft.split_bf16: needs multiples of 8 elements (rows: a last dim that is a multiple of 32)");

@@ -922,38 +922,35 @@ std::string sfno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64
 // ------------------------------------------------------------------ LayerNorm (+ residual)
 std::tuple<at::Tensor, at::Tensor> layer_norm_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                   double eps, const std::optional<at::Tensor>& residual) {
-  at::Tensor xs = residual.has_value() ? (x.to(at::kFloat) + residual->to(at::kFloat)).to(x.scalar_type()) : x;
-  at::Tensor y = at::layer_norm(xs.to(at::kFloat), {x.size(-1)}, w.to(at::kFloat), b.to(at::kFloat), eps);
-  return {y.to(x.scalar_type()), xs};
+  // like the kernel: the fp32 sum is normalised, x_out is its rounding (LN of the rounded x_out would carry a
+  // 2^-9 |x + residual| error per element into y, far above one output rounding where |mean| >> std)
+  at::Tensor xf = present(residual) ? x.to(at::kFloat) + residual->to(at::kFloat) : x.to(at::kFloat);
+  at::Tensor y = at::layer_norm(xf, {x.size(-1)}, w.to(at::kFloat), b.to(at::kFloat), eps);
+  return {y.to(x.scalar_type()), present(residual) ? xf.to(x.scalar_type()) : x};
+}
+
+// The LayerNorm ops' per-channel arguments hold exactly C entries (the kernels read C of them with 16-byte loads)
+void check_channels(const char* op, int64_t C, const at::Tensor& w, const at::Tensor& b,
+                    const c10::optional<at::Tensor>& pre) {
+  TORCH_CHECK(w.numel() == C && b.numel() == C && (!present(pre) || pre->numel() == C), "amd_dft.", op,
+              ": weight/bias/pre must have C = ", C, " entries");
 }
 
 std::tuple<at::Tensor, at::Tensor> layer_norm_cuda(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,
                                                    double eps, const std::optional<at::Tensor>& residual) {
   const c10::DeviceGuard guard(x_.device());
-  if (x_.scalar_type() == at::kFloat && !residual.has_value() && x_.size(-1) % 4 == 0 && x_.size(-1) <= 2048) {
-    at::Tensor x = x_.contiguous();
-    at::Tensor w = w_.to(at::kFloat).contiguous(), b = b_.to(at::kFloat).contiguous();
-    at::Tensor y = at::empty_like(x);
-    LayerNormLaunch p;
-    p.x = x.data_ptr();
-    p.y = y.data_ptr();
-    p.gamma = w.data_ptr();
-    p.beta = b.data_ptr();
-    p.residual = nullptr;
-    p.resid_out = nullptr;
-    p.cols = static_cast<int>(x.size(-1));
-    p.rows = x.numel() / p.cols;
-    p.eps = static_cast<float>(eps);
-    p.bf16 = 0;
-    if (p.rows > 0) launch_layernorm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-    return {y, x};
-  }
-  if (x_.scalar_type() != at::kBFloat16 || x_.size(-1) % 8 != 0 || x_.size(-1) > 2048) {
+  const bool res = present(residual);
+  const int64_t C = x_.size(-1);
+  check_channels("layer_norm", C, w_, b_, c10::nullopt);
+  TORCH_CHECK(!res || residual->sizes() == x_.sizes(), "amd_dft.layer_norm: residual shape mismatch");
+  const bool f32 = x_.scalar_type() == at::kFloat, bf16 = x_.scalar_type() == at::kBFloat16;
+  if (!(f32 || bf16) || ln_route(res ? LnOp::LayerNormRes : LnOp::LayerNorm, C, bf16).kernel == LnKernel::None) {
     fallback_note("layer_norm", "dtype/shape outside the LayerNorm kernels");
     return layer_norm_cpu(x_, w_, b_, eps, residual);  // ATen ops on the device tensors
   }
-  at::Tensor x = x_.contiguous();
-  at::Tensor w = w_.to(at::kBFloat16).contiguous(), b = b_.to(at::kBFloat16).contiguous();
+  const at::ScalarType dt = x_.scalar_type();
+  at::Tensor x = vec_aligned(x_.contiguous());
+  at::Tensor w = vec_aligned(w_.to(dt).contiguous()), b = vec_aligned(b_.to(dt).contiguous());
   at::Tensor y = at::empty_like(x);
   at::Tensor xs = x;
   LayerNormLaunch p;
@@ -964,17 +961,16 @@ std::tuple<at::Tensor, at::Tensor> layer_norm_cuda(const at::Tensor& x_, const a
   p.residual = nullptr;
   p.resid_out = nullptr;
   at::Tensor r;
-  if (residual.has_value()) {
-    r = residual->to(at::kBFloat16).contiguous();
-    TORCH_CHECK(r.sizes() == x.sizes(), "layer_norm: residual shape mismatch");
+  if (res) {
+    r = vec_aligned(residual->to(at::kBFloat16).contiguous());
     xs = at::empty_like(x);
     p.residual = r.data_ptr();
     p.resid_out = xs.data_ptr();
   }
-  p.cols = static_cast<int>(x.size(-1));
+  p.cols = static_cast<int>(C);
   p.rows = x.numel() / p.cols;
   p.eps = static_cast<float>(eps);
-  p.bf16 = 1;
+  p.bf16 = bf16 ? 1 : 0;
   if (p.rows > 0) launch_layernorm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
   return {y, xs};
 }
@@ -989,7 +985,7 @@ std::tuple<at::Tensor, at::Tensor> layer_norm_meta(const at::Tensor& x, const at
 at::Tensor layer_norm_split_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b, double eps,
                                 const std::optional<at::Tensor>& pre) {
   at::Tensor xf = x.to(at::kFloat);
-  if (pre.has_value()) xf = xf + pre->to(at::kFloat);
+  if (present(pre)) xf = xf + pre->to(at::kFloat);
   at::Tensor y = at::layer_norm(xf, {x.size(-1)}, w.to(at::kFloat), b.to(at::kFloat), eps);
   at::Tensor hi = y.to(at::kBFloat16);
   at::Tensor lo = (y - hi.to(at::kFloat)).to(at::kBFloat16);
@@ -1005,13 +1001,12 @@ at::Tensor layer_norm_split_cuda(const at::Tensor& x_, const at::Tensor& w_, con
                                  const std::optional<at::Tensor>& pre_) {
   const c10::DeviceGuard guard(x_.device());
   const int64_t C = x_.size(-1);
-  TORCH_CHECK(x_.scalar_type() == at::kFloat && C % 32 == 0 && C <= 2048,
+  TORCH_CHECK(x_.scalar_type() == at::kFloat && ln_route(LnOp::LayerNormSplit, C, false).kernel != LnKernel::None,
               "amd_dft.layer_norm_split: x must be float32 with C % 32 == 0 and C <= 2048");
-  TORCH_CHECK(w_.numel() == C && b_.numel() == C && (!pre_.has_value() || pre_->numel() == C),
-              "amd_dft.layer_norm_split: weight/bias/pre must have C entries");
-  at::Tensor x = x_.contiguous();
-  at::Tensor w = w_.to(at::kFloat).contiguous(), b = b_.to(at::kFloat).contiguous(), pre;
-  if (pre_.has_value()) pre = pre_->to(at::kFloat).contiguous();
+  check_channels("layer_norm_split", C, w_, b_, pre_);
+  at::Tensor x = vec_aligned(x_.contiguous());
+  at::Tensor w = vec_aligned(w_.to(at::kFloat).contiguous()), b = vec_aligned(b_.to(at::kFloat).contiguous());
+  at::Tensor pre = vec_aligned(f32_or_undef(pre_));
   std::vector<int64_t> os(x.sizes().begin(), x.sizes().end());
   os.back() = 2 * C;
   at::Tensor y = at::empty(os, x.options().dtype(at::kBFloat16));
@@ -1043,31 +1038,33 @@ at::Tensor layer_norm_split_meta(const at::Tensor& x, const at::Tensor&, const a
 // (mean, rstd) per row of x' = x + pre: the AFNO W-transforms apply LN(x') on load.
 at::Tensor ln_stats_cpu(const at::Tensor& x, const std::optional<at::Tensor>& pre, double eps) {
   at::Tensor xp = x.to(at::kFloat);
-  if (pre.has_value()) xp = xp + pre->to(at::kFloat);
+  if (present(pre)) xp = xp + pre->to(at::kFloat);
   xp = xp.reshape({-1, x.size(-1)});
-  auto vm = at::var_mean(xp, {1}, /*correction=*/0, /*keepdim=*/false);
-  return at::stack({std::get<1>(vm), at::rsqrt(std::get<0>(vm) + eps)}, 1).contiguous();
+  // two passes like the kernels (mean, then the centred sum of squares): an error of the mean cancels in the
+  // variance to first order.  at::var_mean on the device came out 2.3x over the kernels' error model at 6 channels
+  // (tests/test_layernorm.py, rows with |mean| / std up to 100).
+  at::Tensor mean = xp.mean({1}, /*keepdim=*/true);
+  at::Tensor d = xp - mean;
+  at::Tensor var = (d * d).mean({1});
+  return at::stack({mean.squeeze(1), at::rsqrt(var + eps)}, 1).contiguous();
 }
 
 at::Tensor ln_stats_cuda(const at::Tensor& x_, const std::optional<at::Tensor>& pre_, double eps) {
   const c10::DeviceGuard guard(x_.device());
   const int64_t C = x_.size(-1);
-  const bool f32 = x_.scalar_type() == at::kFloat && C % 4 == 0 && C <= 2048;
-  if (!f32 && (x_.scalar_type() != at::kBFloat16 || C % 8 != 0 || C > 2048)) {
+  TORCH_CHECK(!present(pre_) || pre_->numel() == C, "amd_dft.ln_stats: pre must have one entry per channel");
+  const bool f32 = x_.scalar_type() == at::kFloat && ln_route(LnOp::LnStats, C, false).kernel != LnKernel::None;
+  if (!f32 && (x_.scalar_type() != at::kBFloat16 || ln_route(LnOp::LnStats, C, true).kernel == LnKernel::None)) {
     fallback_note("ln_stats", "dtype/shape outside the LayerNorm kernels");
     return ln_stats_cpu(x_, pre_, eps);
   }
-  at::Tensor x = x_.contiguous();
-  at::Tensor pre;
-  if (pre_.has_value()) {
-    pre = pre_->to(at::kFloat).contiguous();
-    TORCH_CHECK(pre.numel() == C, "amd_dft.ln_stats: pre must have one entry per channel");
-  }
+  at::Tensor x = vec_aligned(x_.contiguous());
+  at::Tensor pre = vec_aligned(f32_or_undef(pre_));
   const int64_t rows = x.numel() / C;
   at::Tensor st = at::empty({rows, 2}, x.options().dtype(at::kFloat));
   LnStatsLaunch p;
   p.x = x.data_ptr();
-  p.pre = pre_.has_value() ? pre.data_ptr<float>() : nullptr;
+  p.pre = pre.defined() ? pre.data_ptr<float>() : nullptr;
   p.stats = st.data_ptr<float>();
   p.rows = rows;
   p.cols = static_cast<int>(C);
@@ -1086,7 +1083,7 @@ at::Tensor ln_stats_meta(const at::Tensor& x, const std::optional<at::Tensor>&, 
 // centred on that offset, e.g. c2r_ln_add_split's pairs)
 static void check_merge_shift(const at::Tensor& part, const std::optional<at::Tensor>& shift) {
   TORCH_CHECK(part.dim() == 3 && part.size(2) == 2, "amd_dft.ln_stats_merge: part must be [rows, chunks, 2]");
-  if (shift) {
+  if (present(shift)) {
     TORCH_CHECK(shift->numel() == part.size(0) * 2 && shift->size(-1) == 2 && shift->device() == part.device(),
                 "amd_dft.ln_stats_merge: shift must hold [rows, 2] on the device of part");
   }
@@ -1098,7 +1095,7 @@ at::Tensor ln_stats_merge_cpu(const at::Tensor& part, double eps, const std::opt
   at::Tensor m = p.select(2, 0), q = p.select(2, 1);
   at::Tensor mean = m.mean(1);
   at::Tensor m2 = q.sum(1) + 64.0 * (m - mean.unsqueeze(1)).pow(2).sum(1);
-  if (shift) mean = mean - shift->reshape({-1, 2}).select(1, 0).to(at::kFloat);
+  if (present(shift)) mean = mean - shift->reshape({-1, 2}).select(1, 0).to(at::kFloat);
   return at::stack({mean, at::rsqrt(m2 / (64.0 * p.size(1)) + eps)}, 1).contiguous();
 }
 
@@ -1106,8 +1103,8 @@ at::Tensor ln_stats_merge_cuda(const at::Tensor& part_, double eps, const std::o
   const c10::DeviceGuard guard(part_.device());
   check_merge_shift(part_, shift_);
   TORCH_CHECK(part_.scalar_type() == at::kFloat, "amd_dft.ln_stats_merge: part must be fp32 [rows, chunks, 2]");
-  at::Tensor part = part_.contiguous();
-  at::Tensor shift = shift_ ? shift_->to(at::kFloat).contiguous() : at::Tensor();
+  at::Tensor part = vec_aligned(part_.contiguous());
+  at::Tensor shift = vec_aligned(f32_or_undef(shift_));  // read as float2: 8 bytes would do, the one helper serves
   at::Tensor st = at::empty({part.size(0), 2}, part.options());
   launch_ln_stats_merge(part.data_ptr<float>(), st.data_ptr<float>(), part.size(0), static_cast<int>(part.size(1)), 64,
                         static_cast<float>(eps), c10::hip::getCurrentHIPStream(part.device().index()).stream(),
@@ -1117,6 +1114,27 @@ at::Tensor ln_stats_merge_cuda(const at::Tensor& part_, double eps, const std::o
 
 at::Tensor ln_stats_merge_meta(const at::Tensor& part, double, const std::optional<at::Tensor>&) {
   return at::empty({part.size(0), 2}, part.options());
+}
+
+// The kernel of layernorm.hip a 16-byte-aligned device call of a LayerNorm op takes at channel count C -- host
+// only, no device (the companion of afno_w_info).  op: layer_norm, layer_norm_res (layer_norm with a residual),
+// ln_stats or layer_norm_split; bf16: the dtype of x (else fp32).  "ln_bf16<4>", "ln_bf16_res<1>", "ln_stats<2>",
+// "ln_stats_768", "ln_f32<8>", "ln_f32_stats<3>", "ln_f32_split<2>", "ln_split_lds<3>": kernel<16-byte chunks per
+// lane>; "fallback" where the op routes to ATen, "error" where it raises.  Answers from ln_route(), which the
+// wrappers above and the launchers dispatch on.  The shipped route only: the duplicated-load split kernel
+// (ln_split_kernel, MI_DFT_LN_SPLIT=dup) exists in AMD_DFT_TUNING builds alone, its switch is latched on first use
+// in the process, and it is neither reported here nor covered by tests/test_layernorm.py.
+std::string ln_info(std::string op, int64_t C, bool bf16) {
+  const bool split = op == "layer_norm_split";
+  TORCH_CHECK(op == "layer_norm" || op == "layer_norm_res" || op == "ln_stats" || split,
+              "amd_dft.ln_info: op must be layer_norm, layer_norm_res, ln_stats or layer_norm_split");
+  TORCH_CHECK(C >= 1, "amd_dft.ln_info: C must be >= 1");
+  const LnOp o = split ? LnOp::LayerNormSplit : op == "ln_stats" ? LnOp::LnStats
+                 : op == "layer_norm_res" ? LnOp::LayerNormRes : LnOp::LayerNorm;
+  const LnRoute r = ln_route(o, C, bf16);
+  if (r.kernel == LnKernel::None) return split ? "error" : "fallback";
+  const std::string name = ln_kernel_name(r.kernel);
+  return r.kernel == LnKernel::Stats768 ? name : name + "<" + std::to_string(r.nch) + ">";
 }
 
 at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -1138,6 +1156,7 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("ln_stats(Tensor x, Tensor? pre=None, float eps=1e-6) -> Tensor");
   m.def("ln_stats_merge(Tensor part, float eps=1e-6, Tensor? shift=None) -> Tensor");
   m.def("layer_norm_split(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? pre=None) -> Tensor");
+  m.def("ln_info(str op, int C, bool bf16) -> str", &amd_dft::ln_info);
   m.def("fno_mix(Tensor x, Tensor w, int path=0) -> Tensor");
   m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
   m.def("fno_pointwise_out(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");

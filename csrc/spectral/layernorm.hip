@@ -436,16 +436,15 @@ __global__ void __launch_bounds__(64 * kWaves) ln_split_lds_kernel(const float* 
 
 template <bool STATS, bool SPLIT>
 void launch_f32(const float* x, const float* pre, const float* g, const float* b, void* y, float2* st, int64_t rows,
-                int cols, float eps, hipStream_t s) {
+                int cols, float eps, int nch, hipStream_t s) {
   const dim3 grid(static_cast<uint32_t>((rows + kWaves - 1) / kWaves)), blk(64 * kWaves);
-  const int nch = (cols / 4 + 63) / 64;
 #define AMD_DFT_LNF(N)                                                                                       \
   if (pre) hipLaunchKernelGGL((ln_f32_kernel<N, STATS, SPLIT, true>), grid, blk, 0, s, x, pre, g, b, y, st, rows, cols, eps); \
   else hipLaunchKernelGGL((ln_f32_kernel<N, STATS, SPLIT, false>), grid, blk, 0, s, x, pre, g, b, y, st, rows, cols, eps);
-  if (nch <= 1) { AMD_DFT_LNF(1) }
+  if (nch == 1) { AMD_DFT_LNF(1) }
   else if (nch == 2) { AMD_DFT_LNF(2) }
   else if (nch == 3) { AMD_DFT_LNF(3) }
-  else if (nch <= 4) { AMD_DFT_LNF(4) }
+  else if (nch == 4) { AMD_DFT_LNF(4) }
   else { AMD_DFT_LNF(8) }
 #undef AMD_DFT_LNF
 }
@@ -476,6 +475,50 @@ __global__ void __launch_bounds__(256) split_bf16_kernel(const float* __restrict
 }
 
 }  // namespace
+
+// Width -> kernel instance, the one table behind every launcher below and the ln_info op.  bf16 rows hold
+// cols / 8 chunks of 16 bytes, fp32 rows cols / 4; a wave covers 64 chunks per step, so an instance needs
+// NCH >= ceil(chunks / 64).  Compiled: bf16 NCH 1, 2, 4; fp32 NCH 1, 2, 3, 4, 8.  Two widths have a kernel of
+// their own: bf16 statistics at 768 (two rows per wave) and the fp32 split output at 768 (pair row staged in LDS).
+// (MI_DFT_LN_SPLIT=dup swaps the latter for ln_split_kernel in AMD_DFT_TUNING builds only; the switch is
+// latched on first use and is not part of the shipped route, so the table does not know it.)
+LnRoute ln_route(LnOp op, int64_t cols, bool bf16) {
+  LnRoute r;
+  if (op == LnOp::LayerNormSplit) {
+    if (bf16 || cols % 32 != 0 || cols > 64 * 4 * 8) return r;
+  } else if (bf16) {
+    if (cols % 8 != 0 || cols > 64 * 8 * 4) return r;
+  } else {
+    if (op == LnOp::LayerNormRes || cols % 4 != 0 || cols > 64 * 4 * 8) return r;
+  }
+  if (bf16) {
+    const int nch = static_cast<int>((cols / 8 + 63) / 64);
+    r.nch = nch <= 1 ? 1 : nch == 2 ? 2 : 4;
+    r.kernel = op == LnOp::LnStats ? LnKernel::Stats : op == LnOp::LayerNormRes ? LnKernel::Bf16Res : LnKernel::Bf16;
+    if (op == LnOp::LnStats && cols == 768) r = {LnKernel::Stats768, 3};
+    return r;
+  }
+  const int nch = static_cast<int>((cols / 4 + 63) / 64);
+  r.nch = nch <= 1 ? 1 : nch == 2 ? 2 : nch == 3 ? 3 : nch <= 4 ? 4 : 8;
+  r.kernel = op == LnOp::LnStats ? LnKernel::F32Stats : op == LnOp::LayerNormSplit ? LnKernel::F32Split : LnKernel::F32;
+  if (op == LnOp::LayerNormSplit && cols == 768) r = {LnKernel::SplitLds, 3};
+  return r;
+}
+
+const char* ln_kernel_name(LnKernel k) {
+  switch (k) {
+    case LnKernel::Bf16: return "ln_bf16";
+    case LnKernel::Bf16Res: return "ln_bf16_res";
+    case LnKernel::Stats: return "ln_stats";
+    case LnKernel::Stats768: return "ln_stats_768";
+    case LnKernel::F32: return "ln_f32";
+    case LnKernel::F32Stats: return "ln_f32_stats";
+    case LnKernel::F32Split: return "ln_f32_split";
+    case LnKernel::SplitLds: return "ln_split_lds";
+    case LnKernel::None: break;
+  }
+  return "none";
+}
 
 // (mean, rstd) per row from per-chunk partials (mean_c, M2_c) of equal chunk width W (Chan et al.:
 // mean = avg mean_c, M2 = sum M2_c + W sum (mean_c - mean)^2): the statistics the fp32 fc2 GEMM
@@ -551,20 +594,21 @@ void launch_ln_stats_merge(const float* part, float* stats, int64_t rows, int nc
 }
 
 void launch_ln_stats(const LnStatsLaunch& p, void* stream) {
+  const LnRoute route = ln_route(LnOp::LnStats, p.cols, !p.f32);
   if (p.f32) {
-    if (p.cols % 4 != 0 || p.cols > 64 * 4 * 8) throw std::runtime_error("amd_dft: ln_stats: fp32 rows need cols % 4 == 0, <= 2048");
+    if (route.kernel == LnKernel::None) throw std::runtime_error("amd_dft: ln_stats: fp32 rows need cols % 4 == 0, <= 2048");
     launch_f32<true, false>(static_cast<const float*>(p.x), p.pre, nullptr, nullptr, nullptr,
-                            reinterpret_cast<float2*>(p.stats), p.rows, p.cols, p.eps, static_cast<hipStream_t>(stream));
+                            reinterpret_cast<float2*>(p.stats), p.rows, p.cols, p.eps, route.nch,
+                            static_cast<hipStream_t>(stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: ln_stats launch: ") + hipGetErrorString(e));
     return;
   }
-  if (p.cols % 8 != 0 || p.cols > 64 * 8 * 4)
+  if (route.kernel == LnKernel::None)
     throw std::runtime_error("amd_dft: ln_stats kernel supports bf16 rows with cols % 8 == 0 and cols <= 2048");
   if (p.rows > static_cast<int64_t>(0x7fffffff) * kWaves) throw std::runtime_error("amd_dft: ln_stats: too many rows");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nch = (p.cols / 8 + 63) / 64;
-  if (p.cols == 768) {
+  if (route.kernel == LnKernel::Stats768) {
     const dim3 grid(static_cast<uint32_t>((p.rows + 2 * kWaves - 1) / (2 * kWaves)));
     const auto* x = static_cast<const uint16_t*>(p.x);
     auto* o = reinterpret_cast<float2*>(p.stats);
@@ -572,8 +616,8 @@ void launch_ln_stats(const LnStatsLaunch& p, void* stream) {
       hipLaunchKernelGGL((ln_stats_768_kernel<true>), grid, dim3(64 * kWaves), 0, st, x, p.pre, o, p.rows, p.eps);
     else
       hipLaunchKernelGGL((ln_stats_768_kernel<false>), grid, dim3(64 * kWaves), 0, st, x, nullptr, o, p.rows, p.eps);
-  } else if (nch <= 1) launch_stats_n<1>(p, st);
-  else if (nch == 2) launch_stats_n<2>(p, st);
+  } else if (route.nch == 1) launch_stats_n<1>(p, st);
+  else if (route.nch == 2) launch_stats_n<2>(p, st);
   else launch_stats_n<4>(p, st);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: ln_stats launch: ") + hipGetErrorString(e));
@@ -581,13 +625,15 @@ void launch_ln_stats(const LnStatsLaunch& p, void* stream) {
 
 void launch_layernorm(const LayerNormLaunch& p, void* stream) {
   if (!p.bf16) {
-    if (p.residual || p.cols % 4 != 0 || p.cols > 64 * 4 * 8)
+    if (ln_route(p.residual ? LnOp::LayerNormRes : LnOp::LayerNorm, p.cols, false).kernel == LnKernel::None)
       throw std::runtime_error("amd_dft: layernorm: fp32 rows need cols % 4 == 0, <= 2048, no residual");
-    if (p.split_out && p.cols % 32 != 0) throw std::runtime_error("amd_dft: layernorm: split output needs cols % 32 == 0");
+    const LnRoute route = ln_route(p.split_out ? LnOp::LayerNormSplit : LnOp::LayerNorm, p.cols, false);
+    if (route.kernel == LnKernel::None) throw std::runtime_error("amd_dft: layernorm: split output needs cols % 32 == 0");
     const auto* x = static_cast<const float*>(p.x);
     const auto* g = static_cast<const float*>(p.gamma);
     const auto* b = static_cast<const float*>(p.beta);
-    if (p.split_out && p.cols == 768 && p.rows <= static_cast<int64_t>(0x7fffffff) * kWaves) {
+    // (a row count past the LDS kernel's 32-bit grid takes the general split instance of the same width)
+    if (route.kernel == LnKernel::SplitLds && p.rows <= static_cast<int64_t>(0x7fffffff) * kWaves) {
       const dim3 grid(static_cast<uint32_t>((p.rows + kWaves - 1) / kWaves)), blk(64 * kWaves);
       auto* y = static_cast<uint16_t*>(p.y);
       hipStream_t s = static_cast<hipStream_t>(stream);
@@ -603,20 +649,22 @@ void launch_layernorm(const LayerNormLaunch& p, void* stream) {
         else hipLaunchKernelGGL((ln_split_lds_kernel<3, false>), grid, blk, 0, s, x, nullptr, g, b, y, p.rows, p.eps);
       }
     } else if (p.split_out) {
-      launch_f32<false, true>(x, p.pre, g, b, p.y, nullptr, p.rows, p.cols, p.eps, static_cast<hipStream_t>(stream));
+      launch_f32<false, true>(x, p.pre, g, b, p.y, nullptr, p.rows, p.cols, p.eps, route.nch,
+                              static_cast<hipStream_t>(stream));
     }
-    else launch_f32<false, false>(x, p.pre, g, b, p.y, nullptr, p.rows, p.cols, p.eps, static_cast<hipStream_t>(stream));
+    else launch_f32<false, false>(x, p.pre, g, b, p.y, nullptr, p.rows, p.cols, p.eps, route.nch,
+                                  static_cast<hipStream_t>(stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: layernorm launch: ") + hipGetErrorString(e));
     return;
   }
-  if (!p.bf16 || p.cols % 8 != 0 || p.cols > 64 * 8 * 4)
+  const LnRoute route = ln_route(p.residual ? LnOp::LayerNormRes : LnOp::LayerNorm, p.cols, true);
+  if (route.kernel == LnKernel::None)
     throw std::runtime_error("amd_dft: layernorm kernel supports bf16 rows with cols % 8 == 0 and cols <= 2048");
   if (p.rows > static_cast<int64_t>(0x7fffffff) * kWaves) throw std::runtime_error("amd_dft: layernorm: too many rows");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nch = (p.cols / 8 + 63) / 64;
-  if (nch <= 1) launch_bf16<1>(p, st);
-  else if (nch == 2) launch_bf16<2>(p, st);
+  if (route.nch == 1) launch_bf16<1>(p, st);
+  else if (route.nch == 2) launch_bf16<2>(p, st);
   else launch_bf16<4>(p, st);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: layernorm launch: ") + hipGetErrorString(e));

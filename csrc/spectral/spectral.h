@@ -277,6 +277,19 @@ struct LayerNormLaunch {
 };
 void launch_layernorm(const LayerNormLaunch& p, void* stream);
 
+// The kernel of layernorm.hip a launch runs for a row width (host only; the launchers and the ln_info op both ask
+// here).  nch = the instance's 16-byte chunks per lane (Stats768, SplitLds: 3 by construction).  None: no kernel
+// takes the width (bf16 rows need cols % 8 == 0, fp32 rows cols % 4 == 0, split rows cols % 32 == 0, all <= 2048;
+// a residual needs bf16) and the launchers throw.
+enum class LnOp { LayerNorm, LayerNormRes, LnStats, LayerNormSplit };
+enum class LnKernel { None, Bf16, Bf16Res, Stats, Stats768, F32, F32Stats, F32Split, SplitLds };
+struct LnRoute {
+  LnKernel kernel = LnKernel::None;
+  int nch = 0;
+};
+LnRoute ln_route(LnOp op, int64_t cols, bool bf16);
+const char* ln_kernel_name(LnKernel k);
+
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {
   const void* x = nullptr;        // [O, L, C] bf16 (fp32 if f32) stored residual stream
