@@ -919,6 +919,153 @@ std::string sfno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64
          " grid=" + std::to_string(r.grid) + " tri=" + std::to_string(tri) + (bf16 ? " bf16=1" : "");
 }
 
+// ------------------------------------------------------------------ instance normalisation (NCHW planes)
+// x [B, C, *spatial] fp32 / bf16, weight / bias [C] (fp32 or x's dtype, either may be absent):
+//   y = (x - mean) * rsqrt(var + eps) * weight[c] + bias[c], biased variance over the P = prod(spatial) elements of
+// each (b, c) plane -- nn.InstanceNorm2d without running statistics.  The result has x's dtype.
+struct InDims {
+  int64_t B, C, P;
+};
+InDims check_instance_norm(const char* op, const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                           const c10::optional<at::Tensor>& b) {
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, op,
+              ": x must be float32 or bfloat16, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 3, op, ": x must be [B, C, *spatial] with at least one spatial dimension, got ", x.sizes());
+  InDims d{x.size(0), x.size(1), 1};
+  for (int64_t i = 2; i < x.dim(); ++i) d.P *= x.size(i);
+  TORCH_CHECK(d.C >= 1, op, ": x has no channels");
+  TORCH_CHECK(d.P >= 2, op, ": expected more than 1 spatial element per channel, got input of size ", x.sizes());
+  TORCH_CHECK(d.P < (int64_t(1) << 31) && d.C < (int64_t(1) << 31), op, ": tensor too large");
+  auto per_channel = [&](const c10::optional<at::Tensor>& t, const char* name) {
+    if (!present(t)) return;
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == d.C, op, ": ", name, " must be [C] = [", d.C, "], got ", t->sizes());
+    TORCH_CHECK(t->scalar_type() == at::kFloat || t->scalar_type() == x.scalar_type(), op, ": ", name,
+                " must be float32 or ", x.scalar_type(), ", got ", t->scalar_type());
+    TORCH_CHECK(t->device() == x.device(), op, ": ", name, " must be on the device of x");
+  };
+  per_channel(w, "weight");
+  per_channel(b, "bias");
+  return d;
+}
+
+// CPU: fp64 ATen math on the fp32 / bf16 values, one rounding to x's dtype
+std::tuple<at::Tensor, at::Tensor, at::Tensor> instance_norm_moments_cpu(const at::Tensor& x, const InDims& d,
+                                                                         double eps) {
+  at::Tensor xd = x.to(at::kDouble).reshape({d.B, d.C, d.P});
+  at::Tensor mean = xd.mean({-1}, /*keepdim=*/true);
+  at::Tensor xc = xd - mean;
+  at::Tensor rstd = at::rsqrt((xc * xc).mean({-1}, /*keepdim=*/true) + eps);
+  return {xc, mean, rstd};
+}
+
+at::Tensor instance_norm_cpu(const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                             const c10::optional<at::Tensor>& b, double eps) {
+  const InDims d = check_instance_norm("instance_norm", x, w, b);
+  if (x.numel() == 0) return at::empty_like(x, at::MemoryFormat::Contiguous);
+  auto [xc, mean, rstd] = instance_norm_moments_cpu(x, d, eps);
+  at::Tensor y = xc * rstd;
+  if (present(w)) y = y * w->to(at::kDouble).reshape({1, d.C, 1});
+  if (present(b)) y = y + b->to(at::kDouble).reshape({1, d.C, 1});
+  return y.reshape(x.sizes()).to(x.scalar_type());
+}
+
+at::Tensor& instance_norm_out_cpu(const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                                  const c10::optional<at::Tensor>& b, double eps, at::Tensor& out) {
+  check_instance_norm("instance_norm_out", x, w, b);
+  check_out(out, x.sizes(), x, "instance_norm_out");
+  out.copy_(instance_norm_cpu(x, w, b, eps));
+  return out;
+}
+
+at::Tensor instance_norm_stats_cpu(const at::Tensor& x, double eps) {
+  const InDims d = check_instance_norm("instance_norm_stats", x, c10::nullopt, c10::nullopt);
+  if (x.numel() == 0) return at::empty({d.B, d.C, 2}, x.options().dtype(at::kFloat));
+  auto [xc, mean, rstd] = instance_norm_moments_cpu(x, d, eps);
+  return at::cat({mean, rstd}, -1).to(at::kFloat);
+}
+
+// the launch path of the three device ops: y (contiguous, 16-byte aligned, x's dtype) or stats ([B, C, 2] fp32)
+void instance_norm_run(const InDims& d, const at::Tensor& x_, const c10::optional<at::Tensor>& w,
+                       const c10::optional<at::Tensor>& b, double eps, const at::Tensor& y, const at::Tensor& stats) {
+  if (x_.numel() == 0) return;
+  // 16-byte vectors between the peeled ends of every plane: a view at an odd element offset gets its own copy
+  at::Tensor x = vec_aligned(x_.contiguous());
+  at::Tensor wf = f32_or_undef(w), bf = f32_or_undef(b);
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  const InstanceNormRoute r = instance_norm_route(d.B * d.C, d.P, bf16);
+  at::Tensor part;
+  if (!r.resident) part = at::empty({d.B * d.C, r.S, 4}, x.options().dtype(at::kFloat));
+  InstanceNormLaunch p;
+  p.x = x.data_ptr();
+  p.y = y.defined() ? y.data_ptr() : nullptr;
+  p.w = wf.defined() ? wf.data_ptr<float>() : nullptr;
+  p.b = bf.defined() ? bf.data_ptr<float>() : nullptr;
+  p.stats = stats.defined() ? stats.data_ptr<float>() : nullptr;
+  p.part = part.defined() ? part.data_ptr<float>() : nullptr;
+  p.planes = d.B * d.C;
+  p.P = d.P;
+  p.C = static_cast<int>(d.C);
+  p.eps = static_cast<float>(eps);
+  p.bf16 = bf16 ? 1 : 0;
+  launch_instance_norm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+}
+
+at::Tensor instance_norm_cuda(const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                              const c10::optional<at::Tensor>& b, double eps) {
+  const InDims d = check_instance_norm("instance_norm", x, w, b);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(x.sizes(), x.options());
+  instance_norm_run(d, x, w, b, eps, y, at::Tensor());
+  return checked(y, "instance_norm");
+}
+
+at::Tensor& instance_norm_out_cuda(const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                                   const c10::optional<at::Tensor>& b, double eps, at::Tensor& out) {
+  const InDims d = check_instance_norm("instance_norm_out", x, w, b);
+  check_out(out, x.sizes(), x, "instance_norm_out");
+  check_out_aligned(out, 16, "instance_norm_out");
+  const c10::DeviceGuard guard(x.device());
+  instance_norm_run(d, x, w, b, eps, out, at::Tensor());
+  checked(out, "instance_norm_out");
+  return out;
+}
+
+at::Tensor instance_norm_stats_cuda(const at::Tensor& x, double eps) {
+  const InDims d = check_instance_norm("instance_norm_stats", x, c10::nullopt, c10::nullopt);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor st = at::empty({d.B, d.C, 2}, x.options().dtype(at::kFloat));
+  instance_norm_run(d, x, c10::nullopt, c10::nullopt, eps, at::Tensor(), st);
+  return checked(st, "instance_norm_stats");
+}
+
+at::Tensor instance_norm_meta(const at::Tensor& x, const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
+                              double) {
+  return at::empty(x.sizes(), x.options());
+}
+
+at::Tensor& instance_norm_out_meta(const at::Tensor&, const c10::optional<at::Tensor>&,
+                                   const c10::optional<at::Tensor>&, double, at::Tensor& out) {
+  return out;
+}
+
+at::Tensor instance_norm_stats_meta(const at::Tensor& x, double) {
+  TORCH_CHECK(x.dim() >= 3, "instance_norm_stats: x must be [B, C, *spatial]");
+  return at::empty({x.size(0), x.size(1), 2}, x.options().dtype(at::kFloat));
+}
+
+// The route instance_norm runs for planes = B C planes of P elements -- host only, no device (the companion of
+// ln_info): "route=resident S=1 chunk=4050 vec=4 lds=16472 wgs=20" or "route=split S=64 chunk=16256 vec=4 lds=65296
+// wgs=1280".  chunk: elements per workgroup (the last chunk of a plane may be shorter); lds: dynamic LDS bytes of
+// the kernel that holds the data (the split route's normalising kernel takes 16).
+std::string instance_norm_info(int64_t planes, int64_t P, bool bf16) {
+  TORCH_CHECK(planes >= 1 && P >= 2 && P < (int64_t(1) << 31) && planes < (int64_t(1) << 31),
+              "amd_dft.instance_norm_info: planes must be >= 1 and 2 <= P < 2^31");
+  const InstanceNormRoute r = instance_norm_route(planes, P, bf16);
+  return std::string("route=") + (r.resident ? "resident" : "split") + " S=" + std::to_string(r.S) +
+         " chunk=" + std::to_string(r.chunk) + " vec=" + std::to_string(r.vec) + " lds=" + std::to_string(r.lds) +
+         " wgs=" + std::to_string(r.wgs);
+}
+
 // ------------------------------------------------------------------ LayerNorm (+ residual)
 std::tuple<at::Tensor, at::Tensor> layer_norm_cpu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                   double eps, const std::optional<at::Tensor>& residual) {
@@ -1157,6 +1304,10 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("ln_stats_merge(Tensor part, float eps=1e-6, Tensor? shift=None) -> Tensor");
   m.def("layer_norm_split(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? pre=None) -> Tensor");
   m.def("ln_info(str op, int C, bool bf16) -> str", &amd_dft::ln_info);
+  m.def("instance_norm(Tensor x, Tensor? weight=None, Tensor? bias=None, float eps=1e-5) -> Tensor");
+  m.def("instance_norm_out(Tensor x, Tensor? weight, Tensor? bias, float eps, Tensor(a!) out) -> Tensor(a!)");
+  m.def("instance_norm_stats(Tensor x, float eps=1e-5) -> Tensor");
+  m.def("instance_norm_info(int planes, int P, bool bf16) -> str", &amd_dft::instance_norm_info);
   m.def("fno_mix(Tensor x, Tensor w, int path=0) -> Tensor");
   m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
   m.def("fno_pointwise_out(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");
@@ -1183,6 +1334,9 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("ln_stats", AMD_DFT_TRACED("amd_dft::ln_stats", amd_dft::ln_stats_cuda));
   m.impl("ln_stats_merge", AMD_DFT_TRACED("amd_dft::ln_stats_merge", amd_dft::ln_stats_merge_cuda));
   m.impl("layer_norm_split", AMD_DFT_TRACED("amd_dft::layer_norm_split", amd_dft::layer_norm_split_cuda));
+  m.impl("instance_norm", AMD_DFT_TRACED("amd_dft::instance_norm", amd_dft::instance_norm_cuda));
+  m.impl("instance_norm_out", AMD_DFT_TRACED("amd_dft::instance_norm_out", amd_dft::instance_norm_out_cuda));
+  m.impl("instance_norm_stats", AMD_DFT_TRACED("amd_dft::instance_norm_stats", amd_dft::instance_norm_stats_cuda));
   m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cuda));
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cuda));
   m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cuda));
@@ -1203,6 +1357,9 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("ln_stats", AMD_DFT_TRACED("amd_dft::ln_stats", amd_dft::ln_stats_cpu));
   m.impl("ln_stats_merge", AMD_DFT_TRACED("amd_dft::ln_stats_merge", amd_dft::ln_stats_merge_cpu));
   m.impl("layer_norm_split", AMD_DFT_TRACED("amd_dft::layer_norm_split", amd_dft::layer_norm_split_cpu));
+  m.impl("instance_norm", AMD_DFT_TRACED("amd_dft::instance_norm", amd_dft::instance_norm_cpu));
+  m.impl("instance_norm_out", AMD_DFT_TRACED("amd_dft::instance_norm_out", amd_dft::instance_norm_out_cpu));
+  m.impl("instance_norm_stats", AMD_DFT_TRACED("amd_dft::instance_norm_stats", amd_dft::instance_norm_stats_cpu));
   m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cpu));
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cpu));
   m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cpu));
@@ -1223,6 +1380,9 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("ln_stats", &amd_dft::ln_stats_meta);
   m.impl("ln_stats_merge", &amd_dft::ln_stats_merge_meta);
   m.impl("layer_norm_split", &amd_dft::layer_norm_split_meta);
+  m.impl("instance_norm", &amd_dft::instance_norm_meta);
+  m.impl("instance_norm_out", &amd_dft::instance_norm_out_meta);
+  m.impl("instance_norm_stats", &amd_dft::instance_norm_stats_meta);
   m.impl("fno_mix", &amd_dft::fno_mix_meta);
   m.impl("fno_pointwise", &amd_dft::fno_pointwise_meta);
   m.impl("fno_pointwise_out", &amd_dft::fno_pointwise_out_meta);

@@ -290,6 +290,57 @@ struct LnRoute {
 LnRoute ln_route(LnOp op, int64_t cols, bool bf16);
 const char* ln_kernel_name(LnKernel k);
 
+// ---- Instance normalisation over the spatial plane of each (batch, channel) of an NCHW tensor (instance_norm.hip):
+//   y[p, :] = (x[p, :] - mean_p) * rsqrt(var_p + eps) * w[p % C] + b[p % C],  biased variance over the P elements
+struct InstanceNormLaunch {
+  const void* x = nullptr;     // [planes, P] fp32 (bf16 if bf16), starting on a 16-byte boundary
+  void* y = nullptr;           // same shape and alignment; nullptr: statistics only
+  const float* w = nullptr;    // [C] fp32 or nullptr (1)
+  const float* b = nullptr;    // [C] fp32 or nullptr (0)
+  float* stats = nullptr;      // statistics only: [planes, 2] (mean, rstd)
+  float* part = nullptr;       // split route: [planes, S, 4] workspace (count, mean - x[p, 0], M2, unused)
+  int64_t planes = 0, P = 0;
+  int C = 1;
+  float eps = 1e-5f;
+  int bf16 = 0;
+};
+// The route of a call (host only; launch_instance_norm and the instance_norm_info op both answer from here).
+// resident: P <= kInMaxLen, the plane fits the LDS image of one workgroup (64 KB with its scratch, so two
+// workgroups share a CU) -- one workgroup per plane.  split: every larger plane, in S = ceil(P / chunk) chunks; the
+// chunk starts at kInMaxLen elements and halves, down to kInMinChunk, while planes * S would leave fewer than
+// kInFillWgs workgroups (four per CU).  Both dtypes share the rule: the LDS image is fp32.
+constexpr int kInThreads = 512;
+constexpr int kInScratchBytes = 256;                // reduction scratch in front of the LDS image
+constexpr int64_t kInMaxLen = 16256;                // elements: 256 + (16256 + 4) * 4 = 65296 bytes <= 64 KB
+constexpr int64_t kInMinChunk = kInMaxLen / 8;      // 2032
+constexpr int64_t kInFillWgs = 1024;
+struct InstanceNormRoute {
+  bool resident;
+  int64_t S;       // chunks per plane (resident: 1)
+  int64_t chunk;   // elements per chunk, the last one of a plane may be shorter (resident: P)
+  int vec;         // elements per 16-byte access
+  int64_t lds;     // dynamic LDS bytes per workgroup of the kernel that holds the data
+  int64_t wgs;     // workgroups per launch: planes * S
+};
+inline int64_t instance_norm_lds_bytes(int64_t len) { return kInScratchBytes + (len + 4) * 4; }
+inline InstanceNormRoute instance_norm_route(int64_t planes, int64_t P, bool bf16) {
+  InstanceNormRoute r{};
+  r.vec = bf16 ? 8 : 4;
+  r.resident = P <= kInMaxLen;
+  if (r.resident) {
+    r.S = 1;
+    r.chunk = P;
+  } else {
+    r.chunk = kInMaxLen;
+    while (r.chunk > kInMinChunk && planes * ((P + r.chunk - 1) / r.chunk) < kInFillWgs) r.chunk /= 2;
+    r.S = (P + r.chunk - 1) / r.chunk;
+  }
+  r.lds = instance_norm_lds_bytes(r.chunk);
+  r.wgs = planes * r.S;
+  return r;
+}
+void launch_instance_norm(const InstanceNormLaunch& p, void* stream);
+
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {
   const void* x = nullptr;        // [O, L, C] bf16 (fp32 if f32) stored residual stream

@@ -7,6 +7,8 @@ longitude followed by a Legendre transform along latitude (conventions: :mod:`..
   out, so they drop into code written against that package.
 * ``SphericalConv2d``: the SFNO "diagonal" spectral operator y[b,o,l,m] = sum_i x[b,i,l,m] w[i,o,l].
 * ``SFNOBlock``: ``act(SphericalConv2d(x) + Conv1x1(x))``.
+* ``SFNONet`` / ``SFNOConfig``: a whole network of them (FourCastNet-v2 style): 1x1 encoder, position embedding,
+  ``depth`` blocks of instance norm -> ``SFNOBlock`` -> instance norm -> 1x1 MLP with a residual, 1x1 decoder.
 
 Backends: ``"amd"`` (the default: ``sht`` -> mix -> ``isht`` and the ``fno_pointwise`` tail, hand kernels on a
 GPU, their ATen counterparts on CPU tensors) and ``"torch"`` (torch.fft + einsum on a table built in fp64: the
@@ -24,7 +26,8 @@ fp32 / complex64, and bf16 callers use ``ops.sht.sht`` / ``isht`` (coefficients 
 """
 from __future__ import annotations
 
-from typing import Optional
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -33,7 +36,7 @@ import torch.nn.functional as F
 
 from ..ops import sht as S
 
-__all__ = ["RealSHT", "InverseRealSHT", "SphericalConv2d", "SFNOBlock"]
+__all__ = ["RealSHT", "InverseRealSHT", "SphericalConv2d", "SFNOBlock", "SFNOConfig", "SFNONet"]
 
 # SphericalConv2d(mix="auto") expands its [Cin, Cout, lmax] weights over m for fno_mix; beyond this many bytes it
 # does not, and mixes per degree
@@ -225,3 +228,148 @@ class SFNOBlock(nn.Module):
                                                    self.w.bias.float(), self.activation)
         y = spec.to(x.dtype) + self.w(x)
         return F.gelu(y) if self.activation else y
+
+
+@dataclass
+class SFNOConfig:
+    img_size: Tuple[int, int] = (180, 360)  # (nlat, nlon)
+    in_chans: int = 20
+    out_chans: int = 20
+    embed_dim: int = 64
+    depth: int = 4
+    lmax: Optional[int] = None
+    mmax: Optional[int] = None
+    grid: str = "equiangular"
+    mlp_ratio: float = 2.0
+    norm: str = "instance"  # "instance" | "none"
+    pos_embed: bool = True
+    mix: str = "auto"       # of the SphericalConv2d layers: "auto" | "degree"
+    eps: float = 1e-6
+
+
+def _conv1x1(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """The 1x1 convolution in x's precision (the torch backend follows its input, fp64 included)."""
+    return F.conv2d(x, conv.weight.to(x.dtype), conv.bias.to(x.dtype))
+
+
+class SFNONetBlock(nn.Module):
+    """One block of :class:`SFNONet`: ``h + fc2(GELU(fc1(IN1(SFNOBlock(IN0(h))))))``."""
+
+    def __init__(self, cfg: SFNOConfig, lmax: int, mmax: int, backend: str):
+        super().__init__()
+        nlat, nlon = cfg.img_size
+        E, hidden = cfg.embed_dim, int(round(cfg.mlp_ratio * cfg.embed_dim))
+        instance = cfg.norm == "instance"
+        self.norm0 = nn.InstanceNorm2d(E, eps=cfg.eps, affine=True) if instance else nn.Identity()
+        self.layer = SFNOBlock(E, nlat, nlon, lmax, mmax, cfg.grid, True, backend, cfg.mix)
+        self.norm1 = nn.InstanceNorm2d(E, eps=cfg.eps, affine=True) if instance else nn.Identity()
+        self.fc1 = nn.Conv2d(E, hidden, 1)
+        self.fc2 = nn.Conv2d(hidden, E, 1)
+
+
+class SFNONet(nn.Module):
+    """A spherical FNO on an (nlat, nlon) grid, FourCastNet-v2 style, random init::
+
+        h = enc2(GELU(enc1(x))) + pos              # 1x1 convs in_chans -> embed -> embed; pos [1, embed, nlat, nlon]
+        for each block:
+            n0 = IN0(h)
+            a  = SFNOBlock(n0)                     # GELU(SphericalConv2d(n0) + Conv1x1(n0))
+            n1 = IN1(a)
+            h  = h + fc2(GELU(fc1(n1)))            # 1x1 convs embed -> mlp_ratio * embed -> embed
+        y = dec2(GELU(dec1(h)))                    # embed -> embed -> out_chans
+
+    GELU is the erf form; ``IN`` is ``nn.InstanceNorm2d(affine=True)`` (``norm="none"``: the identity); ``pos`` is
+    left out with ``pos_embed=False``; ``mix`` goes to the ``SphericalConv2d`` layers.
+
+    ``backend="torch"`` is the definition and the numerics oracle: it follows the input's precision, so an fp64 input
+    gives an fp64 result.  ``backend="amd"`` (the default) runs every line on the hand kernels: each 1x1 convolution is
+    one ``fno_pointwise`` call (its ``spec`` addend carries ``pos`` or the block's residual ``h``, its ``gelu`` flag the
+    activation), the middle of a block is the :class:`SFNOBlock` path (``sht`` -> mix -> ``isht`` -> ``fno_pointwise``)
+    and the norms are ``instance_norm`` (csrc/spectral/instance_norm.hip).  A bf16 input gives a bf16 network: bf16
+    ``instance_norm``, the bf16 spherical line and the bf16 ``fno_pointwise``.  ``pos`` cast to the input's dtype and
+    expanded over the batch is cached on the module per dtype and batch size.
+
+    Out of scope: resolution changes between blocks (``scale_factor``), LayerNorm over NCHW, and weight-for-weight
+    compatibility with any published checkpoint."""
+
+    def __init__(self, cfg: Optional[SFNOConfig] = None, backend: str = "amd"):
+        super().__init__()
+        self.cfg = cfg = cfg or SFNOConfig()
+        if cfg.norm not in ("instance", "none"):
+            raise ValueError(f"norm must be 'instance' or 'none', got {cfg.norm!r}")
+        _check_mix(cfg.mix)
+        nlat, nlon = (int(d) for d in cfg.img_size)
+        lmax, mmax = S._defaults(nlat, nlon, cfg.lmax, cfg.mmax)
+        E = cfg.embed_dim
+        self.enc1 = nn.Conv2d(cfg.in_chans, E, 1)
+        self.enc2 = nn.Conv2d(E, E, 1)
+        self.pos = nn.Parameter(0.02 * torch.randn(1, E, nlat, nlon)) if cfg.pos_embed else None
+        self.blocks = nn.ModuleList([SFNONetBlock(cfg, lmax, mmax, backend) for _ in range(cfg.depth)])
+        self.dec1 = nn.Conv2d(E, E, 1)
+        self.dec2 = nn.Conv2d(E, cfg.out_chans, 1)
+        self.set_backend(backend)
+
+    def set_backend(self, backend: str) -> "SFNONet":
+        self.backend = _check_backend(backend)
+        for b in self.blocks:
+            b.layer.set_backend(backend)
+        return self
+
+    # ---- amd backend
+    @staticmethod
+    def _pw(conv: nn.Conv2d, x: torch.Tensor, gelu: bool, spec: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return torch.ops.amd_dft.fno_pointwise(spec, x, conv.weight.reshape(conv.out_channels, -1).float(),
+                                               conv.bias.float(), gelu)
+
+    def _pos_as(self, x: torch.Tensor) -> Optional[torch.Tensor]:
+        from ..ops.spectral import module_cached
+
+        if self.pos is None:
+            return None
+        B = int(x.shape[0])
+        return module_cached(self, f"pos_{x.dtype}_{B}", (self.pos,),
+                             lambda: self.pos.detach().to(x.dtype).expand(B, -1, -1, -1).contiguous())
+
+    @staticmethod
+    def _norm(n: nn.Module, x: torch.Tensor) -> torch.Tensor:
+        if isinstance(n, nn.Identity):
+            return x
+        from ..ops import spectral as SP  # looked up per call, as the mix ops are (tests trace it)
+
+        return SP.instance_norm(x, n.weight, n.bias, n.eps)
+
+    def _forward_amd(self, x: torch.Tensor) -> torch.Tensor:
+        from .._loader import load_plugins
+
+        load_plugins()
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"SFNONet: the amd backend takes float32 or bfloat16, got {x.dtype}")
+        h = self._pw(self.enc2, self._pw(self.enc1, x, True), False, self._pos_as(x))
+        for b in self.blocks:
+            a = b.layer(self._norm(b.norm0, h))
+            h = self._pw(b.fc2, self._pw(b.fc1, self._norm(b.norm1, a), True), False, h)
+        return self._pw(self.dec2, self._pw(self.dec1, h, True), False)
+
+    # ---- torch backend: the definition
+    @staticmethod
+    def _norm_torch(n: nn.Module, x: torch.Tensor) -> torch.Tensor:
+        if isinstance(n, nn.Identity):
+            return x
+        return F.instance_norm(x, weight=n.weight.to(x.dtype), bias=n.bias.to(x.dtype), eps=n.eps)
+
+    def _forward_torch(self, x: torch.Tensor) -> torch.Tensor:
+        h = _conv1x1(self.enc2, F.gelu(_conv1x1(self.enc1, x)))
+        if self.pos is not None:
+            h = h + self.pos.to(x.dtype)
+        for b in self.blocks:
+            n0 = self._norm_torch(b.norm0, h)
+            a = F.gelu(b.layer.spectral(n0) + _conv1x1(b.layer.w, n0))
+            n1 = self._norm_torch(b.norm1, a)
+            h = h + _conv1x1(b.fc2, F.gelu(_conv1x1(b.fc1, n1)))
+        return _conv1x1(self.dec2, F.gelu(_conv1x1(self.dec1, h)))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        nlat, nlon = self.cfg.img_size
+        if x.dim() != 4 or x.shape[1] != self.cfg.in_chans or x.shape[2] != nlat or x.shape[3] != nlon:
+            raise ValueError(f"SFNONet: expected [B, {self.cfg.in_chans}, {nlat}, {nlon}], got {tuple(x.shape)}")
+        return self._forward_amd(x) if self.backend == "amd" else self._forward_torch(x)

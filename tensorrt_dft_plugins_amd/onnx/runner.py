@@ -240,6 +240,19 @@ def _ln(attrs, x, scale, bias=None):
     return Fn.layer_norm(x, x.shape[axis:], scale, bias, attrs.get("epsilon", 1e-5))
 
 
+@op("InstanceNormalization")
+def _instance_norm(attrs, x, scale, bias):
+    """The stock operator.  fp32 / bf16 device tensors run the hand kernel (``amd_dft::instance_norm``); anything
+    else is ATen."""
+    eps = attrs.get("epsilon", 1e-5)
+    if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.dim() >= 3:
+        from .._loader import load_plugins
+
+        load_plugins()
+        return torch.ops.amd_dft.instance_norm(x, scale, bias, eps)
+    return Fn.instance_norm(x, weight=scale, bias=bias, eps=eps)
+
+
 @op("GlobalAveragePool")
 def _gap(attrs, x):
     return x.mean(dim=tuple(range(2, x.dim())), keepdim=True)
@@ -511,7 +524,7 @@ _AMD_NODE_DENY = frozenset({"wrap_device_ptr", "wrap_host_ptr", "plan_cache_clea
                             "fallback_counts", "fallback_reset", "fallback_note", "plugin_registry",
                             # test support, and the ops that write into a caller's tensor
                             "lds_poison", "lds_probe", "lds_poison_info", "afno_mlp_out", "legendre_out", "sfno_mix_out",
-                            "fno_pointwise_out", "fno_c2r_pw_out"})
+                            "fno_pointwise_out", "fno_c2r_pw_out", "instance_norm_out"})
 
 
 def _amd_node(opname: str):

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from .._loader import load_plugins
 from . import dft as D
 
-__all__ = ["pack_afno_weights", "afno_fused_available", "afno_spectral_h", "c2r_w_add", "layer_norm",
+__all__ = ["pack_afno_weights", "afno_fused_available", "afno_spectral_h", "c2r_w_add", "layer_norm", "instance_norm",
            "afno_mlp_available", "afno_mlp_block_size_ok", "afno_spectral_mlp", "afno_block_mlp_hand",
            "afno_block_amd", "afno_block_fused", "afno_block_fused_f32",
            "afno_block_spectral", "afno_block_mlp", "fno_spectral_mix", "sfno_mix", "sfno_mix_split", "split_bf16", "module_cached",
@@ -181,6 +181,18 @@ def c2r_w_add(yw: torch.Tensor, x: torch.Tensor, W: int, scale: float,
 def layer_norm(x: torch.Tensor, ln: torch.nn.LayerNorm, residual: Optional[torch.Tensor] = None):
     """Fused (x + residual) -> LayerNorm.  Returns (normed, x + residual)."""
     return _ops().layer_norm(x, ln.weight, ln.bias, ln.eps, residual)
+
+
+def instance_norm(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                  eps: float = 1e-5) -> torch.Tensor:
+    """Instance normalisation of x [B, C, *spatial] (fp32 or bf16) over the spatial plane of each (b, c):
+    ``(x - mean) * rsqrt(var + eps) * weight[c] + bias[c]`` with the biased variance -- ``nn.InstanceNorm2d`` without
+    running statistics.  ``weight`` / ``bias``: [C], fp32 or x's dtype, either may be absent.  fp32 statistics and
+    arithmetic, the result in x's dtype (one rounding for bf16).  Native op on every device (CPU: ATen in fp64;
+    GPU: csrc/spectral/instance_norm.hip -- a plane of up to 16256 elements stays in one workgroup's LDS, one read
+    and one write; larger planes are cut into chunks whose (count, mean, M2) partials are merged in a fixed order,
+    two reads and one write; ``torch.ops.amd_dft.instance_norm_info`` names the route)."""
+    return _ops().instance_norm(x, weight, bias, float(eps))
 
 
 def _gelu_linear(y2: torch.Tensor, fc: torch.nn.Linear) -> torch.Tensor:
