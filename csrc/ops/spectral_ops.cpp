@@ -243,62 +243,110 @@ std::string afno_mlp_info(int64_t block_size, bool split, int64_t tokens) {
 }
 
 // ------------------------------------------------------------------ FNO mode mixing
-// x [B, Cin, M, 2] fp32, w [Cin, Cout, M, 2] fp32 -> y [B, Cout, M, 2] fp32
-at::Tensor fno_mix_cpu(const at::Tensor& x, const at::Tensor& w, int64_t /*path*/) {
+// x [B, Cin, M, 2], w [Cin, Cout, M, 2] -> y [B, Cout, M, 2]:   y[b, o, m] = sum_i x[b, i, m] w[i, o, m]   (complex)
+// dtype rule: x and w both bfloat16 -> the bf16 kernels and a bf16 result (bf16 operands as they are, fp32
+// accumulation, one rounding); every other combination is upcast to fp32, runs the fp32 kernels and returns fp32.
+void check_fno_mix(const at::Tensor& x, const at::Tensor& w) {
   TORCH_CHECK(x.dim() == 4 && x.size(3) == 2 && w.dim() == 4 && w.size(3) == 2 && w.size(0) == x.size(1) &&
                   w.size(2) == x.size(2),
               "fno_mix: x [B, Cin, M, 2], w [Cin, Cout, M, 2]");
+}
+bool fno_mix_bf16(const at::Tensor& x, const at::Tensor& w) {
+  return x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16;
+}
+std::vector<int64_t> fno_mix_out_shape(const at::Tensor& x, const at::Tensor& w) {
+  return {x.size(0), w.size(1), x.size(2), 2};
+}
+// what the result is like: dtype by the rule above, on x's device
+at::Tensor fno_mix_like(const at::Tensor& x, const at::Tensor& w) {
+  return at::empty({0}, x.options().dtype(fno_mix_bf16(x, w) ? at::kBFloat16 : at::kFloat));
+}
+
+at::Tensor fno_mix_cpu(const at::Tensor& x, const at::Tensor& w, int64_t /*path*/) {
+  check_fno_mix(x, w);
   at::Tensor xc = at::view_as_complex(x.to(at::kFloat).contiguous());
   at::Tensor wc = at::view_as_complex(w.to(at::kFloat).contiguous());
-  return at::view_as_real(at::einsum("bim,iom->bom", {xc, wc})).contiguous();
+  at::Tensor y = at::view_as_real(at::einsum("bim,iom->bom", {xc, wc})).contiguous();
+  return fno_mix_bf16(x, w) ? y.to(at::kBFloat16) : y;  // the product of the upcast operands, rounded once
 }
 
-bool fno_mix_fits(int64_t B, int64_t Cin, int64_t Cout) {
-  const int64_t K = 2 * Cin, N = 2 * Cout, Kp = (K + 3) & ~3, Bp = (B + 15) & ~15, Np = (N + 15) & ~15;
-  return 4 * 8 * (Bp * Kp + Kp * Np + Bp * Np) <= 160 * 1024;
+at::Tensor& fno_mix_out_cpu(const at::Tensor& x, const at::Tensor& w, int64_t path, at::Tensor& out) {
+  check_fno_mix(x, w);
+  check_out(out, fno_mix_out_shape(x, w), fno_mix_like(x, w), "fno_mix_out");
+  out.copy_(fno_mix_cpu(x, w, path));
+  return out;
 }
 
-// path: 0 = auto (scalar split-K stream for B <= 8, the MFMA kernel above), 2 = the MFMA kernel at any B
-at::Tensor fno_mix_cuda(const at::Tensor& x_, const at::Tensor& w_, int64_t path) {
-  const c10::DeviceGuard guard(x_.device());
-  TORCH_CHECK(x_.dim() == 4 && x_.size(3) == 2 && w_.dim() == 4 && w_.size(3) == 2 && w_.size(0) == x_.size(1) &&
-                  w_.size(2) == x_.size(2),
-              "fno_mix: x [B, Cin, M, 2], w [Cin, Cout, M, 2]");
+// the launch path of fno_mix and fno_mix_out: y is the contiguous result, aligned to one (re, im) pair (8 bytes fp32,
+// 4 bytes bf16: the kernels' stores).  path: 0 = auto (the split-K stream kernel for B <= 8, the MFMA kernel above),
+// 2 = the MFMA kernel at any B; fno_mix_route (spectral.h) decides.
+void fno_mix_run(const at::Tensor& x_, const at::Tensor& w_, int64_t path, const at::Tensor& y) {
+  const bool bf16 = fno_mix_bf16(x_, w_);
   const int64_t B = x_.size(0), Cin = x_.size(1), M = x_.size(2), Cout = w_.size(1);
-  at::Tensor x = x_.to(at::kFloat).contiguous(), w = w_.to(at::kFloat).contiguous();
-  at::Tensor y = at::empty({B, Cout, M, 2}, x.options());
-  if (!fno_mix_fits(B, Cin, Cout)) {
-    // operand tiles beyond the MFMA kernel's 160 KB LDS (e.g. width 40 at any batch): the split-K stream
-    // kernel has no channel limit and takes up to 8 samples per launch
-    for (int64_t b0 = 0; b0 < B; b0 += 8) {
-      FnoMixLaunch q;
-      q.x = x.data_ptr<float>() + b0 * Cin * M * 2;
-      q.w = w.data_ptr<float>();
-      q.y = y.data_ptr<float>() + b0 * Cout * M * 2;
-      q.B = static_cast<int>(std::min<int64_t>(8, B - b0));
-      q.Cin = static_cast<int>(Cin);
-      q.Cout = static_cast<int>(Cout);
-      q.M = static_cast<int>(M);
-      q.mfma = 0;
-      launch_fno_mix(q, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-    }
-    return checked(y, "fno_mix");
-  }
+  TORCH_CHECK(B < (1 << 30) && Cin < (1 << 28) && Cout < (1 << 28) && M < (int64_t(1) << 31) &&
+                  Cout * M < (int64_t(1) << 37),
+              "fno_mix: tensor too large");
+  const at::ScalarType dt = bf16 ? at::kBFloat16 : at::kFloat;
+  at::Tensor x = x_.to(dt).contiguous(), w = w_.to(dt).contiguous();
+  // one load per (re, im) pair: a view at an odd element offset gets its own copy
+  const uintptr_t al = bf16 ? 4 : 8;
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % al != 0) x = x.clone();
+  if (reinterpret_cast<uintptr_t>(w.data_ptr()) % al != 0) w = w.clone();
+  if (y.numel() == 0) return;
   FnoMixLaunch p;
-  p.x = x.data_ptr<float>();
-  p.w = w.data_ptr<float>();
-  p.y = y.data_ptr<float>();
+  p.x = x.data_ptr();
+  p.w = w.data_ptr();
+  p.y = y.data_ptr();
   p.B = static_cast<int>(B);
   p.Cin = static_cast<int>(Cin);
   p.Cout = static_cast<int>(Cout);
   p.M = static_cast<int>(M);
   p.mfma = path == 2 ? 1 : 0;
+  p.bf16 = bf16 ? 1 : 0;
   launch_fno_mix(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+}
+
+at::Tensor fno_mix_cuda(const at::Tensor& x, const at::Tensor& w, int64_t path) {
+  const c10::DeviceGuard guard(x.device());
+  check_fno_mix(x, w);
+  TORCH_CHECK(w.device() == x.device(), "fno_mix: w must be on the device of x");
+  at::Tensor y = at::empty(fno_mix_out_shape(x, w), fno_mix_like(x, w).options());
+  fno_mix_run(x, w, path, y);
   return checked(y, "fno_mix");
 }
 
+at::Tensor& fno_mix_out_cuda(const at::Tensor& x, const at::Tensor& w, int64_t path, at::Tensor& out) {
+  check_fno_mix(x, w);
+  TORCH_CHECK(w.device() == x.device(), "fno_mix_out: w must be on the device of x");
+  check_out(out, fno_mix_out_shape(x, w), fno_mix_like(x, w), "fno_mix_out");
+  check_out_aligned(out, fno_mix_bf16(x, w) ? 4 : 8, "fno_mix_out");
+  const c10::DeviceGuard guard(x.device());
+  fno_mix_run(x, w, path, out);
+  checked(out, "fno_mix_out");
+  return out;
+}
+
 at::Tensor fno_mix_meta(const at::Tensor& x, const at::Tensor& w, int64_t) {
-  return at::empty({x.size(0), w.size(1), x.size(2), 2}, x.options().dtype(at::kFloat));
+  return at::empty({x.size(0), w.size(1), x.size(2), 2},
+                   x.options().dtype(fno_mix_bf16(x, w) ? at::kBFloat16 : at::kFloat));
+}
+
+at::Tensor& fno_mix_out_meta(const at::Tensor&, const at::Tensor&, int64_t, at::Tensor& out) { return out; }
+
+// Which kernel fno_mix runs for (B, Cin, Cout, M, dtype, path) -- host only, no device (the companion of
+// sfno_mix_info): "stream NB=4 vec=1 lds=6144 wgs=640 launches=1", "mfma MT=8 lds=151552 wgs=256 launches=1" or
+// "stream-batched NB=8 vec=1 lds=12288 wgs=8 launches=2"; bf16: the bf16 instances' route (vec=2: two modes per lane,
+// what an even M runs when x, w and the result start on 8-byte boundaries) with a trailing " bf16=1"
+std::string fno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t M, bool bf16, int64_t path) {
+  TORCH_CHECK(B >= 1 && Cin >= 1 && Cout >= 1 && M >= 1 && B < (1 << 30) && Cin < (1 << 28) && Cout < (1 << 28) &&
+                  M < (int64_t(1) << 31) && Cout * M < (int64_t(1) << 37),
+              "amd_dft.fno_mix_info: B, Cin, Cout, M must be >= 1 (and the tensor within the op's limits)");
+  const FnoMixRoute r = fno_mix_route(B, Cin, Cout, M, bf16, path == 2);
+  std::string s = r.kind == FnoMixKind::Mfma ? "mfma MT=" + std::to_string(r.mt)
+                                             : std::string(r.kind == FnoMixKind::Stream ? "stream" : "stream-batched") +
+                                                   " NB=" + std::to_string(r.nb) + " vec=" + std::to_string(r.vec);
+  return s + " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) +
+         " launches=" + std::to_string(r.launches) + (bf16 ? " bf16=1" : "");
 }
 
 // ------------------------------------------------------------------ FNO pointwise epilogue
@@ -1309,6 +1357,8 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("instance_norm_stats(Tensor x, float eps=1e-5) -> Tensor");
   m.def("instance_norm_info(int planes, int P, bool bf16) -> str", &amd_dft::instance_norm_info);
   m.def("fno_mix(Tensor x, Tensor w, int path=0) -> Tensor");
+  m.def("fno_mix_out(Tensor x, Tensor w, int path, Tensor(a!) out) -> Tensor(a!)");
+  m.def("fno_mix_info(int B, int Cin, int Cout, int M, bool bf16=False, int path=0) -> str", &amd_dft::fno_mix_info);
   m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
   m.def("fno_pointwise_out(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");
   m.def("fno_pointwise_info(int cin, int cout, bool bf16, int P) -> str", &amd_dft::fno_pointwise_info);
@@ -1338,6 +1388,7 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("instance_norm_out", AMD_DFT_TRACED("amd_dft::instance_norm_out", amd_dft::instance_norm_out_cuda));
   m.impl("instance_norm_stats", AMD_DFT_TRACED("amd_dft::instance_norm_stats", amd_dft::instance_norm_stats_cuda));
   m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cuda));
+  m.impl("fno_mix_out", AMD_DFT_TRACED("amd_dft::fno_mix_out", amd_dft::fno_mix_out_cuda));
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cuda));
   m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cuda));
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cuda));
@@ -1361,6 +1412,7 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("instance_norm_out", AMD_DFT_TRACED("amd_dft::instance_norm_out", amd_dft::instance_norm_out_cpu));
   m.impl("instance_norm_stats", AMD_DFT_TRACED("amd_dft::instance_norm_stats", amd_dft::instance_norm_stats_cpu));
   m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cpu));
+  m.impl("fno_mix_out", AMD_DFT_TRACED("amd_dft::fno_mix_out", amd_dft::fno_mix_out_cpu));
   m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cpu));
   m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cpu));
   m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cpu));
@@ -1384,6 +1436,7 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("instance_norm_out", &amd_dft::instance_norm_out_meta);
   m.impl("instance_norm_stats", &amd_dft::instance_norm_stats_meta);
   m.impl("fno_mix", &amd_dft::fno_mix_meta);
+  m.impl("fno_mix_out", &amd_dft::fno_mix_out_meta);
   m.impl("fno_pointwise", &amd_dft::fno_pointwise_meta);
   m.impl("fno_pointwise_out", &amd_dft::fno_pointwise_out_meta);
   m.impl("fno_c2r_pw", &amd_dft::fno_c2r_pw_meta);

@@ -83,12 +83,85 @@ void launch_afno_mlp(const AfnoMlpLaunch& p, void* stream);
 
 // ---- FNO: per-mode complex channel mixing out[b,o,m] = sum_i x[b,i,m] * w[i,o,m]
 struct FnoMixLaunch {
-  const float* x;   // [B, Cin, M, 2] fp32 (M = kept modes, flattened)
-  const float* w;   // [Cin, Cout, M, 2] fp32
-  float* y;         // [B, Cout, M, 2] fp32
+  const void* x;    // [B, Cin, M, 2] fp32 (bf16 if bf16; M = kept modes, flattened)
+  const void* w;    // [Cin, Cout, M, 2] fp32 (bf16 if bf16)
+  void* y;          // [B, Cout, M, 2] fp32 (bf16 if bf16)
   int B, Cin, Cout, M;
   int mfma = 0;     // 1: the batched MFMA kernel even for B <= 8 (weights read once per mode tile)
+  int bf16 = 0;     // 1: bf16 x, w and y; a (re, im) pair is one 4-byte word, fp32 accumulation, one rounding
 };
+// Which kernel a call takes (host only; launch_fno_mix and the fno_mix_info op both answer from here).
+//   Stream: B <= 8 unless the caller asks for the MFMA kernel -- one lane per (o, m) output, the Cin sum split over
+//     the 4 waves of a workgroup; the instance NB = 1 / 2 / 4 / 8 holds the batch in registers.  bf16 with an even M:
+//     two modes per lane, so that a lane's loads are 8 bytes as in fp32.
+//   Mfma: every other call whose LDS tile fits.  A workgroup owns mt consecutive modes.
+//     fp32: mt = 8, tiles X [mt][Bp][Kp], W [mt][Kp][Np], Y [mt][Bp][Np] floats with Bp = ceil16(B), Kp = ceil4(2 Cin),
+//       Np = ceil16(2 Cout), within the device's 160 KB.
+//     bf16: K-major tiles X [mt][Bp][pitch], W [mt][Np][pitch] with pitch = 2 ceil32(2 Cin) + 16 bytes (the pad keeps
+//       the 16-byte fragment reads of 16 consecutive rows off each other's banks) and the packed result
+//       Y [mt][Bp][Np / 2] words (each mode's tiles 16 bytes / one word apart from the next).  mt is the largest of 16 / 8 / 4 whose tile stays within 80 KB (two workgroups per
+//       CU), halved while the grid would leave CUs without a workgroup; where not even 4 modes fit 80 KB, 4 modes
+//       within 160 KB.
+//   StreamBatched: the MFMA tile does not fit -- the stream kernel, 8 samples per launch (a call with B <= 8 is then
+//     plain Stream, whatever the caller asked for).
+constexpr int64_t kFnoMixLdsMax = 160 * 1024;
+constexpr int64_t kFnoMixLdsShared = 80 * 1024;
+constexpr int64_t kFnoMixFillWgs = 256;
+enum class FnoMixKind { Stream, Mfma, StreamBatched };
+struct FnoMixRoute {
+  FnoMixKind kind;
+  int nb;          // stream: the instance (samples held per lane) of the first launch
+  int vec;         // stream: modes per lane -- 2 (8-byte loads and stores) for bf16 with an even M and x, w, y on
+                   // 8-byte boundaries (aligned), else 1
+  int mt;          // mfma: modes per workgroup
+  int pitch;       // mfma, bf16: bytes per K-major LDS row
+  int64_t lds;     // LDS bytes per workgroup (stream: the static reduction buffer)
+  int64_t wgs;     // workgroups per launch
+  int launches;
+};
+inline int64_t fno_mix_lds_f32(int64_t B, int64_t Cin, int64_t Cout) {
+  const int64_t K = 2 * Cin, N = 2 * Cout, Kp = (K + 3) & ~int64_t(3), Bp = (B + 15) & ~int64_t(15),
+                Np = (N + 15) & ~int64_t(15);
+  return 4 * 8 * (Bp * Kp + Kp * Np + Bp * Np);
+}
+inline int64_t fno_mix_pitch_bf16(int64_t Cin) { return 2 * ((2 * Cin + 31) / 32 * 32) + 16; }
+inline int64_t fno_mix_lds_bf16(int64_t B, int64_t Cin, int64_t Cout, int mt) {
+  const int64_t Bp = (B + 15) & ~int64_t(15), Np = (2 * Cout + 15) & ~int64_t(15);
+  // each mode's x and w tiles are followed by 16 bytes, its result tile by one word (bank spreading over the modes)
+  return mt * ((Bp + Np) * fno_mix_pitch_bf16(Cin) + 32 + Bp * Np * 2 + 4);
+}
+inline FnoMixRoute fno_mix_route(int64_t B, int64_t Cin, int64_t Cout, int64_t M, bool bf16, bool mfma,
+                                 bool aligned = true) {
+  FnoMixRoute r{};
+  int mt = 0;
+  int64_t lds = 0;
+  if (!bf16) {
+    lds = fno_mix_lds_f32(B, Cin, Cout);
+    if (lds <= kFnoMixLdsMax) mt = 8;
+  } else {
+    for (int t = 16; t >= 4 && mt == 0; t /= 2)
+      if (fno_mix_lds_bf16(B, Cin, Cout, t) <= kFnoMixLdsShared) mt = t;
+    while (mt > 4 && (M + mt - 1) / mt < kFnoMixFillWgs) mt /= 2;
+    if (mt == 0 && fno_mix_lds_bf16(B, Cin, Cout, 4) <= kFnoMixLdsMax) mt = 4;
+    lds = fno_mix_lds_bf16(B, Cin, Cout, mt);
+  }
+  if (mt != 0 && (B > 8 || mfma)) {
+    r.kind = FnoMixKind::Mfma;
+    r.mt = mt;
+    r.pitch = bf16 ? static_cast<int>(fno_mix_pitch_bf16(Cin)) : 0;
+    r.lds = lds;
+    r.wgs = (M + mt - 1) / mt;
+    r.launches = 1;
+    return r;
+  }
+  r.kind = B <= 8 ? FnoMixKind::Stream : FnoMixKind::StreamBatched;
+  r.nb = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : 8;
+  r.vec = bf16 && M % 2 == 0 && aligned ? 2 : 1;
+  r.lds = 3LL * r.nb * 64 * 8 * r.vec;
+  r.wgs = (Cout * (M / r.vec) + 63) / 64;
+  r.launches = static_cast<int>((B + 7) / 8);
+  return r;
+}
 void launch_fno_mix(const FnoMixLaunch& p, void* stream);
 
 // ---- FNO pointwise epilogue: y[b,o,p] = act(spec[b,o,p] + sum_i w[o,i] x[b,i,p] + bias[o])

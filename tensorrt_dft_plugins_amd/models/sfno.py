@@ -5,7 +5,8 @@ longitude followed by a Legendre transform along latitude (conventions: :mod:`..
 
 * ``RealSHT`` / ``InverseRealSHT``: the torch-harmonics modules by name and argument order, complex tensors in and
   out, so they drop into code written against that package.
-* ``SphericalConv2d``: the SFNO "diagonal" spectral operator y[b,o,l,m] = sum_i x[b,i,l,m] w[i,o,l].
+* ``SphericalConv2d``: the SFNO spectral operator, y[b,o,l,m] = sum_i x[b,i,l,m] w[i,o,l] (``operator="dhconv"``, one
+  weight per degree: the Driscoll-Healy form) or sum_i x[b,i,l,m] w[i,o,l,m] (``operator="diagonal"``, one per mode).
 * ``SFNOBlock``: ``act(SphericalConv2d(x) + Conv1x1(x))``.
 * ``SFNONet`` / ``SFNOConfig``: a whole network of them (FourCastNet-v2 style): 1x1 encoder, position embedding,
   ``depth`` blocks of instance norm -> ``SFNOBlock`` -> instance norm -> 1x1 MLP with a residual, 1x1 decoder.
@@ -17,11 +18,13 @@ numerics oracle; it follows the input's precision, so an fp64 input gives an fp6
 The mix of the amd backend is one of two ops (``mix=`` of the layers): ``fno_mix`` on the weights expanded over
 every order m, or ``sfno_mix`` (csrc/spectral/sfno_mix.hip), which reads the per-degree weights directly -- one
 bf16x3 MFMA GEMM per degree -- and needs no expansion.  ``"auto"`` expands up to ``EXPAND_LIMIT_BYTES`` and runs
-``sfno_mix`` on device tensors above it; ``"degree"`` always runs ``sfno_mix``.
+``sfno_mix`` on device tensors above it; ``"degree"`` always runs ``sfno_mix``; ``"expand"`` always runs ``fno_mix``
+on the expansion.  The per-mode operator (``operator="diagonal"``) is an ``fno_mix`` call as it stands.
 
-Precision of the amd backend follows the input: fp32, or bf16 end to end (``sht``, ``sfno_mix``, ``isht`` and the
-``fno_pointwise`` tail all take and return bf16; the bf16 mix is the per-degree kernel under both ``mix`` values,
-since ``fno_mix`` has no bf16 kernel; the weights are cast and repacked once per dtype and cached on the module).  ``RealSHT`` / ``InverseRealSHT`` have complex tensors at one end, and complex bf16 does not exist: they stay
+Precision of the amd backend follows the input: fp32, or bf16 end to end (``sht``, the mix, ``isht`` and the
+``fno_pointwise`` tail all take and return bf16; the bf16 mix is the per-degree kernel under ``"auto"`` and
+``"degree"``, the bf16 ``fno_mix`` under ``"expand"`` and for the diagonal operator; the weights are cast, and
+repacked or expanded, once per dtype and cached on the module).  ``RealSHT`` / ``InverseRealSHT`` have complex tensors at one end, and complex bf16 does not exist: they stay
 fp32 / complex64, and bf16 callers use ``ops.sht.sht`` / ``isht`` (coefficients with a trailing re/im dim).
 """
 from __future__ import annotations
@@ -39,14 +42,20 @@ from ..ops import sht as S
 __all__ = ["RealSHT", "InverseRealSHT", "SphericalConv2d", "SFNOBlock", "SFNOConfig", "SFNONet"]
 
 # SphericalConv2d(mix="auto") expands its [Cin, Cout, lmax] weights over m for fno_mix; beyond this many bytes it
-# does not, and mixes per degree
+# does not, and mixes per degree; mix="expand" raises beyond it
 EXPAND_LIMIT_BYTES = 256 << 20
 
 
 def _check_mix(mix: str) -> str:
-    if mix not in ("auto", "degree"):
-        raise ValueError(f"mix must be 'auto' or 'degree', got {mix!r}")
+    if mix not in ("auto", "degree", "expand"):
+        raise ValueError(f"mix must be 'auto', 'degree' or 'expand', got {mix!r}")
     return mix
+
+
+def _check_operator(operator: str) -> str:
+    if operator not in ("dhconv", "diagonal"):
+        raise ValueError(f"operator must be 'dhconv' or 'diagonal', got {operator!r}")
+    return operator
 
 
 def _check_backend(backend: str) -> str:
@@ -115,10 +124,17 @@ class InverseRealSHT(_SHTBase):
 
 
 class SphericalConv2d(nn.Module):
-    """The SFNO "diagonal" spectral operator: one complex weight per (in, out, degree l), shared by all orders m:
-    ``y = isht(mix(sht(x)))`` with ``mix[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l]``; ``weight`` is [Cin, Cout, lmax, 2].
+    """The SFNO spectral operator ``y = isht(mix(sht(x)))``.  ``operator`` picks the weights:
 
-    The amd backend runs ``sht`` -> mix -> ``isht``; ``mix`` picks the middle op:
+    * ``"dhconv"`` (the default, the Driscoll-Healy form): one complex weight per (in, out, degree l), shared by all
+      orders m, ``mix[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l]``; ``weight`` is [Cin, Cout, lmax, 2].
+    * ``"diagonal"``: one complex weight per (in, out, l, m), ``mix[b,o,l,m] = sum_i c[b,i,l,m] w[i,o,l,m]``;
+      ``weight`` is [Cin, Cout, lmax, mmax, 2], initialised with the same scale.  The torch backend is
+      ``einsum("bilm,iolm->bolm")`` in the input's precision; the amd backend runs ``sht`` -> ``fno_mix`` on the
+      [.., lmax * mmax, 2] views -> ``isht``: fp32 on the fp32 weights, bf16 on the weights cast once and cached on
+      the module (``w_diag_bf16``), bf16 end to end on the bf16 ``fno_mix`` kernels.  ``mix`` is ignored.
+
+    The amd backend of ``"dhconv"`` runs ``sht`` -> mix -> ``isht``; ``mix`` picks the middle op:
 
     * ``"auto"`` (the default).  Up to 256 MiB of expanded weights (``EXPAND_LIMIT_BYTES``): ``fno_mix``, which
       takes one weight per mode, on the weights expanded over m once and cached on the module
@@ -128,23 +144,30 @@ class SphericalConv2d(nn.Module):
       alive for captured graphs); a CPU tensor notes a ``sfno_mix`` fallback (not counted on CPU tensors) and mixes
       with ``torch.einsum``.
     * ``"degree"``: ``sfno_mix`` on every device and at every size; the expansion is never built.
+    * ``"expand"``: ``fno_mix`` on the expansion, on every device and in both dtypes (a bf16 ``x`` mixes on the bf16
+      ``fno_mix`` kernels with a bf16 expansion, ``w_expanded_bf16``, cached beside the fp32 one).  Above
+      ``EXPAND_LIMIT_BYTES`` (counted in fp32 bytes for both dtypes) the forward raises ``ValueError``.
 
-    A bf16 ``x`` runs bf16 end to end: ``sht`` -> ``sfno_mix`` -> ``isht`` on bf16 tensors, under both ``mix`` values,
-    on every device and at every size.  ``fno_mix`` has no bf16 kernel (it would upcast the spectrum and the whole
-    expansion, mix in fp32 and round back), so the bf16 ``"auto"`` never takes it and never builds the expansion; the
-    per-degree kernel reads the bf16 weights directly.  Its tables (``w_bf16``, ``w_degree_bf16``: the weights rounded
-    to bf16 once, and their one-plane repacked form) are cached beside the fp32 ones."""
+    A bf16 ``x`` runs bf16 end to end.  Under ``"auto"`` and ``"degree"`` that is ``sht`` -> ``sfno_mix`` -> ``isht``
+    on every device and at every size: the bf16 ``"auto"`` never builds the expansion, although ``fno_mix`` has bf16
+    kernels -- the per-degree kernel reads Cin * Cout * lmax weights where the expansion streams mmax times as many,
+    and which of the two is faster depends on the shape (README, "bf16 fno_mix"), so the route that existing callers
+    get stays the one they have.  Its tables (``w_bf16``, ``w_degree_bf16``: the weights rounded to bf16 once, and
+    their one-plane repacked form) are cached beside the fp32 ones."""
 
     def __init__(self, in_ch: int, out_ch: int, nlat: int, nlon: int, lmax: Optional[int] = None,
-                 mmax: Optional[int] = None, grid: str = "equiangular", backend: str = "amd", mix: str = "auto"):
+                 mmax: Optional[int] = None, grid: str = "equiangular", backend: str = "amd", mix: str = "auto",
+                 operator: str = "dhconv"):
         super().__init__()
         self.in_ch, self.out_ch = in_ch, out_ch
         self.mix = _check_mix(mix)
+        self.operator = _check_operator(operator)
         self.sht = RealSHT(nlat, nlon, lmax, mmax, grid, backend)
         self.isht = InverseRealSHT(nlat, nlon, self.sht.lmax, self.sht.mmax, grid, backend)
         self.backend = _check_backend(backend)
         scale = 1.0 / (in_ch * out_ch)
-        self.weight = nn.Parameter(scale * torch.rand(in_ch, out_ch, self.sht.lmax, 2))
+        modes = (self.sht.lmax, self.sht.mmax) if self.operator == "diagonal" else (self.sht.lmax,)
+        self.weight = nn.Parameter(scale * torch.rand(in_ch, out_ch, *modes, 2))
 
     def set_backend(self, backend: str) -> "SphericalConv2d":
         self.backend = self.sht.backend = self.isht.backend = _check_backend(backend)
@@ -153,16 +176,26 @@ class SphericalConv2d(nn.Module):
     def expanded_bytes(self) -> int:
         return self.in_ch * self.out_ch * self.sht.lmax * self.sht.mmax * 2 * 4
 
-    def _expanded_weight(self) -> torch.Tensor:
+    def _expanded_weight(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
         from ..ops.spectral import module_cached
 
         L, M = self.sht.lmax, self.sht.mmax
 
         def build():
-            w = self.weight.detach().float()
+            w = self.weight.detach().to(dtype)
             return w[:, :, :, None, :].expand(-1, -1, -1, M, -1).reshape(self.in_ch, self.out_ch, L * M, 2).contiguous()
 
-        return module_cached(self, "w_expanded", (self.weight,), build)
+        return module_cached(self, "w_expanded" if dtype == torch.float32 else "w_expanded_bf16", (self.weight,), build)
+
+    def _mode_weight(self, dtype: torch.dtype) -> torch.Tensor:
+        """The diagonal operator's weights as ``fno_mix`` takes them, [Cin, Cout, lmax * mmax, 2]."""
+        from ..ops.spectral import module_cached
+
+        shape = (self.in_ch, self.out_ch, self.sht.lmax * self.sht.mmax, 2)
+        if dtype == torch.float32:
+            return self.weight.detach().float().reshape(shape)
+        return module_cached(self, "w_diag_bf16", (self.weight,),
+                             lambda: self.weight.detach().to(torch.bfloat16).reshape(shape).contiguous())
 
     def _degree_weight(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
         from ..ops.spectral import module_cached, sfno_mix_split
@@ -182,15 +215,26 @@ class SphericalConv2d(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.backend == "torch":
             wc = torch.view_as_complex(self.weight.to(x.dtype).contiguous())
-            return self.isht(torch.einsum("bilm,iol->bolm", self.sht(x), wc))
+            eq = "bilm,iolm->bolm" if self.operator == "diagonal" else "bilm,iol->bolm"
+            return self.isht(torch.einsum(eq, self.sht(x), wc))
         from ..ops.spectral import fno_spectral_mix, note_fallback, sfno_mix
 
         B = x.shape[0]
         L, M = self.sht.lmax, self.sht.mmax
         c = S.sht(x, L, M, self.sht.grid)  # [B, Cin, L, M, 2], fp32 or bf16 as x
         dt = c.dtype
+        if self.operator == "diagonal":
+            y = fno_spectral_mix(c.reshape(B, self.in_ch, L * M, 2), self._mode_weight(dt))
+            return S.isht(y.reshape(B, self.out_ch, L, M, 2), self.sht.nlat, self.sht.nlon, self.sht.grid)
         above = self.expanded_bytes() > EXPAND_LIMIT_BYTES
-        # bf16: always the per-degree kernel (fno_mix has no bf16 kernel; it would mix in fp32 between two casts)
+        if self.mix == "expand":
+            if above:
+                raise ValueError(f"SphericalConv2d(mix='expand'): the weights expanded over m take "
+                                 f"{self.expanded_bytes()} bytes, above EXPAND_LIMIT_BYTES ({EXPAND_LIMIT_BYTES}); "
+                                 "use mix='degree'")
+            y = fno_spectral_mix(c.reshape(B, self.in_ch, L * M, 2), self._expanded_weight(dt))
+            return S.isht(y.reshape(B, self.out_ch, L, M, 2), self.sht.nlat, self.sht.nlon, self.sht.grid)
+        # bf16 under "auto": the per-degree kernel, as before fno_mix had bf16 kernels (class docstring)
         if self.mix == "degree" or dt == torch.bfloat16 or (above and x.is_cuda):
             y = sfno_mix(c, self._weight_as(dt), self._degree_weight(dt), tri=1)
         elif above:
@@ -204,14 +248,15 @@ class SphericalConv2d(nn.Module):
 
 class SFNOBlock(nn.Module):
     """One SFNO layer: ``act(SphericalConv2d(x) + Conv1x1(x))``.  On the amd backend the tail (1x1 convolution,
-    bias, the spectral addend and the GELU) is one ``fno_pointwise`` call.  ``mix`` goes to the ``SphericalConv2d``
-    (``"auto"`` or ``"degree"``).  A bf16 ``x`` gives a bf16 layer: the bf16 ``SphericalConv2d`` and the bf16
-    ``fno_pointwise``."""
+    bias, the spectral addend and the GELU) is one ``fno_pointwise`` call.  ``mix`` and ``operator`` go to the
+    ``SphericalConv2d`` (``"auto"``, ``"degree"`` or ``"expand"``; ``"dhconv"`` or ``"diagonal"``).  A bf16 ``x`` gives
+    a bf16 layer: the bf16 ``SphericalConv2d`` and the bf16 ``fno_pointwise``."""
 
     def __init__(self, width: int, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None,
-                 grid: str = "equiangular", activation: bool = True, backend: str = "amd", mix: str = "auto"):
+                 grid: str = "equiangular", activation: bool = True, backend: str = "amd", mix: str = "auto",
+                 operator: str = "dhconv"):
         super().__init__()
-        self.spectral = SphericalConv2d(width, width, nlat, nlon, lmax, mmax, grid, backend, mix)
+        self.spectral = SphericalConv2d(width, width, nlat, nlon, lmax, mmax, grid, backend, mix, operator)
         self.w = nn.Conv2d(width, width, 1)
         self.activation = activation
         self.backend = _check_backend(backend)
@@ -243,8 +288,9 @@ class SFNOConfig:
     mlp_ratio: float = 2.0
     norm: str = "instance"  # "instance" | "none"
     pos_embed: bool = True
-    mix: str = "auto"       # of the SphericalConv2d layers: "auto" | "degree"
+    mix: str = "auto"       # of the SphericalConv2d layers: "auto" | "degree" | "expand"
     eps: float = 1e-6
+    operator: str = "dhconv"  # of the SphericalConv2d layers: "dhconv" | "diagonal"
 
 
 def _conv1x1(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
@@ -261,7 +307,7 @@ class SFNONetBlock(nn.Module):
         E, hidden = cfg.embed_dim, int(round(cfg.mlp_ratio * cfg.embed_dim))
         instance = cfg.norm == "instance"
         self.norm0 = nn.InstanceNorm2d(E, eps=cfg.eps, affine=True) if instance else nn.Identity()
-        self.layer = SFNOBlock(E, nlat, nlon, lmax, mmax, cfg.grid, True, backend, cfg.mix)
+        self.layer = SFNOBlock(E, nlat, nlon, lmax, mmax, cfg.grid, True, backend, cfg.mix, cfg.operator)
         self.norm1 = nn.InstanceNorm2d(E, eps=cfg.eps, affine=True) if instance else nn.Identity()
         self.fc1 = nn.Conv2d(E, hidden, 1)
         self.fc2 = nn.Conv2d(hidden, E, 1)
@@ -279,7 +325,7 @@ class SFNONet(nn.Module):
         y = dec2(GELU(dec1(h)))                    # embed -> embed -> out_chans
 
     GELU is the erf form; ``IN`` is ``nn.InstanceNorm2d(affine=True)`` (``norm="none"``: the identity); ``pos`` is
-    left out with ``pos_embed=False``; ``mix`` goes to the ``SphericalConv2d`` layers.
+    left out with ``pos_embed=False``; ``mix`` and ``operator`` go to the ``SphericalConv2d`` layers.
 
     ``backend="torch"`` is the definition and the numerics oracle: it follows the input's precision, so an fp64 input
     gives an fp64 result.  ``backend="amd"`` (the default) runs every line on the hand kernels: each 1x1 convolution is
@@ -298,6 +344,7 @@ class SFNONet(nn.Module):
         if cfg.norm not in ("instance", "none"):
             raise ValueError(f"norm must be 'instance' or 'none', got {cfg.norm!r}")
         _check_mix(cfg.mix)
+        _check_operator(cfg.operator)
         nlat, nlon = (int(d) for d in cfg.img_size)
         lmax, mmax = S._defaults(nlat, nlon, cfg.lmax, cfg.mmax)
         E = cfg.embed_dim

@@ -509,8 +509,10 @@ def afno_block_mlp_hand(blk, x: torch.Tensor, yn: torch.Tensor) -> torch.Tensor:
 
 def fno_spectral_mix(xm: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """FNO mode mixing out[b,o,m] = sum_i x[b,i,m] w[i,o,m] on complex-as-pair tensors
-    xm [B, Cin, M, 2], w [Cin, Cout, M, 2] -> [B, Cout, M, 2] (fp32).  Native op on every device
-    (CPU: ATen einsum; GPU: csrc/spectral/fno_mix.hip), so it also exports as one ONNX node."""
+    xm [B, Cin, M, 2], w [Cin, Cout, M, 2] -> [B, Cout, M, 2].  Both bf16: bf16 pairs go through unchanged to the bf16
+    kernels (fp32 accumulation, one rounding) and the result is bf16; every other dtype combination is mixed and
+    returned in fp32.  Native op on every device (CPU: ATen einsum; GPU: csrc/spectral/fno_mix.hip), so it also
+    exports as one ONNX node."""
     return _ops().fno_mix(xm.contiguous(), w.contiguous())
 
 
