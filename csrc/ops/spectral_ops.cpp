@@ -814,6 +814,157 @@ std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t
          (bf16 ? " bf16=1" : "");
 }
 
+// ------------------------------------------------------------------ vector Legendre transform (vector SHT)
+// x [..., 2, Q, M, 2] (a tangential vector field's two components, complex as trailing re/im), ta and tb [M, R, Q]
+// -> y [..., 2, R, M, 2]:
+//   y[n, 0, r, m] = sum_q ta[m, r, q] x[n, 0, q, m] - i tb[m, r, q] x[n, 1, q, m]
+//   y[n, 1, r, m] = sum_q ta[m, r, q] x[n, 1, q, m] + i tb[m, r, q] x[n, 0, q, m]
+// All float32 (bf16x3) or all bfloat16, as legendre; tri, the split forms and the _out variant are legendre's too,
+// with tri declaring the same zero part of both tables.
+void check_legendre_vec(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+                        const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  TORCH_CHECK((x.scalar_type() == at::kFloat || bf16) && ta.scalar_type() == x.scalar_type() &&
+                  tb.scalar_type() == x.scalar_type(),
+              "legendre_vec: x, ta and tb must all be float32 or all be bfloat16, got ", x.scalar_type(), ", ",
+              ta.scalar_type(), " and ", tb.scalar_type());
+  TORCH_CHECK(x.dim() >= 4 && x.size(-1) == 2 && x.size(-4) == 2 && ta.dim() == 3,
+              "legendre_vec: x [..., 2, Q, M, 2], ta and tb [M, R, Q]");
+  TORCH_CHECK(tb.sizes() == ta.sizes(), "legendre_vec: ta and tb must have the same shape, got ", ta.sizes(), " and ",
+              tb.sizes());
+  TORCH_CHECK(tb.device() == ta.device(), "legendre_vec: ta and tb must be on the same device");
+  TORCH_CHECK(x.size(-3) == ta.size(2), "legendre_vec: x has ", x.size(-3),
+              " points along the transformed dim, the tables ", ta.size(2));
+  TORCH_CHECK(x.size(-2) == ta.size(0), "legendre_vec: mode counts differ: x has ", x.size(-2), ", the tables ",
+              ta.size(0));
+  TORCH_CHECK(tri >= 0 && tri <= 2, "legendre_vec: tri must be 0, 1 or 2");
+  TORCH_CHECK(ta.size(0) < (1 << 30) && ta.size(1) < (1 << 30) && ta.size(2) >= 1 && ta.size(2) < (1 << 30),
+              "legendre_vec: bad table size");
+  const int64_t Rp = (ta.size(1) + 15) / 16 * 16, Qp = (ta.size(2) + 31) / 32 * 32;
+  for (const c10::optional<at::Tensor>* ts : {&tas, &tbs}) {
+    if (!present(*ts)) continue;
+    TORCH_CHECK((*ts)->scalar_type() == at::kBFloat16 &&
+                    (*ts)->sizes() == at::IntArrayRef({bf16 ? 1 : 2, ta.size(0), Rp, Qp}) &&
+                    (*ts)->device() == x.device(),
+                "legendre_vec: ta_split and tb_split must be bfloat16 [", bf16 ? 1 : 2,
+                ", M, ceil16(R), ceil32(Q)] on the device of x (two planes for float32 tables, one for bfloat16)");
+  }
+}
+
+at::Tensor legendre_vec_cpu(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+                            const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
+  check_legendre_vec(x, ta, tb, tas, tbs, tri);
+  // the definition: four plain transforms and the two rotations; y0 = A x0 - i B x1, y1 = A x1 + i B x0
+  if (x.scalar_type() == at::kBFloat16)  // the bf16 operands as they are, everything in fp32, rounded once
+    return legendre_vec_cpu(x.to(at::kFloat), ta.to(at::kFloat), tb.to(at::kFloat), c10::nullopt, c10::nullopt, tri)
+        .to(at::kBFloat16);
+  at::Tensor a = legendre_cpu(x, ta, c10::nullopt, tri);  // [..., 2, R, M, 2]: (A x0, A x1)
+  at::Tensor b = legendre_cpu(x, tb, c10::nullopt, tri);  //                    (B x0, B x1)
+  at::Tensor b0 = b.select(-4, 0), b1 = b.select(-4, 1);
+  // -i (re, im) = (im, -re);  +i (re, im) = (-im, re)
+  at::Tensor r0 = at::stack({b1.select(-1, 1), b1.select(-1, 0).neg()}, -1);
+  at::Tensor r1 = at::stack({b0.select(-1, 1).neg(), b0.select(-1, 0)}, -1);
+  return (a + at::stack({r0, r1}, -4)).contiguous();
+}
+
+at::Tensor& legendre_vec_out_cpu(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+                                 const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs,
+                                 int64_t tri, at::Tensor& out) {
+  check_legendre_vec(x, ta, tb, tas, tbs, tri);
+  check_out(out, legendre_out_shape(x, ta), x, "legendre_vec_out");
+  out.copy_(legendre_vec_cpu(x, ta, tb, tas, tbs, tri));
+  return out;
+}
+
+// the launch path of legendre_vec and legendre_vec_out (y as for legendre_run)
+void legendre_vec_run(const at::Tensor& x_, const at::Tensor& ta_, const at::Tensor& tb_,
+                      const c10::optional<at::Tensor>& tas_, const c10::optional<at::Tensor>& tbs_, int64_t tri,
+                      const at::Tensor& y) {
+  const int64_t M = ta_.size(0), R = ta_.size(1), Q = ta_.size(2);
+  const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
+  auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
+  const bool bf16 = x_.scalar_type() == at::kBFloat16;
+  at::Tensor x = x_.contiguous();
+  // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % (bf16 ? 4 : 8) != 0) x = x.clone();
+  auto split = [&](const at::Tensor& t, const c10::optional<at::Tensor>& ts_) {
+    if (present(ts_)) return ts_->contiguous();
+    TORCH_CHECK(t.device() == x.device(), "legendre_vec: ta and tb must be on the device of x");
+    at::Tensor tp = at::constant_pad_nd(t, {0, Qp - Q, 0, Rp - R}).contiguous();
+    if (bf16) return tp.unsqueeze(0);
+    at::Tensor ts = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
+    if (tp.numel() > 0)
+      launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
+                        static_cast<int>(Qp), false, stream);
+    return ts;
+  };
+  at::Tensor tas = split(ta_, tas_), tbs = split(tb_, tbs_);
+  if (y.numel() == 0) return;
+  const int64_t N = x.numel() / (2 * Q * M * 2);
+  TORCH_CHECK(N < (int64_t(1) << 31) / 32, "legendre_vec: too many fields");
+  LegendreVecLaunch p;
+  p.x = x.data_ptr();
+  p.ah = reinterpret_cast<const uint16_t*>(tas.data_ptr());
+  p.al = bf16 ? nullptr : p.ah + M * Rp * Qp;
+  p.bh = reinterpret_cast<const uint16_t*>(tbs.data_ptr());
+  p.bl = bf16 ? nullptr : p.bh + M * Rp * Qp;
+  p.y = y.data_ptr();
+  p.bf16 = bf16 ? 1 : 0;
+  p.N = N;
+  p.Q = static_cast<int>(Q);
+  p.R = static_cast<int>(R);
+  p.M = static_cast<int>(M);
+  p.tri = static_cast<int>(tri);
+  launch_legendre_vec(p, stream);
+}
+
+at::Tensor legendre_vec_cuda(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+                             const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
+  check_legendre_vec(x, ta, tb, tas, tbs, tri);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(legendre_out_shape(x, ta), x.options());
+  legendre_vec_run(x, ta, tb, tas, tbs, tri, y);
+  return checked(y, "legendre_vec");
+}
+
+at::Tensor& legendre_vec_out_cuda(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+                                  const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs,
+                                  int64_t tri, at::Tensor& out) {
+  check_legendre_vec(x, ta, tb, tas, tbs, tri);
+  check_out(out, legendre_out_shape(x, ta), x, "legendre_vec_out");
+  check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 4 : 8, "legendre_vec_out");
+  const c10::DeviceGuard guard(x.device());
+  legendre_vec_run(x, ta, tb, tas, tbs, tri, out);
+  checked(out, "legendre_vec_out");
+  return out;
+}
+
+at::Tensor legendre_vec_meta(const at::Tensor& x, const at::Tensor& ta, const at::Tensor&,
+                             const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t) {
+  return at::empty(legendre_out_shape(x, ta), x.options());
+}
+
+at::Tensor& legendre_vec_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                                  const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t,
+                                  at::Tensor& out) {
+  return out;
+}
+
+// Which tiling legendre_vec runs for (Q, R, M, real columns = 4 x fields, tri) -- host only, no device; the fields
+// of legendre_info, from legendre_vec_route (fp32 has no MT=8 instance)
+std::string legendre_vec_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
+  TORCH_CHECK(Q >= 1 && R >= 1 && M >= 1 && cols >= 4 && cols % 4 == 0 && Q < (1 << 30) && R < (1 << 30) &&
+                  M < (1 << 30) && cols < (int64_t(1) << 31) / 8,
+              "amd_dft.legendre_vec_info: Q, R, M must be >= 1 and cols a positive multiple of 4");
+  TORCH_CHECK(tri >= 0 && tri <= 2, "amd_dft.legendre_vec_info: tri must be 0, 1 or 2");
+  const LegendreRoute r = legendre_vec_route(Q, R, M, cols, static_cast<int>(tri), bf16);
+  return "mfma MT=" + std::to_string(r.mt) + " CT=" + std::to_string(r.ct) + " slabs=" + std::to_string(r.slabs) +
+         " rtiles=" + std::to_string(r.rtiles) + " rgroups=" + std::to_string(r.rgroups) +
+         " mgroups=" + std::to_string(r.mgroups) + " ctiles=" + std::to_string(r.ctiles) +
+         " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri) +
+         (bf16 ? " bf16=1" : "");
+}
+
 // ------------------------------------------------------------------ SFNO per-degree channel mixing
 // c [B, Cin, L, M, 2] fp32 (spherical harmonic coefficients, complex as trailing re/im), w [Cin, Cout, L, 2] fp32
 // -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
@@ -1369,6 +1520,11 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("legendre(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor");
   m.def("legendre_out(Tensor x, Tensor table, Tensor? table_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("legendre_info(int Q, int R, int M, int cols, int tri, bool bf16=False) -> str", &amd_dft::legendre_info);
+  m.def("legendre_vec(Tensor x, Tensor ta, Tensor tb, Tensor? ta_split=None, Tensor? tb_split=None, int tri=0) -> Tensor");
+  m.def("legendre_vec_out(Tensor x, Tensor ta, Tensor tb, Tensor? ta_split, Tensor? tb_split, int tri, Tensor(a!) out) "
+        "-> Tensor(a!)");
+  m.def("legendre_vec_info(int Q, int R, int M, int cols, int tri, bool bf16=False) -> str",
+        &amd_dft::legendre_vec_info);
   m.def("sfno_mix(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor");
   m.def("sfno_mix_out(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
@@ -1396,6 +1552,8 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cuda));
   m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cuda));
   m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cuda));
+  m.impl("legendre_vec", AMD_DFT_TRACED("amd_dft::legendre_vec", amd_dft::legendre_vec_cuda));
+  m.impl("legendre_vec_out", AMD_DFT_TRACED("amd_dft::legendre_vec_out", amd_dft::legendre_vec_out_cuda));
   m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cuda));
   m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cuda));
 }
@@ -1420,6 +1578,8 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cpu));
   m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cpu));
   m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cpu));
+  m.impl("legendre_vec", AMD_DFT_TRACED("amd_dft::legendre_vec", amd_dft::legendre_vec_cpu));
+  m.impl("legendre_vec_out", AMD_DFT_TRACED("amd_dft::legendre_vec_out", amd_dft::legendre_vec_out_cpu));
   m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cpu));
   m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cpu));
 }
@@ -1444,6 +1604,8 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("fno_c2r", &amd_dft::fno_c2r_meta);
   m.impl("legendre", &amd_dft::legendre_meta);
   m.impl("legendre_out", &amd_dft::legendre_out_meta);
+  m.impl("legendre_vec", &amd_dft::legendre_vec_meta);
+  m.impl("legendre_vec_out", &amd_dft::legendre_vec_out_meta);
   m.impl("sfno_mix", &amd_dft::sfno_mix_meta);
   m.impl("sfno_mix_out", &amd_dft::sfno_mix_out_meta);
 }

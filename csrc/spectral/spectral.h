@@ -269,6 +269,44 @@ inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t col
 }
 void launch_legendre(const LegendreLaunch& p, void* stream);
 
+// ---- Vector Legendre transform (the latitude half of a vector spherical harmonic transform, legendre_vec.hip):
+//   y[n, 0, r, m] = sum_q A[m, r, q] x[n, 0, q, m] - i B[m, r, q] x[n, 1, q, m]
+//   y[n, 1, r, m] = sum_q A[m, r, q] x[n, 1, q, m] + i B[m, r, q] x[n, 0, q, m]
+struct LegendreVecLaunch {
+  const void* x;       // [N, 2, Q, M, 2] fp32 (bf16 if bf16)
+  const uint16_t* ah;  // [M, Rp, Qp] bf16, hi plane of A zero-padded to Rp = ceil16(R), Qp = ceil32(Q)
+  const uint16_t* al;  // the lo plane, bf16(A - hi); not read if bf16
+  const uint16_t* bh;  // the same two planes of B
+  const uint16_t* bl;
+  void* y;             // [N, 2, R, M, 2] fp32 (bf16 if bf16)
+  int64_t N;
+  int Q, R, M;
+  int tri = 0;         // 0: dense; 1: rows r < m of A and B are zero; 2: columns q < m are zero
+  int bf16 = 0;        // 1: bf16 x and y, one plane per table, one MFMA per fragment pair
+};
+// Which tiling a call takes (host only; launch_legendre_vec and the legendre_vec_info op both answer from here).
+// The kernel is legendre's over the 2 N component planes -- a 16-column tile is 4 fields x 2 components x
+// (re | im), cols = 4 x fields -- so the tiles, the LDS image and the shrink rule are legendre's: 8 modes x 8
+// fields, then 4 modes, then 4 fields while the grid would leave most CUs without a workgroup.  fp32 starts at
+// 4 modes: with two tables in two planes an 8-mode fp32 kernel leaves one wave per SIMD (legendre_vec.hip).
+inline LegendreRoute legendre_vec_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/, bool bf16 = false) {
+  LegendreRoute r{};
+  r.slabs = static_cast<int>((Q + kLegSlab - 1) / kLegSlab);
+  r.rtiles = static_cast<int>((R + 15) / 16);
+  r.rgroups = (r.rtiles + kLegRowTiles - 1) / kLegRowTiles;
+  auto count = [&](int mt, int ct) { return ((M + mt - 1) / mt) * ((cols + 16 * ct - 1) / (16 * ct)) * r.rgroups; };
+  r.mt = bf16 ? 8 : 4;
+  r.ct = 2;
+  if (M <= 4 || count(r.mt, r.ct) < kLegFillWgs) r.mt = 4;
+  if (cols <= 16 || count(r.mt, r.ct) < kLegFillWgs) r.ct = 1;
+  r.mgroups = static_cast<int>((M + r.mt - 1) / r.mt);
+  r.ctiles = static_cast<int>((cols + 16 * r.ct - 1) / (16 * r.ct));
+  r.lds = legendre_lds_bytes(r.mt, r.ct, bf16);
+  r.wgs = count(r.mt, r.ct);
+  return r;
+}
+void launch_legendre_vec(const LegendreVecLaunch& p, void* stream);
+
 // ---- SFNO per-degree channel mixing (sfno_mix.hip):
 //   y[b, o, l, m] = sum_i c[b, i, l, m] * w[i, o, l]       (complex; one weight per degree l, shared by all orders m)
 struct SfnoMixLaunch {

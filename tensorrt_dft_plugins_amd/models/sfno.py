@@ -5,6 +5,8 @@ longitude followed by a Legendre transform along latitude (conventions: :mod:`..
 
 * ``RealSHT`` / ``InverseRealSHT``: the torch-harmonics modules by name and argument order, complex tensors in and
   out, so they drop into code written against that package.
+* ``RealVectorSHT`` / ``InverseRealVectorSHT``: the vector pair (tangential fields <-> spheroidal / toroidal
+  coefficients; definitions and sign convention in :mod:`..ops.sht`), the same constructor arguments.
 * ``SphericalConv2d``: the SFNO spectral operator, y[b,o,l,m] = sum_i x[b,i,l,m] w[i,o,l] (``operator="dhconv"``, one
   weight per degree: the Driscoll-Healy form) or sum_i x[b,i,l,m] w[i,o,l,m] (``operator="diagonal"``, one per mode).
 * ``SFNOBlock``: ``act(SphericalConv2d(x) + Conv1x1(x))``.
@@ -39,7 +41,7 @@ import torch.nn.functional as F
 
 from ..ops import sht as S
 
-__all__ = ["RealSHT", "InverseRealSHT", "SphericalConv2d", "SFNOBlock", "SFNOConfig", "SFNONet"]
+__all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT", "SphericalConv2d", "SFNOBlock", "SFNOConfig", "SFNONet"]
 
 # SphericalConv2d(mix="auto") expands its [Cin, Cout, lmax] weights over m for fno_mix; beyond this many bytes it
 # does not, and mixes per degree; mix="expand" raises beyond it
@@ -121,6 +123,70 @@ class InverseRealSHT(_SHTBase):
             return S.isht(c, self.nlat, self.nlon, self.grid)
         xf = torch.einsum("mkl,...lmc->...kmc", self._table(c), torch.view_as_real(c))
         return torch.fft.irfft(torch.view_as_complex(xf.contiguous()), n=self.nlon, dim=-1, norm="forward")
+
+
+class _VectorSHTBase(nn.Module):
+    def __init__(self, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None,
+                 grid: str = "equiangular", backend: str = "amd"):
+        super().__init__()
+        self.nlat, self.nlon, self.grid = int(nlat), int(nlon), grid
+        self.lmax, self.mmax = S._defaults(self.nlat, self.nlon, lmax, mmax)
+        self.backend = _check_backend(backend)
+        _, w, D0, D1 = S.vector_legendre_tables(self.nlat, self.lmax, self.mmax, grid)
+        # fp64, host: the "torch" backend casts them to the input's precision
+        self._a64, self._b64 = self._make_tables(w, D0, D1)
+
+    def _transform(self, x: torch.Tensor) -> torch.Tensor:
+        """The definition on a complex [..., 2, Q, M] tensor: y0 = A x0 - i B x1, y1 = A x1 + i B x0."""
+        xr = torch.view_as_real(x)
+        ta, tb = (t.to(device=x.device, dtype=xr.dtype) for t in (self._a64, self._b64))
+        a = torch.view_as_complex(torch.einsum("mrq,...qmc->...rmc", ta, xr).contiguous())
+        b = torch.view_as_complex(torch.einsum("mrq,...qmc->...rmc", tb, xr).contiguous())
+        return torch.stack([a[..., 0, :, :] - 1j * b[..., 1, :, :], a[..., 1, :, :] + 1j * b[..., 0, :, :]], dim=-3)
+
+    extra_repr = _SHTBase.extra_repr
+
+
+class RealVectorSHT(_VectorSHTBase):
+    """Forward vector SHT: real [..., 2, nlat, nlon] (v_theta, v_phi) -> complex [..., 2, lmax, mmax] (spheroidal,
+    toroidal).  amd backend: fp32 only -- a bf16 field raises ``TypeError``; call ``vsht`` (trailing re/im) instead."""
+
+    @staticmethod
+    def _make_tables(w, D0, D1):
+        l = np.arange(D0.shape[1], dtype=np.float64)
+        norm = np.where(l > 0, 1.0 / np.maximum(1.0, l * (l + 1.0)), 0.0)[None, :, None] * w[None, None, :]
+        return torch.from_numpy(D0 * norm), torch.from_numpy(D1 * norm)  # [mmax, lmax, nlat]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() < 3 or tuple(x.shape[-3:]) != (2, self.nlat, self.nlon):
+            raise ValueError(f"RealVectorSHT: expected a [..., 2, {self.nlat}, {self.nlon}] field, got {tuple(x.shape)}")
+        if self.backend == "amd":
+            if x.dtype == torch.bfloat16:
+                raise TypeError("RealVectorSHT: complex bfloat16 does not exist; for a bfloat16 field call vsht() "
+                                "(ops.sht.vsht), which returns the coefficients with a trailing re/im dim")
+            return torch.view_as_complex(S.vsht(x, self.lmax, self.mmax, self.grid))
+        return self._transform(2.0 * np.pi * torch.fft.rfft(x, dim=-1, norm="forward")[..., :self.mmax])
+
+
+class InverseRealVectorSHT(_VectorSHTBase):
+    """Inverse vector SHT: complex [..., 2, lmax, mmax] -> real [..., 2, nlat, nlon].  amd backend: complex64 only --
+    bf16 coefficients (a real tensor with a trailing re/im dim) raise ``TypeError``; call ``ivsht`` instead."""
+
+    @staticmethod
+    def _make_tables(w, D0, D1):
+        return (torch.from_numpy(np.ascontiguousarray(D0.transpose(0, 2, 1))),
+                torch.from_numpy(np.ascontiguousarray(D1.transpose(0, 2, 1))))  # [mmax, nlat, lmax]
+
+    def forward(self, c: torch.Tensor) -> torch.Tensor:
+        if self.backend == "amd" and c.dtype == torch.bfloat16:
+            raise TypeError("InverseRealVectorSHT: complex bfloat16 does not exist; for bfloat16 coefficients with a "
+                            "trailing re/im dim call ivsht() (ops.sht.ivsht)")
+        if c.dim() < 3 or tuple(c.shape[-3:]) != (2, self.lmax, self.mmax):
+            raise ValueError(f"InverseRealVectorSHT: expected [..., 2, {self.lmax}, {self.mmax}] coefficients, got "
+                             f"{tuple(c.shape)}")
+        if self.backend == "amd":
+            return S.ivsht(c, self.nlat, self.nlon, self.grid)
+        return torch.fft.irfft(self._transform(c), n=self.nlon, dim=-1, norm="forward")
 
 
 class SphericalConv2d(nn.Module):

@@ -523,7 +523,8 @@ AMD_DOMAIN = "com.amd.dft"
 _AMD_NODE_DENY = frozenset({"wrap_device_ptr", "wrap_host_ptr", "plan_cache_clear", "plan_cache_size", "plan_cache_pinned",
                             "fallback_counts", "fallback_reset", "fallback_note", "plugin_registry",
                             # test support, and the ops that write into a caller's tensor
-                            "lds_poison", "lds_probe", "lds_poison_info", "afno_mlp_out", "legendre_out", "sfno_mix_out",
+                            "lds_poison", "lds_probe", "lds_poison_info", "afno_mlp_out", "legendre_out", "legendre_vec_out",
+                            "sfno_mix_out",
                             "fno_pointwise_out", "fno_c2r_pw_out", "instance_norm_out", "fno_mix_out"})
 
 

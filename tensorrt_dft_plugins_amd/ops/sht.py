@@ -18,6 +18,21 @@ Conventions (the torch-harmonics "ortho" ones, so weights trained there carry ov
   C2R from ``mmax`` stored modes (``torch.fft.irfft(..., n=nlon, norm="forward")``).
 * defaults: ``lmax = nlat``, ``mmax = min(lmax, nlon // 2 + 1)``.
 
+Vector transforms (``vsht`` / ``ivsht``, the pair torch-harmonics calls ``RealVectorSHT`` / ``InverseRealVectorSHT``,
+same layout and names): a tangential field v = (v_theta, v_phi) [..., 2, nlat, nlon], component 0 colatitudinal, is
+expanded in the vector harmonics Psi = grad Y (spheroidal) and Phi = r x grad Y (toroidal, r the unit radial vector:
+this fixes the sign of the toroidal part) -> [..., 2, lmax, mmax, 2].  With the derivative tables
+D0[m, l, k] = d Pb_l^m / d theta and D1[m, l, k] = m Pb_l^m / sin theta (``vector_legendre_tables``; both zero for
+l < max(m, 1)), U, V the scaled longitude transforms of the two components and W_j = w_k D_j / (l (l + 1)):
+
+* forward: s[l, m] = sum_k W0 U - i W1 V,  t[l, m] = sum_k W0 V + i W1 U;
+* inverse: U[k, m] = sum_l D0 s - i D1 t,  V[k, m] = sum_l D0 t + i D1 s, then the C2R of ``isht`` per component.
+
+Both are the ``legendre_vec`` op (``csrc/spectral/legendre_vec.hip``): one kernel pass over both tables and both
+components.  ``vsht`` of the gradient (d f / d theta, (1 / sin theta) d f / d phi) of a band-limited scalar f is
+s = sht(f) for l >= 1, t = 0.  ``ivsht(vsht(v))`` reproduces a band-limited v where the quadrature is exact for the
+products involved: ``legendre-gauss`` up to lmax = nlat, ``equiangular`` up to lmax = (nlat + 1) / 2.
+
 Precision follows the input: fp32 (the tables are built in fp64 on the host and rounded once to fp32; the Legendre
 kernel runs the bf16x3 split, ~1e-6) or bf16 (the tables are ``bf16(fp32 table)``, the spectrum between the longitude
 FFT and ``legendre`` is bf16, the kernel multiplies the bf16 operands as they are with fp32 accumulation and rounds
@@ -36,7 +51,8 @@ import torch.nn.functional as F
 from .._loader import load_plugins
 from .dft import _from_complex
 
-__all__ = ["legendre_tables", "sht", "isht", "sht_tables", "legendre_split", "GRIDS"]
+__all__ = ["legendre_tables", "sht", "isht", "sht_tables", "legendre_split", "GRIDS",
+           "vector_legendre_tables", "vsht", "ivsht", "vsht_tables"]
 
 GRIDS = ("equiangular", "legendre-gauss")
 
@@ -182,4 +198,112 @@ def isht(c: torch.Tensor, nlat: int, nlon: int, grid: str = "equiangular") -> to
     t = sht_tables(nlat, nlon, lmax, mmax, grid, c.device, c.dtype)
     ops = _ops()
     xf = ops.legendre(c, t.inv, t.inv_split, 2)  # [..., nlat, mmax, 2]
+    return ops.c2r(xf, [xf.dim() - 2], [nlon], 1.0, [mmax, 0], c.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ vector transforms
+def vector_legendre_tables(nlat: int, lmax: int, mmax: int, grid: str = "equiangular"):
+    """(nodes [nlat], weights [nlat], D0 [mmax, lmax, nlat], D1 [mmax, lmax, nlat]), all float64 numpy.
+
+    D0[m, l, k] = d Pb_l^m / d theta = -1/2 (sqrt((l + m)(l - m + 1)) Pb_l^{m-1} - sqrt((l - m)(l + m + 1)) Pb_l^{m+1})
+    D1[m, l, k] = m Pb_l^m / sin theta
+                = -1/2 sqrt((2l + 1) / (2l - 1)) (sqrt((l - m)(l - m - 1)) Pb_{l-1}^{m+1} + sqrt((l + m)(l + m - 1)) Pb_{l-1}^{m-1})
+    with Pb_l^{-1} = -Pb_l^1, from the recurrence of ``legendre_tables`` carried one order further.  Rows l < max(m, 1)
+    are zero and so is the m = 0 plane of D1; D1 never divides by sin theta, so it is finite at the poles."""
+    x, w, P = legendre_tables(nlat, lmax, mmax + 1, grid)  # orders 0 .. mmax
+
+    def order(m):  # Pb^m as [lmax, nlat], m >= -1
+        return P[m] if m >= 0 else -P[1]
+
+    l = np.arange(lmax, dtype=np.float64)[:, None]
+    D0 = np.zeros((mmax, lmax, nlat), dtype=np.float64)
+    D1 = np.zeros((mmax, lmax, nlat), dtype=np.float64)
+    for m in range(min(mmax, lmax)):
+        lo, hi = order(m - 1), order(m + 1)
+        cm = np.sqrt(np.maximum(0.0, (l + m) * (l - m + 1.0)))
+        cp = np.sqrt(np.maximum(0.0, (l - m) * (l + m + 1.0)))
+        D0[m] = -0.5 * (cm * lo - cp * hi)
+        if m >= 1:
+            am = np.sqrt(np.maximum(0.0, (l - m) * (l - m - 1.0)))
+            ap = np.sqrt(np.maximum(0.0, (l + m) * (l + m - 1.0)))
+            D1[m, 1:] = (-0.5 * np.sqrt((2.0 * l + 1.0) / np.maximum(1.0, 2.0 * l - 1.0)))[1:] * (
+                am[1:] * hi[:-1] + ap[1:] * lo[:-1])
+        D0[m, :max(m, 1)] = 0.0
+        D1[m, :max(m, 1)] = 0.0
+    return x, w, D0, D1
+
+
+class _VecTables:
+    """The operands of ``vsht`` / ``ivsht`` for one (grid, truncation) on one device in one precision:
+    ``fwd_a``, ``fwd_b`` [mmax, lmax, nlat] = w_k D_j / (l (l + 1)), ``inv_a``, ``inv_b`` [mmax, nlat, lmax] = D_j
+    transposed, and on a GPU their split forms.  ``like``: the fp32 tables to round to bf16."""
+
+    NAMES = ("fwd_a", "fwd_b", "inv_a", "inv_b")
+
+    def __init__(self, nlat, nlon, lmax, mmax, grid, device, like: "Optional[_VecTables]" = None):
+        if like is not None:
+            for n in self.NAMES:
+                setattr(self, n, getattr(like, n).to(torch.bfloat16))
+        else:
+            _, w, D0, D1 = vector_legendre_tables(nlat, lmax, mmax, grid)
+            l = np.arange(lmax, dtype=np.float64)
+            norm = np.where(l > 0, 1.0 / np.maximum(1.0, l * (l + 1.0)), 0.0)[None, :, None] * w[None, None, :]
+            for n, D in (("fwd_a", D0 * norm), ("fwd_b", D1 * norm),
+                         ("inv_a", D0.transpose(0, 2, 1)), ("inv_b", D1.transpose(0, 2, 1))):
+                setattr(self, n, torch.from_numpy(np.ascontiguousarray(D)).float().to(device))
+        cuda = torch.device(device).type == "cuda"
+        for n in self.NAMES:
+            setattr(self, n + "_split", legendre_split(getattr(self, n)) if cuda else None)
+
+
+def vsht_tables(nlat: int, nlon: int, lmax: int, mmax: int, grid: str, device,
+                dtype: torch.dtype = torch.float32) -> _VecTables:
+    """The vector tables, cached like ``sht_tables`` (the same key plus a vector tag)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"vsht_tables: dtype must be float32 or bfloat16, got {dtype}")
+    key = (int(nlat), int(nlon), int(lmax), int(mmax), grid, str(torch.device(device)), "vector")
+    t = _CACHE.get(key)
+    if t is None:
+        t = _CACHE[key] = _VecTables(nlat, nlon, lmax, mmax, grid, device)
+    if dtype == torch.bfloat16:
+        key, t32 = key + (dtype,), t
+        t = _CACHE.get(key)
+        if t is None:
+            t = _CACHE[key] = _VecTables(nlat, nlon, lmax, mmax, grid, device, like=t32)
+    return t
+
+
+def vsht(x: torch.Tensor, lmax: Optional[int] = None, mmax: Optional[int] = None,
+         grid: str = "equiangular") -> torch.Tensor:
+    """Forward vector SHT of ``x`` [..., 2, nlat, nlon] (fp32 or bf16; component 0 = v_theta, 1 = v_phi) ->
+    [..., 2, lmax, mmax, 2] of the same dtype (component 0 spheroidal, 1 toroidal; trailing re/im).
+
+    One R2C along longitude over both components (as ``sht``), then ``legendre_vec`` with ``tri=1``."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"vsht: x must be float32 or bfloat16, got {x.dtype}")
+    if x.dim() < 3 or x.shape[-3] != 2:
+        raise ValueError(f"vsht: x must be [..., 2, nlat, nlon], got {tuple(x.shape)}")
+    nlat, nlon = int(x.shape[-2]), int(x.shape[-1])
+    lmax, mmax = _defaults(nlat, nlon, lmax, mmax)
+    t = vsht_tables(nlat, nlon, lmax, mmax, grid, x.device, x.dtype)
+    ops = _ops()
+    xf = ops.r2c(x, [x.dim() - 1], 2.0 * math.pi / nlon, [mmax, 0], x.dtype)  # [..., 2, nlat, mmax, 2]
+    return ops.legendre_vec(xf, t.fwd_a, t.fwd_b, t.fwd_a_split, t.fwd_b_split, 1)
+
+
+def ivsht(c: torch.Tensor, nlat: int, nlon: int, grid: str = "equiangular") -> torch.Tensor:
+    """Inverse vector SHT of ``c`` [..., 2, lmax, mmax, 2] (fp32 or bf16; or complex64 [..., 2, lmax, mmax]) ->
+    [..., 2, nlat, nlon] of the same real dtype.
+
+    ``legendre_vec`` with ``tri=2``, then one unnormalised C2R along longitude over both components (as ``isht``)."""
+    c = _from_complex(c)
+    if c.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ivsht: c must be float32 / complex64 or bfloat16 (trailing re/im), got {c.dtype}")
+    if c.dim() < 4 or c.shape[-4] != 2 or c.shape[-1] != 2:
+        raise ValueError(f"ivsht: c must be [..., 2, lmax, mmax, 2], got {tuple(c.shape)}")
+    lmax, mmax = int(c.shape[-3]), int(c.shape[-2])
+    _defaults(nlat, nlon, lmax, mmax)
+    t = vsht_tables(nlat, nlon, lmax, mmax, grid, c.device, c.dtype)
+    ops = _ops()
+    xf = ops.legendre_vec(c, t.inv_a, t.inv_b, t.inv_a_split, t.inv_b_split, 2)  # [..., 2, nlat, mmax, 2]
     return ops.c2r(xf, [xf.dim() - 2], [nlon], 1.0, [mmax, 0], c.dtype)
