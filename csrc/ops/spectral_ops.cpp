@@ -2,6 +2,7 @@
 // fused LayerNorm.  CPU implementations are plain ATen math (reference semantics); the
 // CUDA (HIP) implementations launch the hand-written gfx950 kernels.
 #include <ATen/ATen.h>
+#include <ATen/Parallel.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <ATen/core/dispatch/Dispatcher.h>
@@ -965,6 +966,171 @@ std::string legendre_vec_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int
          (bf16 ? " bf16=1" : "");
 }
 
+// ------------------------------------------------------------------ DISCO convolution on the sphere (gather half)
+// x [..., nlat_in, nlon_in], a longitude-invariant filter tensor in CSR over rows p * nlat_out + k' (row_ptr int32
+// [K * nlat_out + 1], idx int32 [nnz] = k * nlon_in + d sorted within a row, val [nnz]) -> y [..., K, nlat_out, nlon_out]:
+//   y[n, p, k', j'] = sum_e val[e] * x[n, k_e, (d_e + s j') mod nlon_in],  s = nlon_in / nlon_out
+// x float32 or bfloat16 with float32 val, fp32 accumulation, one rounding to x's dtype.  CPU tensors only: float64 x
+// with float64 val, the unrounded definition (what the fp64 oracle tests compare).  The table is trusted to be what
+// ops.disco.disco_tables builds (the holder checks it on the host); the kernel reads nothing outside x whatever it
+// holds, and the CPU kernel checks every entry.
+void check_disco(const char* op, const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx,
+                 const at::Tensor& val, int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  const auto xt = x.scalar_type();
+  TORCH_CHECK(xt == at::kFloat || xt == at::kBFloat16 || (xt == at::kDouble && x.device().is_cpu()), op,
+              ": x must be float32 or bfloat16 (float64 on CPU tensors), got ", xt);
+  TORCH_CHECK(val.scalar_type() == (xt == at::kDouble ? at::kDouble : at::kFloat), op, ": val must be ",
+              xt == at::kDouble ? "float64 for a float64 x" : "float32", ", got ", val.scalar_type());
+  TORCH_CHECK(row_ptr.scalar_type() == at::kInt && idx.scalar_type() == at::kInt, op,
+              ": row_ptr and idx must be int32, got ", row_ptr.scalar_type(), " and ", idx.scalar_type());
+  TORCH_CHECK(x.dim() >= 2, op, ": x must be [..., nlat_in, nlon_in], got ", x.sizes());
+  TORCH_CHECK(K >= 1 && nlat_out >= 1 && nlon_out >= 1 && K * nlat_out < (int64_t(1) << 31) - 1, op,
+              ": K, nlat_out and nlon_out must be >= 1");
+  const int64_t nlat_in = x.size(-2), nlon_in = x.size(-1);
+  TORCH_CHECK(nlat_in >= 1 && nlon_in >= 1 && nlat_in * nlon_in < (int64_t(1) << 31), op,
+              ": the input grid must be non-empty and hold fewer than 2^31 points, got ", nlat_in, " x ", nlon_in);
+  TORCH_CHECK(nlon_in % nlon_out == 0, op, ": nlon_in (", nlon_in, ") must be a multiple of nlon_out (", nlon_out, ")");
+  TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.size(0) == K * nlat_out + 1, op, ": row_ptr must be [K * nlat_out + 1] = [",
+              K * nlat_out + 1, "], got ", row_ptr.sizes());
+  TORCH_CHECK(idx.dim() == 1 && val.dim() == 1 && idx.size(0) == val.size(0) && idx.size(0) < (int64_t(1) << 31), op,
+              ": idx and val must be [nnz] with nnz < 2^31, got ", idx.sizes(), " and ", val.sizes());
+  TORCH_CHECK(row_ptr.device() == x.device() && idx.device() == x.device() && val.device() == x.device(), op,
+              ": row_ptr, idx and val must be on the device of x");
+}
+
+std::vector<int64_t> disco_out_shape(const at::Tensor& x, int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  std::vector<int64_t> s(x.sizes().begin(), x.sizes().end() - 2);
+  s.insert(s.end(), {K, nlat_out, nlon_out});
+  return s;
+}
+
+at::Tensor disco_cpu(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+                     int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  check_disco("disco", x, row_ptr, idx, val, K, nlat_out, nlon_out);
+  const int64_t nlat_in = x.size(-2), nlon_in = x.size(-1), s = nlon_in / nlon_out, rows = K * nlat_out;
+  const int64_t nnz = idx.size(0), pin = nlat_in * nlon_in;
+  const at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vd = val.to(at::kDouble).contiguous();
+  const int32_t* rpp = rp.data_ptr<int32_t>();
+  const int32_t* ixp = ix.data_ptr<int32_t>();
+  const double* vp = vd.data_ptr<double>();
+  TORCH_CHECK(rpp[0] >= 0 && rpp[rows] <= nnz, "disco: row_ptr must run from >= 0 to <= nnz");
+  for (int64_t r = 0; r < rows; ++r)
+    TORCH_CHECK(rpp[r] <= rpp[r + 1], "disco: row_ptr must not decrease (row ", r, ")");
+  for (int64_t e = rpp[0]; e < rpp[rows]; ++e)
+    TORCH_CHECK(ixp[e] >= 0 && ixp[e] < pin, "disco: idx[", e, "] = ", ixp[e], " is outside the input grid");
+  // the fp32 / bf16 values as they are, every sum in fp64 in table order, one rounding to x's dtype
+  const at::Tensor xd = x.to(at::kDouble).contiguous();
+  const int64_t planes = pin > 0 ? xd.numel() / pin : 0;
+  at::Tensor y = at::zeros(disco_out_shape(x, K, nlat_out, nlon_out), xd.options());
+  const double* xp = xd.data_ptr<double>();
+  double* yp = y.data_ptr<double>();
+  at::parallel_for(0, planes * rows, 1, [&](int64_t b, int64_t e_) {
+    for (int64_t t = b; t < e_; ++t) {
+      const int64_t n = t / rows, r = t % rows;
+      const double* xn = xp + n * pin;
+      double* yr = yp + t * nlon_out;
+      for (int64_t e = rpp[r]; e < rpp[r + 1]; ++e) {
+        const int64_t k0 = ixp[e] / nlon_in * nlon_in, d = ixp[e] - k0;
+        const double v = vp[e];
+        for (int64_t j = 0; j < nlon_out; ++j) {
+          int64_t c = d + s * j;
+          if (c >= nlon_in) c -= nlon_in;
+          yr[j] += v * xn[k0 + c];
+        }
+      }
+    }
+  });
+  return y.to(x.scalar_type());
+}
+
+at::Tensor& disco_out_cpu(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+                          int64_t K, int64_t nlat_out, int64_t nlon_out, at::Tensor& out) {
+  check_disco("disco_out", x, row_ptr, idx, val, K, nlat_out, nlon_out);
+  check_out(out, disco_out_shape(x, K, nlat_out, nlon_out), x, "disco_out");
+  out.copy_(disco_cpu(x, row_ptr, idx, val, K, nlat_out, nlon_out));
+  return out;
+}
+
+// the launch path of disco and disco_out (y contiguous, x's dtype)
+void disco_run(const at::Tensor& x_, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val, int64_t K,
+               int64_t nlat_out, int64_t nlon_out, const at::Tensor& y) {
+  if (y.numel() == 0) return;
+  at::Tensor x = x_.contiguous();  // element loads: a view at any element offset is read where it is
+  at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vl = val.contiguous();
+  DiscoLaunch p;
+  p.x = x.data_ptr();
+  p.row_ptr = rp.data_ptr<int32_t>();
+  p.idx = ix.data_ptr<int32_t>();
+  p.val = vl.data_ptr<float>();
+  p.y = y.data_ptr();
+  p.nlat_in = static_cast<int>(x.size(-2));
+  p.nlon_in = static_cast<int>(x.size(-1));
+  p.planes = x.numel() / (x.size(-2) * x.size(-1));
+  p.K = static_cast<int>(K);
+  p.nlat_out = static_cast<int>(nlat_out);
+  p.nlon_out = static_cast<int>(nlon_out);
+  p.nnz = idx.size(0);
+  p.bf16 = x.scalar_type() == at::kBFloat16 ? 1 : 0;
+  launch_disco(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+}
+
+void check_disco_device(const char* op, const at::Tensor& x, int64_t nlat_out, int64_t nlon_out) {
+  TORCH_CHECK(x.size(-1) * 4 <= kDiscoLdsBytes, op, ": nlon_in must be at most ", kDiscoLdsBytes / 4,
+              " on the device (one input row per LDS chunk), got ", x.size(-1));
+  TORCH_CHECK(nlon_out < (int64_t(1) << 28) && nlat_out < (int64_t(1) << 30), op, ": output grid too large");
+}
+
+at::Tensor disco_cuda(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+                      int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  check_disco("disco", x, row_ptr, idx, val, K, nlat_out, nlon_out);
+  check_disco_device("disco", x, nlat_out, nlon_out);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(disco_out_shape(x, K, nlat_out, nlon_out), x.options());
+  disco_run(x, row_ptr, idx, val, K, nlat_out, nlon_out, y);
+  return checked(y, "disco");
+}
+
+at::Tensor& disco_out_cuda(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx,
+                           const at::Tensor& val, int64_t K, int64_t nlat_out, int64_t nlon_out, at::Tensor& out) {
+  check_disco("disco_out", x, row_ptr, idx, val, K, nlat_out, nlon_out);
+  check_disco_device("disco_out", x, nlat_out, nlon_out);
+  check_out(out, disco_out_shape(x, K, nlat_out, nlon_out), x, "disco_out");
+  check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 2 : 4, "disco_out");
+  const c10::DeviceGuard guard(x.device());
+  disco_run(x, row_ptr, idx, val, K, nlat_out, nlon_out, out);
+  checked(out, "disco_out");
+  return out;
+}
+
+at::Tensor disco_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t K,
+                      int64_t nlat_out, int64_t nlon_out) {
+  TORCH_CHECK(x.dim() >= 2, "disco: x must be [..., nlat_in, nlon_in]");
+  return at::empty(disco_out_shape(x, K, nlat_out, nlon_out), x.options());
+}
+
+at::Tensor& disco_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t,
+                           int64_t, at::Tensor& out) {
+  return out;
+}
+
+// Which instance and grid disco runs -- host only, no device; from disco_route, which launch_disco dispatches on:
+// "PT=4 rows=11 lds=63360 ptiles=16 wgs=2880 passes=2 items=3 threads=256".  nnz_max: the entry count the launch is
+// given (idx.numel(); only its range is checked).  The band of an output latitude is in the table, not in the
+// arguments, so whether a latitude is walked in chunks (band > rows) is not part of the answer.
+std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out, int64_t nlon_out,
+                       int64_t nnz_max, bool bf16) {
+  TORCH_CHECK(planes >= 1 && nlat_in >= 1 && nlon_in >= 1 && K >= 1 && nlat_out >= 1 && nlon_out >= 1 &&
+                  nlat_in * nlon_in < (int64_t(1) << 31) && nnz_max >= 0 && nnz_max < (int64_t(1) << 31),
+              "amd_dft.disco_info: sizes must be >= 1 and the input grid and nnz_max below 2^31");
+  TORCH_CHECK(nlon_in % nlon_out == 0, "amd_dft.disco_info: nlon_in must be a multiple of nlon_out");
+  TORCH_CHECK(nlon_in * 4 <= kDiscoLdsBytes, "amd_dft.disco_info: nlon_in must be at most ", kDiscoLdsBytes / 4);
+  const DiscoRoute r = disco_route(planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
+  return "PT=" + std::to_string(r.pt) + " rows=" + std::to_string(r.rows) + " lds=" + std::to_string(r.lds) +
+         " ptiles=" + std::to_string(r.ptiles) + " wgs=" + std::to_string(r.wgs) +
+         " passes=" + std::to_string(r.passes) + " items=" + std::to_string(kDiscoItems) +
+         " threads=" + std::to_string(kDiscoThreads) + (bf16 ? " bf16=1" : "");
+}
+
 // ------------------------------------------------------------------ SFNO per-degree channel mixing
 // c [B, Cin, L, M, 2] fp32 (spherical harmonic coefficients, complex as trailing re/im), w [Cin, Cout, L, 2] fp32
 // -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
@@ -1525,6 +1691,12 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
         "-> Tensor(a!)");
   m.def("legendre_vec_info(int Q, int R, int M, int cols, int tri, bool bf16=False) -> str",
         &amd_dft::legendre_vec_info);
+  m.def("disco(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out) -> Tensor");
+  m.def("disco_out(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out, Tensor(a!) out) "
+        "-> Tensor(a!)");
+  m.def("disco_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int nnz_max, "
+        "bool bf16=False) -> str",
+        &amd_dft::disco_info);
   m.def("sfno_mix(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor");
   m.def("sfno_mix_out(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
@@ -1554,6 +1726,8 @@ TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
   m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cuda));
   m.impl("legendre_vec", AMD_DFT_TRACED("amd_dft::legendre_vec", amd_dft::legendre_vec_cuda));
   m.impl("legendre_vec_out", AMD_DFT_TRACED("amd_dft::legendre_vec_out", amd_dft::legendre_vec_out_cuda));
+  m.impl("disco", AMD_DFT_TRACED("amd_dft::disco", amd_dft::disco_cuda));
+  m.impl("disco_out", AMD_DFT_TRACED("amd_dft::disco_out", amd_dft::disco_out_cuda));
   m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cuda));
   m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cuda));
 }
@@ -1580,6 +1754,8 @@ TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
   m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cpu));
   m.impl("legendre_vec", AMD_DFT_TRACED("amd_dft::legendre_vec", amd_dft::legendre_vec_cpu));
   m.impl("legendre_vec_out", AMD_DFT_TRACED("amd_dft::legendre_vec_out", amd_dft::legendre_vec_out_cpu));
+  m.impl("disco", AMD_DFT_TRACED("amd_dft::disco", amd_dft::disco_cpu));
+  m.impl("disco_out", AMD_DFT_TRACED("amd_dft::disco_out", amd_dft::disco_out_cpu));
   m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cpu));
   m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cpu));
 }
@@ -1606,6 +1782,8 @@ TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
   m.impl("legendre_out", &amd_dft::legendre_out_meta);
   m.impl("legendre_vec", &amd_dft::legendre_vec_meta);
   m.impl("legendre_vec_out", &amd_dft::legendre_vec_out_meta);
+  m.impl("disco", &amd_dft::disco_meta);
+  m.impl("disco_out", &amd_dft::disco_out_meta);
   m.impl("sfno_mix", &amd_dft::sfno_mix_meta);
   m.impl("sfno_mix_out", &amd_dft::sfno_mix_out_meta);
 }

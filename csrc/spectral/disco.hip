@@ -1,0 +1,260 @@
+// Discrete-continuous (DISCO) convolution on the sphere, the gather half: a sparse, longitude-invariant filter
+// tensor in CSR applied to every output longitude of a row,
+//
+//   y[n, p, k', j'] = sum_e val[e] * x[n, k_e, (d_e + s j') mod nlon_in],   e in [row_ptr[r], row_ptr[r + 1]),
+//   r = p * nlat_out + k',  idx[e] = k_e * nlon_in + d_e sorted within a row,  s = nlon_in / nlon_out.
+//
+// bf16 or fp32 x and y, fp32 val, fp32 accumulation, one rounding at a bf16 store.
+//
+// A workgroup owns one output latitude k' and PT planes (disco_route in spectral.h).  It reads the band of input rows
+// [k_lo, k_hi] that the K rows (p, k') touch from the table itself -- the first and the last entry of each row, 2 K
+// uniform loads -- and stages that band of its planes into LDS as fp32, once for all K basis rows.  Lanes are
+// (plane, j'), kDiscoItems of them per lane and pass.  The entry stream (idx, val) is the same for every lane: it is
+// fetched with uniform (scalar) loads, four entries ahead, and walked in table order, so the summation order of an
+// output depends on its row alone: results are bit-identical run to run, and no atomics are involved.
+//
+// Longitude wrap: the current input row's start is tracked as the stream advances (idx is sorted, so it only moves
+// forward: scalar compare-and-add, no division), which gives d_e; lane j' reads LDS word idx - base + s j', less
+// nlon_in where d_e >= nlon_in - s j' (one compare and select per entry and lane, no integer modulo).
+//
+// A band taller than the LDS chunk (`rows` of the route) is walked in row chunks: for each basis row p and pass the
+// chunks of [k_lo(p), k_hi(p)] are staged one after the other and the entry pointer carries on where the previous
+// chunk stopped, the accumulators staying in registers -- the order of the sum is unchanged.  The band is then
+// staged once per (p, pass) instead of once per workgroup.
+//
+// Nothing outside x, the table and y is touched whatever the table holds: row_ptr values are clamped to [0, nnz],
+// an entry below the chunk is skipped and one at or above its end stops the walk, so every LDS word read was written
+// by this launch.  Rows near the poles carry about nlon_in * band entries, rows near the equator about band^2:
+// workgroups are numbered from both poles inwards, all plane tiles of a latitude together, so the heavy rows start
+// first.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "spectral.h"
+
+namespace amd_dft {
+namespace {
+
+constexpr int kNT = kDiscoThreads;
+constexpr int kR = kDiscoItems;
+
+__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float(static_cast<uint32_t>(h) << 16); }
+__device__ __forceinline__ uint16_t f2bf(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+struct Args {
+  const void* x;
+  const int32_t* row_ptr;
+  const int32_t* idx;
+  const float* val;
+  void* y;
+  int64_t planes;
+  int nlat_in, nlon_in, K, nlat_out, nlon_out, s, nnz, rows, ptiles;
+};
+
+// rows [c0, c1) of the workgroup's planes -> lds[pl][row - c0][nlon_in] as fp32; planes past the end are not staged
+// (no lane reads them)
+template <bool BF, int PT>
+__device__ __forceinline__ void stage(const Args& a, float* lds, int64_t plane0, int c0, int c1, int plane_stride) {
+  const int n = (c1 - c0) * a.nlon_in;
+  const int64_t pin = static_cast<int64_t>(a.nlat_in) * a.nlon_in;
+#pragma unroll
+  for (int pl = 0; pl < PT; ++pl) {
+    if (plane0 + pl >= a.planes) break;
+    const int64_t g0 = (plane0 + pl) * pin + static_cast<int64_t>(c0) * a.nlon_in;
+    float* d = lds + pl * plane_stride;
+    if constexpr (BF) {
+      const uint16_t* xb = static_cast<const uint16_t*>(a.x) + g0;
+#pragma unroll 4
+      for (int i = threadIdx.x; i < n; i += kNT) d[i] = bf2f(xb[i]);
+    } else {
+      const float* xf = static_cast<const float*>(a.x) + g0;
+#pragma unroll 4
+      for (int i = threadIdx.x; i < n; i += kNT) d[i] = xf[i];
+    }
+  }
+}
+
+// Entries [e, e1) with idx < lim, in table order; base = c0 * nlon_in is LDS word 0 of a plane.  Returns the entry
+// it stopped at.  lane[r]: the lane's LDS offset pl * plane_stride + s j' of item r; thr[r] = nlon_in - s j'.
+template <int RA>
+__device__ __forceinline__ int walk(const Args& a, const float* lds, int e, int e1, int base, int lim,
+                                    const int (&lane)[kR], const int (&thr)[kR], float (&acc)[kR]) {
+  const int W = a.nlon_in;
+  int row_start = base;
+  auto one = [&](int id, float v) {
+    if (id < row_start) return;  // not a sorted table: never read outside the chunk
+    while (id - row_start >= W) row_start += W;
+    const int d = id - row_start;
+    const int off = id - base;
+#pragma unroll
+    for (int r = 0; r < RA; ++r) {
+      const int w = off + lane[r] - (d >= thr[r] ? W : 0);
+      acc[r] = fmaf(v, lds[w], acc[r]);
+    }
+  };
+  while (e + 4 <= e1) {
+    const int i0 = uni(a.idx[e]), i1 = uni(a.idx[e + 1]), i2 = uni(a.idx[e + 2]), i3 = uni(a.idx[e + 3]);
+    if (i0 >= lim || i1 >= lim || i2 >= lim || i3 >= lim) break;
+    const float v0 = a.val[e], v1 = a.val[e + 1], v2 = a.val[e + 2], v3 = a.val[e + 3];
+    one(i0, v0);
+    one(i1, v1);
+    one(i2, v2);
+    one(i3, v3);
+    e += 4;
+  }
+  while (e < e1) {
+    const int id = uni(a.idx[e]);
+    if (id >= lim) break;
+    one(id, a.val[e]);
+    ++e;
+  }
+  return e;
+}
+
+template <bool BF, int PT>
+__global__ void __launch_bounds__(kNT) disco_kernel(const Args a) {
+  extern __shared__ __attribute__((aligned(16))) float disco_lds[];
+  // heavy rows first: latitudes from both poles inwards, the plane tiles of one latitude together
+  const int lin = blockIdx.x / a.ptiles;
+  const int kp = (lin & 1) ? a.nlat_out - 1 - (lin >> 1) : (lin >> 1);
+  const int64_t plane0 = static_cast<int64_t>(blockIdx.x % a.ptiles) * PT;
+  const int W = a.nlon_in;
+  const int plane_stride = a.rows * W;
+  const int nitems = PT * a.nlon_out;
+
+  auto row_range = [&](int p, int& e0, int& e1) {
+    const int r = p * a.nlat_out + kp;
+    e0 = min(max(uni(a.row_ptr[r]), 0), a.nnz);
+    e1 = min(max(uni(a.row_ptr[r + 1]), e0), a.nnz);
+  };
+  auto band = [&](int e0, int e1, int& lo, int& hi) {  // input rows of a non-empty entry range
+    lo = min(max(uni(a.idx[e0]) / W, 0), a.nlat_in - 1);
+    hi = min(max(uni(a.idx[e1 - 1]) / W, lo), a.nlat_in - 1);
+  };
+
+  int klo = a.nlat_in, khi = -1;
+  for (int p = 0; p < a.K; ++p) {
+    int e0, e1;
+    row_range(p, e0, e1);
+    if (e1 > e0) {
+      int lo, hi;
+      band(e0, e1, lo, hi);
+      klo = min(klo, lo);
+      khi = max(khi, hi);
+    }
+  }
+  const bool single = khi - klo + 1 <= a.rows;  // also when every row is empty
+  if (single && khi >= klo) {
+    stage<BF, PT>(a, disco_lds, plane0, klo, khi + 1, plane_stride);
+    __syncthreads();
+  }
+
+  for (int p = 0; p < a.K; ++p) {
+    int e0, e1;
+    row_range(p, e0, e1);
+    int plo = klo, phi = khi;
+    if (!single && e1 > e0) band(e0, e1, plo, phi);
+    if (e1 <= e0) phi = plo - 1;
+    for (int item0 = 0; item0 < nitems; item0 += kNT * kR) {
+      int lane[kR], thr[kR], jo[kR], pls[kR];
+      bool ok[kR];
+      float acc[kR];
+#pragma unroll
+      for (int r = 0; r < kR; ++r) {
+        int item = item0 + r * kNT + static_cast<int>(threadIdx.x);
+        int pl = item / a.nlon_out;
+        ok[r] = item < nitems && plane0 + pl < a.planes;
+        if (!ok[r]) {  // an idle lane follows item 0: plane0 is always there
+          item = 0;
+          pl = 0;
+        }
+        const int j = item - pl * a.nlon_out;
+        jo[r] = j;
+        pls[r] = pl;
+        lane[r] = pl * plane_stride + a.s * j;
+        thr[r] = W - a.s * j;
+        acc[r] = 0.f;
+      }
+      const int left = nitems - item0;
+      const int ra = left >= kR * kNT ? kR : (left + kNT - 1) / kNT;  // slices of kNT items with any item
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kR; ++r) any |= ok[r];
+      const bool busy = __builtin_amdgcn_ballot_w64(any) != 0;  // a wave without items still meets the barriers
+      int e = e0;
+      for (int c0 = plo; c0 <= phi; c0 += a.rows) {
+        const int c1 = min(c0 + a.rows, phi + 1);
+        if (!single) {
+          __syncthreads();
+          stage<BF, PT>(a, disco_lds, plane0, c0, c1, plane_stride);
+          __syncthreads();
+        }
+        const int base = c0 * W, lim = c1 * W;
+        if (!busy) continue;
+        if (ra == 1) e = walk<1>(a, disco_lds, e, e1, base, lim, lane, thr, acc);
+        else if (ra == 2) e = walk<2>(a, disco_lds, e, e1, base, lim, lane, thr, acc);
+        else e = walk<kR>(a, disco_lds, e, e1, base, lim, lane, thr, acc);
+        if (single) break;
+      }
+#pragma unroll
+      for (int r = 0; r < kR; ++r) {
+        if (!ok[r]) continue;
+        const int64_t o = (((plane0 + pls[r]) * a.K + p) * a.nlat_out + kp) * a.nlon_out + jo[r];
+        if constexpr (BF) static_cast<uint16_t*>(a.y)[o] = f2bf(acc[r]);
+        else static_cast<float*>(a.y)[o] = acc[r];
+      }
+    }
+  }
+}
+
+template <bool BF, int PT>
+void launch(const Args& a, const DiscoRoute& r, hipStream_t st) {
+  hipLaunchKernelGGL((disco_kernel<BF, PT>), dim3(static_cast<uint32_t>(r.wgs)), dim3(kNT),
+                     static_cast<size_t>(r.lds), st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: disco: launch: ") + hipGetErrorString(e));
+}
+
+}  // namespace
+
+void launch_disco(const DiscoLaunch& p, void* stream) {
+  if (p.planes <= 0 || p.nlat_out <= 0 || p.nlon_out <= 0 || p.K <= 0) return;
+  if (p.nlat_in < 1 || p.nlon_in < 1 || p.nlon_in % p.nlon_out != 0 || p.nnz < 0 || p.nnz >= (int64_t(1) << 31) ||
+      static_cast<int64_t>(p.nlat_in) * p.nlon_in >= (int64_t(1) << 31) ||
+      static_cast<int64_t>(p.K) * p.nlat_out >= (int64_t(1) << 31) - 1)
+    throw std::invalid_argument("amd_dft: disco: bad launch (nlon_in % nlon_out, sizes below 2^31)");
+  const DiscoRoute r = disco_route(p.planes, p.nlat_in, p.nlon_in, p.K, p.nlat_out, p.nlon_out, p.nnz, p.bf16 != 0);
+  if (r.lds > kDiscoLdsBytes) throw std::invalid_argument("amd_dft: disco: an input row does not fit the LDS chunk");
+  if (r.wgs >= (int64_t(1) << 31) || 4 * static_cast<int64_t>(p.nlon_out) >= (int64_t(1) << 31))
+    throw std::invalid_argument("amd_dft: disco: too many workgroups");
+  Args a;
+  a.x = p.x;
+  a.row_ptr = p.row_ptr;
+  a.idx = p.idx;
+  a.val = p.val;
+  a.y = p.y;
+  a.planes = p.planes;
+  a.nlat_in = p.nlat_in;
+  a.nlon_in = p.nlon_in;
+  a.K = p.K;
+  a.nlat_out = p.nlat_out;
+  a.nlon_out = p.nlon_out;
+  a.s = p.nlon_in / p.nlon_out;
+  a.nnz = static_cast<int>(p.nnz);
+  a.rows = r.rows;
+  a.ptiles = static_cast<int>(r.ptiles);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p.bf16) {
+    if (r.pt == 4) launch<true, 4>(a, r, st);
+    else launch<true, 1>(a, r, st);
+  } else {
+    if (r.pt == 4) launch<false, 4>(a, r, st);
+    else launch<false, 1>(a, r, st);
+  }
+}
+
+}  // namespace amd_dft

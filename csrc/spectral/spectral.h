@@ -452,6 +452,53 @@ inline InstanceNormRoute instance_norm_route(int64_t planes, int64_t P, bool bf1
 }
 void launch_instance_norm(const InstanceNormLaunch& p, void* stream);
 
+// ---- Discrete-continuous (DISCO) convolution on the sphere, the gather half (disco.hip):
+//   y[n, p, k', j'] = sum_e val[e] * x[n, k_e, (d_e + s j') mod nlon_in],  e over CSR row p * nlat_out + k',
+//   idx[e] = k_e * nlon_in + d_e sorted within a row, s = nlon_in / nlon_out
+struct DiscoLaunch {
+  const void* x = nullptr;         // [planes, nlat_in, nlon_in] fp32 (bf16 if bf16), element-aligned
+  const int32_t* row_ptr = nullptr;  // [K * nlat_out + 1]
+  const int32_t* idx = nullptr;    // [nnz]
+  const float* val = nullptr;      // [nnz]
+  void* y = nullptr;               // [planes, K, nlat_out, nlon_out], x's dtype
+  int64_t planes = 0;
+  int nlat_in = 0, nlon_in = 0, K = 0, nlat_out = 0, nlon_out = 0;
+  int64_t nnz = 0;
+  int bf16 = 0;
+};
+// The route of a call (host only; launch_disco and the disco_info op both answer from here).  A workgroup of
+// kDiscoThreads owns one output latitude and PT planes and holds `rows` input rows of each as fp32 in LDS.  PT = 4
+// where four planes of at least kDiscoMinRows rows fit kDiscoLdsBytes and there are four planes, else 1.  The band of
+// an output latitude is read from the table by the kernel; where it is taller than `rows` it is walked in chunks.
+constexpr int kDiscoThreads = 256;
+constexpr int kDiscoItems = 3;                  // outputs per lane and pass
+constexpr int64_t kDiscoLdsBytes = 64 * 1024;   // two workgroups per CU
+constexpr int kDiscoMinRows = 8;
+struct DiscoRoute {
+  int pt;          // planes per workgroup: 1 or 4
+  int rows;        // input rows per plane in LDS (the chunk)
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t ptiles;  // plane tiles
+  int64_t wgs;     // nlat_out * ptiles
+  int passes;      // ceil(pt * nlon_out / (kDiscoThreads * kDiscoItems))
+};
+inline DiscoRoute disco_route(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t /*K*/, int64_t nlat_out,
+                              int64_t nlon_out, int64_t /*nnz_max*/, bool /*bf16*/) {
+  DiscoRoute r{};
+  const int64_t row = nlon_in * 4;
+  r.pt = (planes >= 4 && 4 * kDiscoMinRows * row <= kDiscoLdsBytes) ? 4 : 1;
+  int64_t rows = kDiscoLdsBytes / (r.pt * row);
+  if (rows < 1) rows = 1;
+  if (rows > nlat_in) rows = nlat_in;
+  r.rows = static_cast<int>(rows);
+  r.lds = r.pt * rows * row;
+  r.ptiles = (planes + r.pt - 1) / r.pt;
+  r.wgs = nlat_out * r.ptiles;
+  r.passes = static_cast<int>((r.pt * nlon_out + kDiscoThreads * kDiscoItems - 1) / (kDiscoThreads * kDiscoItems));
+  return r;
+}
+void launch_disco(const DiscoLaunch& p, void* stream);
+
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {
   const void* x = nullptr;        // [O, L, C] bf16 (fp32 if f32) stored residual stream

@@ -51,7 +51,7 @@ import torch.nn.functional as F
 from .._loader import load_plugins
 from .dft import _from_complex
 
-__all__ = ["legendre_tables", "sht", "isht", "sht_tables", "legendre_split", "GRIDS",
+__all__ = ["legendre_tables", "sht", "isht", "sht_tables", "legendre_split", "GRIDS", "quadrature", "colatitudes",
            "vector_legendre_tables", "vsht", "ivsht", "vsht_tables"]
 
 GRIDS = ("equiangular", "legendre-gauss")
@@ -79,19 +79,32 @@ def _clenshaw_curtis(n: int) -> Tuple[np.ndarray, np.ndarray]:
     return np.cos(theta), c * w / N
 
 
+def quadrature(nlat: int, grid: str = "equiangular") -> Tuple[np.ndarray, np.ndarray]:
+    """(nodes cos theta_k [nlat], north to south; weights w_k [nlat], summing to 2) of a latitude grid, float64."""
+    if grid == "legendre-gauss":
+        x, w = np.polynomial.legendre.leggauss(nlat)
+        return x[::-1].copy(), w[::-1].copy()
+    if grid == "equiangular":
+        return _clenshaw_curtis(nlat)
+    raise ValueError(f"grid must be one of {GRIDS}, got {grid!r}")
+
+
+def colatitudes(nlat: int, grid: str = "equiangular") -> Tuple[np.ndarray, np.ndarray]:
+    """(colatitudes theta_k [nlat], north to south; weights w_k [nlat]) of ``quadrature``'s grid.  The equiangular
+    theta_k = pi k / (nlat - 1) are taken as they are defined, not through arccos, which loses digits at the poles."""
+    x, w = quadrature(nlat, grid)
+    if grid == "equiangular":
+        return np.pi * np.arange(nlat, dtype=np.float64) / (nlat - 1), w
+    return np.arccos(x), w
+
+
 def legendre_tables(nlat: int, lmax: int, mmax: int, grid: str = "equiangular"):
     """(nodes cos theta_k [nlat], north to south; weights w_k [nlat]; Pb [mmax, lmax, nlat]), all float64 numpy.
 
     Pb[m, l, k] = Pb_l^m(cos theta_k), zero where l < m, by the standard recurrences carried in fp64:
     Pb_m^m = -sqrt((2m + 1) / (2m)) sin(theta) Pb_{m-1}^{m-1}, then in l
     Pb_l^m = sqrt((4 l^2 - 1) / (l^2 - m^2)) (x Pb_{l-1}^m - sqrt(((l - 1)^2 - m^2) / (4 (l - 1)^2 - 1)) Pb_{l-2}^m)."""
-    if grid == "legendre-gauss":
-        x, w = np.polynomial.legendre.leggauss(nlat)
-        x, w = x[::-1].copy(), w[::-1].copy()
-    elif grid == "equiangular":
-        x, w = _clenshaw_curtis(nlat)
-    else:
-        raise ValueError(f"grid must be one of {GRIDS}, got {grid!r}")
+    x, w = quadrature(nlat, grid)
     if lmax < 1 or mmax < 1:
         raise ValueError("lmax and mmax must be >= 1")
     s = np.sqrt(np.maximum(0.0, 1.0 - x * x))
