@@ -50,6 +50,7 @@
 #include <type_traits>
 
 #include "../fft/dev_check.h"
+#include "bf16_pack.h"
 #include "gelu.h"
 #include "gemm.h"
 #include "../ops/tuning.h"
@@ -68,14 +69,6 @@ constexpr int kThreads = 512;
 constexpr int kRegion = 128 * 128;     // 128 rows x 128 B (64 bf16 of K)
 constexpr int kStage = 4 * kRegion;    // one K-tile: 64 KB
 constexpr int kLds = 2 * kStage;       // two K-tiles: 128 KB
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = static_cast<__bf16>(a);
-  v[1] = static_cast<__bf16>(b);
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + 16 * (chunk ^ (row & 7)); }
 

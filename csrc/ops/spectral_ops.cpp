@@ -660,6 +660,31 @@ at::Tensor fno_c2r_meta(const at::Tensor& yw, int64_t W, std::optional<at::Scala
   return at::empty({yw.size(0), yw.size(1), yw.size(2), W}, yw.options().dtype(out_dtype.has_value() ? *out_dtype : at::kFloat));
 }
 
+// the checks legendre (vec = false) and legendre_vec share once the dtypes and ranks are known to fit: the extents
+// of x against the table's (both tables of legendre_vec have one shape), tri, and the split forms that were given
+void check_legendre_common(bool vec, const at::Tensor& x, const at::Tensor& table,
+                           std::initializer_list<const c10::optional<at::Tensor>*> splits, int64_t tri) {
+  const char* op = vec ? "legendre_vec" : "legendre";
+  const char* tbl = vec ? "the tables " : "the table ";
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(x.size(-3) == table.size(2), op, ": x has ", x.size(-3), " points along the transformed dim, ", tbl,
+              table.size(2));
+  TORCH_CHECK(x.size(-2) == table.size(0), op, ": mode counts differ: x has ", x.size(-2), ", ", tbl, table.size(0));
+  TORCH_CHECK(tri >= 0 && tri <= 2, op, ": tri must be 0, 1 or 2");
+  TORCH_CHECK(table.size(0) < (1 << 30) && table.size(1) < (1 << 30) && table.size(2) >= 1 && table.size(2) < (1 << 30),
+              op, ": bad table size");
+  const int64_t Rp = (table.size(1) + 15) / 16 * 16, Qp = (table.size(2) + 31) / 32 * 32;
+  for (const c10::optional<at::Tensor>* ts : splits) {
+    if (!present(*ts)) continue;
+    TORCH_CHECK((*ts)->scalar_type() == at::kBFloat16 &&
+                    (*ts)->sizes() == at::IntArrayRef({bf16 ? 1 : 2, table.size(0), Rp, Qp}) &&
+                    (*ts)->device() == x.device(),
+                op, vec ? ": ta_split and tb_split" : ": table_split", " must be bfloat16 [", bf16 ? 1 : 2,
+                ", M, ceil16(R), ceil32(Q)] on the device of x (two planes for ",
+                vec ? "float32 tables" : "a float32 table", ", one for bfloat16)");
+  }
+}
+
 // ------------------------------------------------------------------ Legendre transform (latitude half of an SHT)
 // x [..., Q, M, 2] fp32 (complex as trailing re/im), table [M, R, Q] fp32 -> y [..., R, M, 2] fp32:
 //   y[n, r, m, :] = sum_q table[m, r, q] x[n, q, m, :]
@@ -679,20 +704,7 @@ void check_legendre(const at::Tensor& x, const at::Tensor& table, const c10::opt
               "legendre: x and table must both be float32 or both be bfloat16, got ", x.scalar_type(), " and ",
               table.scalar_type());
   TORCH_CHECK(x.dim() >= 3 && x.size(-1) == 2 && table.dim() == 3, "legendre: x [..., Q, M, 2], table [M, R, Q]");
-  TORCH_CHECK(x.size(-3) == table.size(2), "legendre: x has ", x.size(-3), " points along the transformed dim, the table ",
-              table.size(2));
-  TORCH_CHECK(x.size(-2) == table.size(0), "legendre: mode counts differ: x has ", x.size(-2), ", the table ",
-              table.size(0));
-  TORCH_CHECK(tri >= 0 && tri <= 2, "legendre: tri must be 0, 1 or 2");
-  TORCH_CHECK(table.size(0) < (1 << 30) && table.size(1) < (1 << 30) && table.size(2) >= 1 && table.size(2) < (1 << 30),
-              "legendre: bad table size");
-  if (present(ts)) {
-    const int64_t Rp = (table.size(1) + 15) / 16 * 16, Qp = (table.size(2) + 31) / 32 * 32;
-    TORCH_CHECK(ts->scalar_type() == at::kBFloat16 &&
-                    ts->sizes() == at::IntArrayRef({bf16 ? 1 : 2, table.size(0), Rp, Qp}) && ts->device() == x.device(),
-                "legendre: table_split must be bfloat16 [", bf16 ? 1 : 2,
-                ", M, ceil16(R), ceil32(Q)] on the device of x (two planes for a float32 table, one for bfloat16)");
-  }
+  check_legendre_common(false, x, table, {&ts}, tri);
 }
 
 std::vector<int64_t> legendre_out_shape(const at::Tensor& x, const at::Tensor& table) {
@@ -727,47 +739,58 @@ at::Tensor& legendre_out_cpu(const at::Tensor& x, const at::Tensor& table, const
   return out;
 }
 
-// the launch path of legendre and legendre_out: y is the contiguous result, aligned to one (re, im) pair (8 bytes
-// fp32, 4 bytes bf16: the kernel's stores)
-void legendre_run(const at::Tensor& x_, const at::Tensor& table_, const c10::optional<at::Tensor>& ts_, int64_t tri,
-                  const at::Tensor& y) {
-  const int64_t M = table_.size(0), R = table_.size(1), Q = table_.size(2);
+// a table as the kernel reads it: its split form where the caller gave one, else the table zero-padded to
+// [M, Rp, Qp] and split into bf16 planes [2, M, Rp, Qp] (a bf16 table: the padded table itself, [1, M, Rp, Qp])
+at::Tensor legendre_table_planes(bool vec, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
+                                 const at::Tensor& x, hipStream_t stream) {
+  if (present(ts)) return ts->contiguous();
+  TORCH_CHECK(table.device() == x.device(),
+              vec ? "legendre_vec: ta and tb must be on the device of x" : "legendre: table must be on the device of x");
+  const int64_t M = table.size(0), R = table.size(1), Q = table.size(2);
   const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
+  at::Tensor tp = at::constant_pad_nd(table, {0, Qp - Q, 0, Rp - R}).contiguous();
+  if (x.scalar_type() == at::kBFloat16) return tp.unsqueeze(0);
+  at::Tensor planes = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
+  if (tp.numel() > 0)
+    launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(planes.data_ptr()), tp.numel(),
+                      static_cast<int>(Qp), false, stream);
+  return planes;
+}
+
+// the launch path of legendre, legendre_vec (tb given: two tables) and their _out forms: y is the contiguous result,
+// aligned to one (re, im) pair (8 bytes fp32, 4 bytes bf16: the kernel's stores)
+void legendre_run(const at::Tensor& x_, const at::Tensor& ta, const c10::optional<at::Tensor>& tas,
+                  const at::Tensor* tb, const c10::optional<at::Tensor>& tbs, int64_t tri, const at::Tensor& y) {
+  const bool vec = tb != nullptr;
+  const int64_t M = ta.size(0), R = ta.size(1), Q = ta.size(2);
+  const int64_t plane = M * ((R + 15) / 16 * 16) * ((Q + 31) / 32 * 32);
   auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
   const bool bf16 = x_.scalar_type() == at::kBFloat16;
   at::Tensor x = x_.contiguous();
   // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
   if (reinterpret_cast<uintptr_t>(x.data_ptr()) % (bf16 ? 4 : 8) != 0) x = x.clone();
-  at::Tensor ts;
-  if (present(ts_)) {
-    ts = ts_->contiguous();
-  } else {
-    TORCH_CHECK(table_.device() == x.device(), "legendre: table must be on the device of x");
-    at::Tensor tp = at::constant_pad_nd(table_, {0, Qp - Q, 0, Rp - R}).contiguous();
-    if (bf16) {
-      ts = tp.unsqueeze(0);
-    } else {
-      ts = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
-      if (tp.numel() > 0)
-        launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
-                          static_cast<int>(Qp), false, stream);
-    }
-  }
+  at::Tensor ap = legendre_table_planes(vec, ta, tas, x, stream), bp;
+  if (vec) bp = legendre_table_planes(vec, *tb, tbs, x, stream);
   if (y.numel() == 0) return;
-  const int64_t N = x.numel() / (Q * M * 2);
-  TORCH_CHECK(N < (int64_t(1) << 31) / 16, "legendre: too many fields");
   LegendreLaunch p;
+  p.N = x.numel() / (Q * M * 2);  // the [Q, M, 2] planes of x: fields, or vec: 2 x fields
+  TORCH_CHECK(p.N < (int64_t(1) << 31) / 16, vec ? "legendre_vec" : "legendre", ": too many fields");
   p.x = x.data_ptr();
-  p.th = reinterpret_cast<const uint16_t*>(ts.data_ptr());
-  p.tl = bf16 ? nullptr : p.th + M * Rp * Qp;
+  p.th = reinterpret_cast<const uint16_t*>(ap.data_ptr());
+  p.tl = bf16 ? nullptr : p.th + plane;
+  if (vec) {
+    p.bh = reinterpret_cast<const uint16_t*>(bp.data_ptr());
+    p.bl = bf16 ? nullptr : p.bh + plane;
+  }
   p.y = y.data_ptr();
   p.bf16 = bf16 ? 1 : 0;
-  p.N = N;
+  p.vec = vec ? 1 : 0;
   p.Q = static_cast<int>(Q);
   p.R = static_cast<int>(R);
   p.M = static_cast<int>(M);
   p.tri = static_cast<int>(tri);
-  launch_legendre(p, stream);
+  if (vec) launch_legendre_vec(p, stream);
+  else launch_legendre(p, stream);
 }
 
 at::Tensor legendre_cuda(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
@@ -775,7 +798,7 @@ at::Tensor legendre_cuda(const at::Tensor& x, const at::Tensor& table, const c10
   check_legendre(x, table, ts, tri);
   const c10::DeviceGuard guard(x.device());
   at::Tensor y = at::empty(legendre_out_shape(x, table), x.options());
-  legendre_run(x, table, ts, tri, y);
+  legendre_run(x, table, ts, nullptr, c10::nullopt, tri, y);
   return checked(y, "legendre");
 }
 
@@ -785,7 +808,7 @@ at::Tensor& legendre_out_cuda(const at::Tensor& x, const at::Tensor& table, cons
   check_out(out, legendre_out_shape(x, table), x, "legendre_out");
   check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 4 : 8, "legendre_out");
   const c10::DeviceGuard guard(x.device());
-  legendre_run(x, table, ts, tri, out);
+  legendre_run(x, table, ts, nullptr, c10::nullopt, tri, out);
   checked(out, "legendre_out");
   return out;
 }
@@ -801,18 +824,27 @@ at::Tensor& legendre_out_meta(const at::Tensor&, const at::Tensor&, const c10::o
 
 // Which tiling legendre runs for (Q, R, M, real columns = 2 x fields, tri) -- host only, no device (the companion
 // of fno_pointwise_info): "mfma MT=8 CT=2 slabs=23 rtiles=4 rgroups=1 mgroups=8 ctiles=3 lds=41472 wgs=24 tri=1";
-// bf16: the same tiling with the bf16 instances' LDS bytes and a trailing " bf16=1"
-std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
-  TORCH_CHECK(Q >= 1 && R >= 1 && M >= 1 && cols >= 2 && cols % 2 == 0 && Q < (1 << 30) && R < (1 << 30) &&
+// bf16: the same tiling with the bf16 instances' LDS bytes and a trailing " bf16=1".  legendre_vec_info: the same
+// fields for legendre_vec, real columns = 4 x fields (fp32 has no MT=8 instance)
+std::string legendre_info_of(bool vec, int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
+  const char* op = vec ? "amd_dft.legendre_vec_info" : "amd_dft.legendre_info";
+  const int64_t unit = vec ? 4 : 2;
+  TORCH_CHECK(Q >= 1 && R >= 1 && M >= 1 && cols >= unit && cols % unit == 0 && Q < (1 << 30) && R < (1 << 30) &&
                   M < (1 << 30) && cols < (int64_t(1) << 31) / 8,
-              "amd_dft.legendre_info: Q, R, M must be >= 1 and cols a positive even count");
-  TORCH_CHECK(tri >= 0 && tri <= 2, "amd_dft.legendre_info: tri must be 0, 1 or 2");
-  const LegendreRoute r = legendre_route(Q, R, M, cols, static_cast<int>(tri), bf16);
+              op, ": Q, R, M must be >= 1 and cols a positive ", vec ? "multiple of 4" : "even count");
+  TORCH_CHECK(tri >= 0 && tri <= 2, op, ": tri must be 0, 1 or 2");
+  const LegendreRoute r = legendre_route(Q, R, M, cols, static_cast<int>(tri), bf16, vec);
   return "mfma MT=" + std::to_string(r.mt) + " CT=" + std::to_string(r.ct) + " slabs=" + std::to_string(r.slabs) +
          " rtiles=" + std::to_string(r.rtiles) + " rgroups=" + std::to_string(r.rgroups) +
          " mgroups=" + std::to_string(r.mgroups) + " ctiles=" + std::to_string(r.ctiles) +
          " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri) +
          (bf16 ? " bf16=1" : "");
+}
+std::string legendre_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
+  return legendre_info_of(false, Q, R, M, cols, tri, bf16);
+}
+std::string legendre_vec_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
+  return legendre_info_of(true, Q, R, M, cols, tri, bf16);
 }
 
 // ------------------------------------------------------------------ vector Legendre transform (vector SHT)
@@ -834,22 +866,7 @@ void check_legendre_vec(const at::Tensor& x, const at::Tensor& ta, const at::Ten
   TORCH_CHECK(tb.sizes() == ta.sizes(), "legendre_vec: ta and tb must have the same shape, got ", ta.sizes(), " and ",
               tb.sizes());
   TORCH_CHECK(tb.device() == ta.device(), "legendre_vec: ta and tb must be on the same device");
-  TORCH_CHECK(x.size(-3) == ta.size(2), "legendre_vec: x has ", x.size(-3),
-              " points along the transformed dim, the tables ", ta.size(2));
-  TORCH_CHECK(x.size(-2) == ta.size(0), "legendre_vec: mode counts differ: x has ", x.size(-2), ", the tables ",
-              ta.size(0));
-  TORCH_CHECK(tri >= 0 && tri <= 2, "legendre_vec: tri must be 0, 1 or 2");
-  TORCH_CHECK(ta.size(0) < (1 << 30) && ta.size(1) < (1 << 30) && ta.size(2) >= 1 && ta.size(2) < (1 << 30),
-              "legendre_vec: bad table size");
-  const int64_t Rp = (ta.size(1) + 15) / 16 * 16, Qp = (ta.size(2) + 31) / 32 * 32;
-  for (const c10::optional<at::Tensor>* ts : {&tas, &tbs}) {
-    if (!present(*ts)) continue;
-    TORCH_CHECK((*ts)->scalar_type() == at::kBFloat16 &&
-                    (*ts)->sizes() == at::IntArrayRef({bf16 ? 1 : 2, ta.size(0), Rp, Qp}) &&
-                    (*ts)->device() == x.device(),
-                "legendre_vec: ta_split and tb_split must be bfloat16 [", bf16 ? 1 : 2,
-                ", M, ceil16(R), ceil32(Q)] on the device of x (two planes for float32 tables, one for bfloat16)");
-  }
+  check_legendre_common(true, x, ta, {&tas, &tbs}, tri);
 }
 
 at::Tensor legendre_vec_cpu(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
@@ -877,54 +894,12 @@ at::Tensor& legendre_vec_out_cpu(const at::Tensor& x, const at::Tensor& ta, cons
   return out;
 }
 
-// the launch path of legendre_vec and legendre_vec_out (y as for legendre_run)
-void legendre_vec_run(const at::Tensor& x_, const at::Tensor& ta_, const at::Tensor& tb_,
-                      const c10::optional<at::Tensor>& tas_, const c10::optional<at::Tensor>& tbs_, int64_t tri,
-                      const at::Tensor& y) {
-  const int64_t M = ta_.size(0), R = ta_.size(1), Q = ta_.size(2);
-  const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
-  auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
-  const bool bf16 = x_.scalar_type() == at::kBFloat16;
-  at::Tensor x = x_.contiguous();
-  // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % (bf16 ? 4 : 8) != 0) x = x.clone();
-  auto split = [&](const at::Tensor& t, const c10::optional<at::Tensor>& ts_) {
-    if (present(ts_)) return ts_->contiguous();
-    TORCH_CHECK(t.device() == x.device(), "legendre_vec: ta and tb must be on the device of x");
-    at::Tensor tp = at::constant_pad_nd(t, {0, Qp - Q, 0, Rp - R}).contiguous();
-    if (bf16) return tp.unsqueeze(0);
-    at::Tensor ts = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
-    if (tp.numel() > 0)
-      launch_split_bf16(tp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), tp.numel(),
-                        static_cast<int>(Qp), false, stream);
-    return ts;
-  };
-  at::Tensor tas = split(ta_, tas_), tbs = split(tb_, tbs_);
-  if (y.numel() == 0) return;
-  const int64_t N = x.numel() / (2 * Q * M * 2);
-  TORCH_CHECK(N < (int64_t(1) << 31) / 32, "legendre_vec: too many fields");
-  LegendreVecLaunch p;
-  p.x = x.data_ptr();
-  p.ah = reinterpret_cast<const uint16_t*>(tas.data_ptr());
-  p.al = bf16 ? nullptr : p.ah + M * Rp * Qp;
-  p.bh = reinterpret_cast<const uint16_t*>(tbs.data_ptr());
-  p.bl = bf16 ? nullptr : p.bh + M * Rp * Qp;
-  p.y = y.data_ptr();
-  p.bf16 = bf16 ? 1 : 0;
-  p.N = N;
-  p.Q = static_cast<int>(Q);
-  p.R = static_cast<int>(R);
-  p.M = static_cast<int>(M);
-  p.tri = static_cast<int>(tri);
-  launch_legendre_vec(p, stream);
-}
-
 at::Tensor legendre_vec_cuda(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
                              const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
   check_legendre_vec(x, ta, tb, tas, tbs, tri);
   const c10::DeviceGuard guard(x.device());
   at::Tensor y = at::empty(legendre_out_shape(x, ta), x.options());
-  legendre_vec_run(x, ta, tb, tas, tbs, tri, y);
+  legendre_run(x, ta, tas, &tb, tbs, tri, y);
   return checked(y, "legendre_vec");
 }
 
@@ -935,7 +910,7 @@ at::Tensor& legendre_vec_out_cuda(const at::Tensor& x, const at::Tensor& ta, con
   check_out(out, legendre_out_shape(x, ta), x, "legendre_vec_out");
   check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 4 : 8, "legendre_vec_out");
   const c10::DeviceGuard guard(x.device());
-  legendre_vec_run(x, ta, tb, tas, tbs, tri, out);
+  legendre_run(x, ta, tas, &tb, tbs, tri, out);
   checked(out, "legendre_vec_out");
   return out;
 }
@@ -949,21 +924,6 @@ at::Tensor& legendre_vec_out_meta(const at::Tensor&, const at::Tensor&, const at
                                   const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t,
                                   at::Tensor& out) {
   return out;
-}
-
-// Which tiling legendre_vec runs for (Q, R, M, real columns = 4 x fields, tri) -- host only, no device; the fields
-// of legendre_info, from legendre_vec_route (fp32 has no MT=8 instance)
-std::string legendre_vec_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int64_t tri, bool bf16) {
-  TORCH_CHECK(Q >= 1 && R >= 1 && M >= 1 && cols >= 4 && cols % 4 == 0 && Q < (1 << 30) && R < (1 << 30) &&
-                  M < (1 << 30) && cols < (int64_t(1) << 31) / 8,
-              "amd_dft.legendre_vec_info: Q, R, M must be >= 1 and cols a positive multiple of 4");
-  TORCH_CHECK(tri >= 0 && tri <= 2, "amd_dft.legendre_vec_info: tri must be 0, 1 or 2");
-  const LegendreRoute r = legendre_vec_route(Q, R, M, cols, static_cast<int>(tri), bf16);
-  return "mfma MT=" + std::to_string(r.mt) + " CT=" + std::to_string(r.ct) + " slabs=" + std::to_string(r.slabs) +
-         " rtiles=" + std::to_string(r.rtiles) + " rgroups=" + std::to_string(r.rgroups) +
-         " mgroups=" + std::to_string(r.mgroups) + " ctiles=" + std::to_string(r.ctiles) +
-         " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) + " tri=" + std::to_string(tri) +
-         (bf16 ? " bf16=1" : "");
 }
 
 // ------------------------------------------------------------------ DISCO convolution on the sphere (gather half)

@@ -53,6 +53,7 @@
 #include <string>
 #include <utility>
 
+#include "../nn/bf16_pack.h"
 #include "../nn/gelu.h"
 #include "../ops/tuning.h"
 #include "dft_gemm.h"
@@ -70,20 +71,6 @@ constexpr int kCH = kFnoWideChunk;  // pixels per unit
 constexpr int kPT = kCH / 16;       // MFMA pixel tiles per unit
 constexpr int kGT = 4;              // output tiles per group
 constexpr int kSlab = 32;           // input channels per conv slab
-
-// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = static_cast<__bf16>(a);
-  v[1] = static_cast<__bf16>(b);
-  return __builtin_bit_cast(uint32_t, v);
-}
-// hi = bf16(a, b); lo = bf16(a - hi.a, b - hi.b)
-__device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pk_bf16(a, b);
-  lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-}
 
 __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -17,6 +17,7 @@
 #include <string>
 #include <type_traits>
 
+#include "../nn/bf16_pack.h"
 #include "spectral.h"
 
 namespace amd_dft {
@@ -25,14 +26,6 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = static_cast<__bf16>(a);
-  v[1] = static_cast<__bf16>(b);
-  return __builtin_bit_cast(uint32_t, v);
-}
 // one (re, im) pair as the kernels hold it in memory (float2, or a packed bf16 pair) <-> float2
 __device__ __forceinline__ float2 pair_load(float2 v) { return v; }
 __device__ __forceinline__ float2 pair_load(uint32_t v) {

@@ -38,6 +38,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../nn/bf16_pack.h"
 #include "../nn/gelu.h"
 #include "spectral.h"
 
@@ -53,20 +54,6 @@ typedef __attribute__((address_space(3))) v4s lds_v4s;
 constexpr int kPX = 64;           // pixels per wave
 constexpr int kPT = kPX / 16;     // MFMA pixel tiles per wave
 constexpr int kGT = kPwGroupTiles;  // output tiles per group
-
-// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = static_cast<__bf16>(a);
-  v[1] = static_cast<__bf16>(b);
-  return __builtin_bit_cast(uint32_t, v);
-}
-// hi = bf16(a, b); lo = bf16(a - hi.a, b - hi.b)
-__device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pk_bf16(a, b);
-  lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-}
 
 template <bool BF, bool GELU>
 __device__ __forceinline__ void act2(float& a, float& b) {

@@ -38,12 +38,47 @@
 //
 // LDS per workgroup (legendre_lds_bytes): 41472 B at MT = 8, CT = 2; 20992 B at 4 x 2; 10752 B at 4 x 1
 // (bf16: 20736, 10496, 5376).
+//
+// Vector instances (VEC) -- the latitude half of a vector spherical harmonic transform (spheroidal / toroidal
+// coefficients of a tangential vector field and back):
+//   y[n, 0, r, m] = sum_q A[m, r, q] x[n, 0, q, m] - i B[m, r, q] x[n, 1, q, m]
+//   y[n, 1, r, m] = sum_q A[m, r, q] x[n, 1, q, m] + i B[m, r, q] x[n, 0, q, m]
+// x [N, 2, Q, M, 2], A, B [M, R, Q] real, y [N, 2, R, M, 2].  Forward: Q = nlat, R = lmax, (A, B) = w_k
+// (dPb/dtheta, m Pb / sin theta) / (l (l + 1)); inverse: Q = lmax, R = nlat, (A, B) the two derivative tables
+// transposed.
+// This is the kernel above (same precision, table format, tiling, staging, tri and edge rules) run over the 2 N
+// component planes of x, [2 N, Q, M, 2], with one addition.  A 16-column MFMA tile holds 4 fields: column =
+// 4 n + 2 component + (re | im).  In that order the operand of B, the other component rotated by -i (component 0:
+// (re, im) <- (im, -re) of x1) or +i (component 1: (re, im) <- (-im, re) of x0), is the SAME tile with its columns
+// permuted, column c <- column c ^ 3, negated where c & 3 is 1 or 2.  So the slab image is staged once; a lane
+// reads its plain fragment at column c and its rotated fragment at column c ^ 3 (the same 16 columns in another
+// order: as conflict-free as the plain read), flips the sign bits of the bf16 values (exact, in both planes of the
+// split), and
+//   acc[tile] += A . plain + B . rotated
+// lands both components of y in one accumulator tile.  Every A fragment is fetched once per slab and feeds
+// A.x0 -> y0 and A.x1 -> y1 of every tile, every B fragment B.rot(x1) -> y0 and B.rot'(x0) -> y1; the output goes
+// through the LDS image unchanged, since y is [2 N, R, M, 2].
+//   The alternative -- separate accumulators for B.x0 and B.x1, rotated in the output image -- would double the
+//   accumulators (128 VGPRs at 8 modes x 8 fields); rotated copies staged beside the plain ones would double the
+//   slab image.  The permuted read costs one more 16-byte LDS read and 4 v_xor per fragment and plane instead.
+// Accumulators: MW x 4 row tiles x CT column tiles x 4 registers, one set (the components share it): 64 at
+// MT = 8, CT = 2; 32 at 8 x 1 and 4 x 2; 16 at 4 x 1.
+// Shipped vector instances (VGPRs + AGPRs as compiled -> waves per SIMD; LDS bytes):
+//   fp32  4 x 2: 158 + 32 -> 2, 20992 B    4 x 1: 134 + 16 -> 3, 10752 B
+//   bf16  8 x 2: 173 + 64 -> 2, 20736 B    8 x 1: 136 + 32 -> 3, 10496 B    4 x 2: 102 + 32 -> 3, 10496 B
+//         4 x 1:  90 + 16 -> 4,  5376 B
+// fp32 has no 8-mode vector instance: two modes per wave hold 4 planes x 2 tables x 4 row tiles of fragments, 128
+// registers, and the 8 x 2 kernel compiles to 256 + 76 registers, one wave per SIMD (8 x 1: 216 + 32, no better
+// than 4 x 2, which reads each table half as often).
+//   tri applies to both tables (1: rows r < m are zero; 2: columns q < m are zero and x[q < m] is not read).
+//   The m = 0 plane of B is zero in a vector SHT, but the op takes any table, so it is multiplied like the rest.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <stdexcept>
 #include <string>
 
+#include "../nn/bf16_pack.h"
 #include "spectral.h"
 
 namespace amd_dft {
@@ -52,24 +87,21 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = static_cast<__bf16>(a);
-  v[1] = static_cast<__bf16>(b);
-  return __builtin_bit_cast(uint32_t, v);
-}
-// hi = bf16(a, b); lo = bf16(a - hi.a, b - hi.b)
-__device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pk_bf16(a, b);
-  lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
+// 8 bf16 with their sign bits flipped where sgn = 0x80008000 (sgn = 0: as they are)
+__device__ __forceinline__ bf16x8 flip(uint4 v, uint32_t sgn) {
+  v.x ^= sgn;
+  v.y ^= sgn;
+  v.z ^= sgn;
+  v.w ^= sgn;
+  return __builtin_bit_cast(bf16x8, v);
 }
 
-template <int CT, int MW, bool BF>
-__global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ x, const uint16_t* __restrict__ th,
-                                                       const uint16_t* __restrict__ tl, void* __restrict__ y,
-                                                       int64_t N, int Q, int R, int M, int Rp, int Qp, int tri) {
+// N counts the [Q, M, 2] planes of x and y (VEC: the 2 x fields component planes); bth, btl are read only if VEC
+template <int CT, int MW, bool BF, bool VEC>
+__global__ void __launch_bounds__(256)
+    legendre_kernel(const void* __restrict__ x, const uint16_t* __restrict__ ath, const uint16_t* __restrict__ atl,
+                    const uint16_t* __restrict__ bth, const uint16_t* __restrict__ btl, void* __restrict__ y,
+                    int64_t N, int Q, int R, int M, int Rp, int Qp, int tri) {
   constexpr int MT = 4 * MW;                       // modes per workgroup
   constexpr int NT = 8 * CT;                       // fields n per workgroup
   constexpr int NC = 16 * CT;                      // real columns per workgroup
@@ -88,6 +120,9 @@ __global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ 
   const int r0 = blockIdx.z * 16 * RT;
   const float2* x2 = reinterpret_cast<const float2*>(x);      // fp32: one (re, im) pair
   const uint32_t* xb2 = reinterpret_cast<const uint32_t*>(x);  // bf16: one (re, im) pair
+  // VEC: the rotated operand of this lane's column: column l15 ^ 3, negated where (l15 & 3) is 1 or 2
+  const int lrot = l15 ^ 3;
+  const uint32_t sgn = ((l15 ^ (l15 >> 1)) & 1) ? 0x80008000u : 0u;
 
   const int nslab = (Q + kLegSlab - 1) / kLegSlab;
   // tri = 2: all columns q < m0 are zero for every mode here; tri = 1: a row group below m0 is all zero
@@ -151,8 +186,10 @@ __global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ 
 
   if (s0 < nslab) load_slab(s0);
   for (int s = s0; s < nslab; ++s) {
-    // ---- this slab's table fragments (global, both planes): lane = T[m][rg + l15][32 s + 8 lq + 0..7]
+    // ---- this slab's table fragments (global, both planes, VEC: of both tables):
+    // lane = T[m][rg + l15][32 s + 8 lq + 0..7]
     uint4 ah[MW][RT], al[BF ? 1 : MW][BF ? 1 : RT];
+    uint4 bh[VEC ? MW : 1][VEC ? RT : 1], bl[VEC && !BF ? MW : 1][VEC && !BF ? RT : 1];
 #pragma unroll
     for (int j = 0; j < MW; ++j) {
       const int m = m0 + wv * MW + j;
@@ -161,8 +198,12 @@ __global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ 
       for (int rt = 0; rt < RT; ++rt) {
         if (live[j][rt] && mode_live) {
           const int64_t off = (static_cast<int64_t>(m) * Rp + r0 + 16 * rt + l15) * Qp + s * kLegSlab + 8 * lq;
-          ah[j][rt] = *reinterpret_cast<const uint4*>(th + off);
-          if constexpr (!BF) al[j][rt] = *reinterpret_cast<const uint4*>(tl + off);
+          ah[j][rt] = *reinterpret_cast<const uint4*>(ath + off);
+          if constexpr (VEC) bh[j][rt] = *reinterpret_cast<const uint4*>(bth + off);
+          if constexpr (!BF) {
+            al[j][rt] = *reinterpret_cast<const uint4*>(atl + off);
+            if constexpr (VEC) bl[j][rt] = *reinterpret_cast<const uint4*>(btl + off);
+          }
         }
       }
     }
@@ -190,18 +231,24 @@ __global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ 
     __syncthreads();
     // ---- the next slab's global loads, in flight during the MFMAs
     if (s + 1 < nslab) load_slab(s + 1);
-    // ---- MFMAs: live (mode, row tile) pairs only
+    // ---- MFMAs: live (mode, row tile) pairs only; per column tile the plain fragment (for A) and, VEC, the rotated
+    // one (for B): the other component's columns of the same tile, signs flipped where the rotation negates
 #pragma unroll
     for (int j = 0; j < MW; ++j) {
       const int ml = wv * MW + j;
       const bool mode_live = !(tri == 2 && s * kLegSlab + kLegSlab - 1 < m0 + ml);
       if (!mode_live) continue;
-      bf16x8 bh[CT], bl[BF ? 1 : CT];
+      bf16x8 ph[CT], pl[BF ? 1 : CT], rh[VEC ? CT : 1], rl[VEC && !BF ? CT : 1];
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         const char* src = smem + ml * MLS + (16 * ct + l15) * kLegXPitch + 16 * lq;
-        bh[ct] = *reinterpret_cast<const bf16x8*>(src);
-        if constexpr (!BF) bl[ct] = *reinterpret_cast<const bf16x8*>(src + PLANE);
+        const char* rot = smem + ml * MLS + (16 * ct + lrot) * kLegXPitch + 16 * lq;
+        ph[ct] = *reinterpret_cast<const bf16x8*>(src);
+        if constexpr (VEC) rh[ct] = flip(*reinterpret_cast<const uint4*>(rot), sgn);
+        if constexpr (!BF) {
+          pl[ct] = *reinterpret_cast<const bf16x8*>(src + PLANE);
+          if constexpr (VEC) rl[ct] = flip(*reinterpret_cast<const uint4*>(rot + PLANE), sgn);
+        }
       }
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
@@ -209,11 +256,23 @@ __global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ 
           const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[j][rt]);
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct) {
-            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bh[ct], acc[j][rt][ct], 0, 0, 0);
+            acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, ph[ct], acc[j][rt][ct], 0, 0, 0);
+            if constexpr (VEC) {
+              const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh[j][rt]);
+              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Bh, rh[ct], acc[j][rt][ct], 0, 0, 0);
+            }
             if constexpr (!BF) {
               const bf16x8 Al = __builtin_bit_cast(bf16x8, al[j][rt]);
-              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, bh[ct], acc[j][rt][ct], 0, 0, 0);
-              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, bl[ct], acc[j][rt][ct], 0, 0, 0);
+              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, ph[ct], acc[j][rt][ct], 0, 0, 0);
+              if constexpr (VEC) {
+                const bf16x8 Bl = __builtin_bit_cast(bf16x8, bl[j][rt]);
+                acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Bl, rh[ct], acc[j][rt][ct], 0, 0, 0);
+              }
+              acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, pl[ct], acc[j][rt][ct], 0, 0, 0);
+              if constexpr (VEC) {
+                const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh[j][rt]);
+                acc[j][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Bh, rl[ct], acc[j][rt][ct], 0, 0, 0);
+              }
             }
           }
         }
@@ -257,36 +316,44 @@ __global__ void __launch_bounds__(256) legendre_kernel(const void* __restrict__ 
   }
 }
 
-template <int CT, int MW, bool BF>
+template <int CT, int MW, bool BF, bool VEC>
 void launch_prec(const LegendreLaunch& p, const LegendreRoute& r, hipStream_t st) {
   const dim3 grid(r.mgroups, r.ctiles, r.rgroups);
-  hipLaunchKernelGGL((legendre_kernel<CT, MW, BF>), grid, dim3(256), static_cast<size_t>(r.lds), st, p.x, p.th, p.tl,
-                     p.y, p.N, p.Q, p.R, p.M, r.rtiles * 16, r.slabs * kLegSlab, p.tri);
+  hipLaunchKernelGGL((legendre_kernel<CT, MW, BF, VEC>), grid, dim3(256), static_cast<size_t>(r.lds), st, p.x, p.th,
+                     p.tl, p.bh, p.bl, p.y, p.N, p.Q, p.R, p.M, r.rtiles * 16, r.slabs * kLegSlab, p.tri);
 }
-template <int CT, int MW>
+// the 8 scalar and 6 vector instances: fp32 has no 8-mode vector kernel (one wave per SIMD, see the header;
+// legendre_route does not pick it)
+template <int CT, int MW, bool VEC>
 void launch_inst(const LegendreLaunch& p, const LegendreRoute& r, hipStream_t st) {
-  if (p.bf16) launch_prec<CT, MW, true>(p, r, st);
-  else launch_prec<CT, MW, false>(p, r, st);
+  if (p.bf16) launch_prec<CT, MW, true, VEC>(p, r, st);
+  else if constexpr (VEC && MW == 2) throw std::runtime_error("amd_dft: legendre_vec: no fp32 instance with 8 modes");
+  else launch_prec<CT, MW, false, VEC>(p, r, st);
+}
+
+template <bool VEC>
+void launch(const LegendreLaunch& p, void* stream) {
+  const std::string op = VEC ? "amd_dft: legendre_vec" : "amd_dft: legendre";
+  if (p.N == 0 || p.R == 0 || p.M == 0) return;
+  if (p.Q < 1) throw std::runtime_error(op + ": Q must be >= 1");
+  if (p.tri < 0 || p.tri > 2) throw std::runtime_error(op + ": tri must be 0, 1 or 2");
+  const LegendreRoute r = legendre_route(p.Q, p.R, p.M, 2 * p.N, p.tri, p.bf16 != 0, VEC);
+  if (r.ctiles > 65535 || r.rgroups > 65535) throw std::runtime_error(op + ": tensor too large");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (r.mt == 8) {
+    if (r.ct == 2) launch_inst<2, 2, VEC>(p, r, st);
+    else launch_inst<1, 2, VEC>(p, r, st);
+  } else {
+    if (r.ct == 2) launch_inst<2, 1, VEC>(p, r, st);
+    else launch_inst<1, 1, VEC>(p, r, st);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw std::runtime_error(op + " launch: " + hipGetErrorString(e));
 }
 
 }  // namespace
 
-void launch_legendre(const LegendreLaunch& p, void* stream) {
-  if (p.N == 0 || p.R == 0 || p.M == 0) return;
-  if (p.Q < 1) throw std::runtime_error("amd_dft: legendre: Q must be >= 1");
-  if (p.tri < 0 || p.tri > 2) throw std::runtime_error("amd_dft: legendre: tri must be 0, 1 or 2");
-  const LegendreRoute r = legendre_route(p.Q, p.R, p.M, 2 * p.N, p.tri, p.bf16 != 0);
-  if (r.ctiles > 65535 || r.rgroups > 65535) throw std::runtime_error("amd_dft: legendre: tensor too large");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (r.mt == 8) {
-    if (r.ct == 2) launch_inst<2, 2>(p, r, st);
-    else launch_inst<1, 2>(p, r, st);
-  } else {
-    if (r.ct == 2) launch_inst<2, 1>(p, r, st);
-    else launch_inst<1, 1>(p, r, st);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw std::runtime_error(std::string("amd_dft: legendre launch: ") + hipGetErrorString(e));
-}
+void launch_legendre(const LegendreLaunch& p, void* stream) { launch<false>(p, stream); }
+void launch_legendre_vec(const LegendreLaunch& p, void* stream) { launch<true>(p, stream); }
 
 }  // namespace amd_dft

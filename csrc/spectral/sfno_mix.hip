@@ -48,6 +48,7 @@
 #include <string>
 #include <type_traits>
 
+#include "../nn/bf16_pack.h"
 #include "spectral.h"
 
 namespace amd_dft {
@@ -55,20 +56,6 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// two floats -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = static_cast<__bf16>(a);
-  v[1] = static_cast<__bf16>(b);
-  return __builtin_bit_cast(uint32_t, v);
-}
-// hi = bf16(a, b); lo = bf16(a - hi.a, b - hi.b)
-__device__ __forceinline__ void split_pk(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pk_bf16(a, b);
-  lo = pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-}
 
 template <bool BF>
 __global__ void __launch_bounds__(256) sfno_mix_kernel(const void* __restrict__ c, const uint16_t* __restrict__ wh,

@@ -214,21 +214,31 @@ inline FnoPointwiseRoute fno_pointwise_route(int cin, int cout, bool bf16, int64
 // ---- Legendre transform (the latitude half of a spherical harmonic transform, legendre.hip):
 //   y[n, r, m, :] = sum_q T[m, r, q] * x[n, q, m, :]      (x complex as trailing re/im, T real, per mode m)
 // forward: Q = nlat, R = lmax, T = w_k P_l^m(cos theta_k); inverse: Q = lmax, R = nlat, T = P transposed.
+// Its vector form (the latitude half of a vector spherical harmonic transform), over pairs of planes of x:
+//   y[n, 0, r, m] = sum_q A[m, r, q] x[n, 0, q, m] - i B[m, r, q] x[n, 1, q, m]
+//   y[n, 1, r, m] = sum_q A[m, r, q] x[n, 1, q, m] + i B[m, r, q] x[n, 0, q, m]
 struct LegendreLaunch {
-  const void* x;       // [N, Q, M, 2] fp32 (bf16 if bf16)
-  const uint16_t* th;  // [M, Rp, Qp] bf16, hi plane of T zero-padded to Rp = ceil16(R), Qp = ceil32(Q)
+  const void* x;       // [N, Q, M, 2] fp32 (bf16 if bf16); vec: [N / 2, 2, Q, M, 2]
+  const uint16_t* th;  // [M, Rp, Qp] bf16, hi plane of T (vec: A) zero-padded to Rp = ceil16(R), Qp = ceil32(Q)
   const uint16_t* tl;  // the lo plane, bf16(T - hi); not read if bf16
-  void* y;             // [N, R, M, 2] fp32 (bf16 if bf16)
-  int64_t N;
+  const uint16_t* bh = nullptr;  // vec: the same two planes of B
+  const uint16_t* bl = nullptr;
+  void* y;             // [N, R, M, 2] fp32 (bf16 if bf16); vec: [N / 2, 2, R, M, 2]
+  int64_t N;           // [Q, M, 2] planes of x (vec: 2 x fields)
   int Q, R, M;
-  int tri = 0;         // 0: dense; 1: rows r < m are zero; 2: columns q < m are zero
-  int bf16 = 0;        // 1: bf16 x and y, one table plane (th = bf16(T)), one MFMA per fragment pair
+  int tri = 0;         // 0: dense; 1: rows r < m (of both tables) are zero; 2: columns q < m are zero
+  int bf16 = 0;        // 1: bf16 x and y, one plane per table (th = bf16(T)), one MFMA per fragment pair
+  int vec = 0;         // 1: the vector form, for launch_legendre_vec
 };
-// Which tiling a call takes (host only; launch_legendre and the legendre_info op both answer from here).
+// Which tiling a call takes (host only; the launchers and the legendre_info / legendre_vec_info ops answer from here).
 // A workgroup (4 waves) owns mt consecutive modes (a wave mt / 4 of them), 8 ct fields n (ct 16-column
 // MFMA tiles of the 2 N real columns) and one group of up to 64 rows r; it walks Q in 32-deep slabs.
 // The tile starts at 8 modes x 16 fields and shrinks -- first to 4 modes, then to 8 fields -- while the grid
 // would leave most of the 256 CUs without a workgroup (or the shape has nothing to fill the larger tile).
+// vec: the kernel runs over the component planes -- a 16-column tile is 4 fields x 2 components x (re | im),
+// cols = 4 x fields -- so the tiles, the LDS image and the shrink rule are the same: 8 modes x 8 fields, then 4
+// modes, then 4 fields.  fp32 vec starts at 4 modes: with two tables in two planes an 8-mode fp32 kernel leaves
+// one wave per SIMD (legendre.hip).
 constexpr int kLegSlab = 32;        // q per K slab
 constexpr int kLegRowTiles = 4;     // 16-row tiles per row group (64 x 16 ct accumulators per mode)
 constexpr int kLegXPitch = 80;      // bytes per LDS column of a slab: 32 bf16 + 16 B (conflict-free 16-byte reads)
@@ -251,13 +261,14 @@ inline int64_t legendre_lds_bytes(int mt, int ct, bool bf16 = false) {
   const int64_t ys = 16LL * (8 * ct * (2 * mt + 2) + 4) * 4;
   return xs > ys ? xs : ys;
 }
-inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/, bool bf16 = false) {
+inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/, bool bf16 = false,
+                                    bool vec = false) {
   LegendreRoute r{};
   r.slabs = static_cast<int>((Q + kLegSlab - 1) / kLegSlab);
   r.rtiles = static_cast<int>((R + 15) / 16);
   r.rgroups = (r.rtiles + kLegRowTiles - 1) / kLegRowTiles;
   auto count = [&](int mt, int ct) { return ((M + mt - 1) / mt) * ((cols + 16 * ct - 1) / (16 * ct)) * r.rgroups; };
-  r.mt = 8;
+  r.mt = vec && !bf16 ? 4 : 8;
   r.ct = 2;
   if (M <= 4 || count(r.mt, r.ct) < kLegFillWgs) r.mt = 4;
   if (cols <= 16 || count(r.mt, r.ct) < kLegFillWgs) r.ct = 1;
@@ -268,44 +279,7 @@ inline LegendreRoute legendre_route(int64_t Q, int64_t R, int64_t M, int64_t col
   return r;
 }
 void launch_legendre(const LegendreLaunch& p, void* stream);
-
-// ---- Vector Legendre transform (the latitude half of a vector spherical harmonic transform, legendre_vec.hip):
-//   y[n, 0, r, m] = sum_q A[m, r, q] x[n, 0, q, m] - i B[m, r, q] x[n, 1, q, m]
-//   y[n, 1, r, m] = sum_q A[m, r, q] x[n, 1, q, m] + i B[m, r, q] x[n, 0, q, m]
-struct LegendreVecLaunch {
-  const void* x;       // [N, 2, Q, M, 2] fp32 (bf16 if bf16)
-  const uint16_t* ah;  // [M, Rp, Qp] bf16, hi plane of A zero-padded to Rp = ceil16(R), Qp = ceil32(Q)
-  const uint16_t* al;  // the lo plane, bf16(A - hi); not read if bf16
-  const uint16_t* bh;  // the same two planes of B
-  const uint16_t* bl;
-  void* y;             // [N, 2, R, M, 2] fp32 (bf16 if bf16)
-  int64_t N;
-  int Q, R, M;
-  int tri = 0;         // 0: dense; 1: rows r < m of A and B are zero; 2: columns q < m are zero
-  int bf16 = 0;        // 1: bf16 x and y, one plane per table, one MFMA per fragment pair
-};
-// Which tiling a call takes (host only; launch_legendre_vec and the legendre_vec_info op both answer from here).
-// The kernel is legendre's over the 2 N component planes -- a 16-column tile is 4 fields x 2 components x
-// (re | im), cols = 4 x fields -- so the tiles, the LDS image and the shrink rule are legendre's: 8 modes x 8
-// fields, then 4 modes, then 4 fields while the grid would leave most CUs without a workgroup.  fp32 starts at
-// 4 modes: with two tables in two planes an 8-mode fp32 kernel leaves one wave per SIMD (legendre_vec.hip).
-inline LegendreRoute legendre_vec_route(int64_t Q, int64_t R, int64_t M, int64_t cols, int /*tri*/, bool bf16 = false) {
-  LegendreRoute r{};
-  r.slabs = static_cast<int>((Q + kLegSlab - 1) / kLegSlab);
-  r.rtiles = static_cast<int>((R + 15) / 16);
-  r.rgroups = (r.rtiles + kLegRowTiles - 1) / kLegRowTiles;
-  auto count = [&](int mt, int ct) { return ((M + mt - 1) / mt) * ((cols + 16 * ct - 1) / (16 * ct)) * r.rgroups; };
-  r.mt = bf16 ? 8 : 4;
-  r.ct = 2;
-  if (M <= 4 || count(r.mt, r.ct) < kLegFillWgs) r.mt = 4;
-  if (cols <= 16 || count(r.mt, r.ct) < kLegFillWgs) r.ct = 1;
-  r.mgroups = static_cast<int>((M + r.mt - 1) / r.mt);
-  r.ctiles = static_cast<int>((cols + 16 * r.ct - 1) / (16 * r.ct));
-  r.lds = legendre_lds_bytes(r.mt, r.ct, bf16);
-  r.wgs = count(r.mt, r.ct);
-  return r;
-}
-void launch_legendre_vec(const LegendreVecLaunch& p, void* stream);
+void launch_legendre_vec(const LegendreLaunch& p, void* stream);
 
 // ---- SFNO per-degree channel mixing (sfno_mix.hip):
 //   y[b, o, l, m] = sum_i c[b, i, l, m] * w[i, o, l]       (complex; one weight per degree l, shared by all orders m)

@@ -28,7 +28,7 @@ l < max(m, 1)), U, V the scaled longitude transforms of the two components and W
 * forward: s[l, m] = sum_k W0 U - i W1 V,  t[l, m] = sum_k W0 V + i W1 U;
 * inverse: U[k, m] = sum_l D0 s - i D1 t,  V[k, m] = sum_l D0 t + i D1 s, then the C2R of ``isht`` per component.
 
-Both are the ``legendre_vec`` op (``csrc/spectral/legendre_vec.hip``): one kernel pass over both tables and both
+Both are the ``legendre_vec`` op (``csrc/spectral/legendre.hip``, ``VEC``): one kernel pass over both tables and both
 components.  ``vsht`` of the gradient (d f / d theta, (1 / sin theta) d f / d phi) of a band-limited scalar f is
 s = sht(f) for l >= 1, t = 0.  ``ivsht(vsht(v))`` reproduces a band-limited v where the quadrature is exact for the
 products involved: ``legendre-gauss`` up to lmax = nlat, ``equiangular`` up to lmax = (nlat + 1) / 2.

@@ -1,4 +1,4 @@
-"""Vector spherical harmonic transforms on the GPU: the ``legendre_vec`` kernel (csrc/spectral/legendre_vec.hip) in
+"""Vector spherical harmonic transforms on the GPU: the ``legendre_vec`` kernel (csrc/spectral/legendre.hip, VEC) in
 both precisions and every shipped instance, ``vsht`` / ``ivsht`` and ``RealVectorSHT`` / ``InverseRealVectorSHT``
 against the fp64 ``"torch"`` backend, and the contracts the spectral MFMA kernels are pinned to (guard bands, stale
 LDS, the part ``tri`` declares zero, odd offsets, determinism, hipGraph replay).  References, cases and error models
@@ -59,7 +59,7 @@ def _route(case, prec, tri):
 
 
 def test_every_shipped_instance_is_reached():
-    """The instances the launcher can dispatch to (legendre_vec_route: fp32 4 x {2, 1}, bf16 {8, 4} x {2, 1}) are all
+    """The instances the launcher can dispatch to (legendre_route with vec: fp32 4 x {2, 1}, bf16 {8, 4} x {2, 1}) are all
     among the cases above, by the info string the launcher's own route function answers."""
     seen = set()
     for case, prec in RUNS:
@@ -95,6 +95,22 @@ def test_legendre_vec_vs_fp64(device, strict, case, prec, tri):
     _check(out, case, prec, tri, "dirty")
     if tri == 0:
         assert V.field_err(out, refs[1], 2) > 1e-2 and V.field_err(out, refs[2], 2) > 1e-2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tri", [0, 1, 2])
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("case", BASE, ids=rid)
+def test_legendre_vec_with_zero_b_is_legendre(device, strict, case, prec, tri):
+    """The two ops are instances of one kernel: with B = 0 the vector instance adds exact zeros between the scalar
+    instance's MFMAs, in the same accumulation order whatever tile either route picks, so the result is bit for bit
+    ``legendre`` of the same table over the 2 N component planes."""
+    N, Q, R, M = case
+    x, ta, _, _, _ = V.op_case(case, prec == "bf16")
+    xd, tad = x.to(device), ta.to(device)
+    out = ops.legendre_vec(xd, tad, torch.zeros_like(tad), None, None, tri)
+    ref = ops.legendre(xd.view(2 * N, Q, M, 2), tad, None, tri)
+    assert torch.equal(out, ref.view(N, 2, R, M, 2))
 
 
 def _guarded(device, case, prec, tri, x=None):
