@@ -6,6 +6,7 @@
 
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGraphsC10Utils.h>
+#include <c10/hip/HIPStream.h>
 
 #include <atomic>
 #include <cstdint>
@@ -72,14 +73,34 @@ inline at::Tensor f32_or_undef(const c10::optional<at::Tensor>& t) {
   return present(t) ? t->to(at::kFloat).contiguous() : at::Tensor();
 }
 
-// ---- 16-byte alignment of kernel inputs
+// ---- alignment of kernel inputs
+// A kernel that loads `bytes` at a time reads tensors that start on that boundary (a pointer test; allocations do, a
+// contiguous view at an odd element offset into a larger buffer does not): t itself, or its own contiguous copy.
+inline at::Tensor aligned_to(const at::Tensor& t, uintptr_t bytes) {
+  if (!t.defined() || t.numel() == 0 || reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0) return t;
+  return t.clone(at::MemoryFormat::Contiguous);
+}
 // The LayerNorm-fused W-transforms (afno_wfft.hip) and the LayerNorm kernels (layernorm.hip) move 8 or 16 bytes
 // per lane, and the former DMA 16-byte pieces of the residual tile and its statistics into LDS: every tensor they
-// read starts on a 16-byte boundary (a pointer test; allocations are, a contiguous view at an odd element offset
-// into a larger buffer is not and is copied).
-inline at::Tensor vec_aligned(const at::Tensor& x) {
-  if (!x.defined() || x.numel() == 0 || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0) return x;
-  return x.clone(at::MemoryFormat::Contiguous);
+// read starts on a 16-byte boundary.
+inline at::Tensor vec_aligned(const at::Tensor& x) { return aligned_to(x, 16); }
+
+// the stream the kernels of an op on t's device are launched on
+inline hipStream_t current_stream(const at::Tensor& t) {
+  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
+}
+
+// ---- padded extents of the MFMA kernels' operands
+constexpr int64_t ceil16(int64_t v) { return (v + 15) / 16 * 16; }
+constexpr int64_t ceil32(int64_t v) { return (v + 31) / 32 * 32; }
+
+// AFNO block-MLP weights [NB, k, k], or their bf16x3 split [NB, k, 2k] (k32-interleaved (hi, lo) rows), as fp32
+// [NB, k, k]
+inline at::Tensor unsplit_k32(const at::Tensor& w, const char* op) {
+  const int64_t k = w.size(1);
+  if (w.size(2) == k) return w.to(at::kFloat);
+  TORCH_CHECK(k % 32 == 0, op, ": split weights need 2 * block_size % 32 == 0");
+  return w.to(at::kFloat).reshape({w.size(0), k, k / 32, 2, 32}).sum(3).reshape({w.size(0), k, k});
 }
 
 }  // namespace amd_dft

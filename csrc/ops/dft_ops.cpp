@@ -393,7 +393,7 @@ void run_dftw(const at::Tensor& in, const at::Tensor& out, const DimSpec& s, flo
   p.m = static_cast<int>(s.lo);
   p.scale = scale;
   p.bf16 = in.scalar_type() == at::kBFloat16;
-  launch_dftw_r2c(p, c10::hip::getCurrentHIPStream(in.device().index()).stream());
+  launch_dftw_r2c(p, current_stream(in));
 }
 
 at::Tensor r2c_cuda(const at::Tensor& x_, at::IntArrayRef dim, double scale, at::IntArrayRef keep,
@@ -775,7 +775,7 @@ at::Tensor r2c_ln_cuda(const at::Tensor& x_, int64_t dim, double scale, int64_t 
     p.KM = static_cast<int>(s.lo);
     p.scale = static_cast<float>(scale);
     p.f32 = w_f32 ? 1 : 0;
-    launch_afno_w_r2c_ln(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    launch_afno_w_r2c_ln(p, current_stream(x));
     return checked(out, "r2c_ln");
   }
   if (x.scalar_type() == at::kBFloat16 && odt == at::kBFloat16 &&
@@ -844,7 +844,7 @@ at::Tensor c2r_ln_add_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double 
       p.KM = static_cast<int>(km);
       p.scale = static_cast<float>(scale);
       p.f32 = 1;
-      launch_afno_w_c2r_ln(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+      launch_afno_w_c2r_ln(p, current_stream(x));
       return checked(out, "c2r_ln_add");
     }
   }
@@ -873,7 +873,7 @@ at::Tensor c2r_ln_add_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double 
       p.C = static_cast<int>(C);
       p.KM = static_cast<int>(km);
       p.scale = static_cast<float>(scale);
-      launch_afno_w_c2r_ln(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+      launch_afno_w_c2r_ln(p, current_stream(x));
       return checked(out, "c2r_ln_add");
     }
     if (run_pass(Kind::C2R, X, out, cur, nxt, static_cast<int>(axis), s.n, in_lo, 0, static_cast<int>(s.n), 0,
@@ -999,7 +999,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_cuda(const at::T
     p.KM = static_cast<int>(km);
     p.scale = static_cast<float>(scale);
     p.f32 = 1;
-    launch_afno_w_c2r_ln(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    launch_afno_w_c2r_ln(p, current_stream(x));
     return {checked(out, "c2r_ln_add_split"), pairs, part};
   }
   fallback_note("c2r_ln_add_split", "no fused W-transform for this shape: c2r_ln_add + ATen split / statistics");
@@ -1069,7 +1069,7 @@ std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_cuda(const at::Tensor& X_, in
     p.C = static_cast<int>(C);
     p.KM = static_cast<int>(km);
     p.scale = static_cast<float>(scale);
-    launch_afno_w_c2r_ln(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    launch_afno_w_c2r_ln(p, current_stream(x));
     return {checked(out, "c2r_ln_add_part"), part};
   }
   fallback_note("c2r_ln_add_part", "no fused W-transform for this shape: c2r_ln_add + ATen statistics");

@@ -12,27 +12,15 @@
 #include "../spectral/dft_gemm.h"
 #include "../spectral/spectral.h"
 #include "checks.h"
+#include "op_family.h"
 #include "plan_cache.h"
 
 namespace amd_dft {
 namespace {
 
-// ------------------------------------------------------------------ `_out` variants
-// An `_out` op runs the launch path of its allocating op into a caller's tensor.  out must be exactly what the
-// allocating op returns -- shape, dtype, device, contiguous -- and on the device start where the kernel's widest
-// store is aligned.  Anything else is an error, never a copy: a copy would move the result out of the caller's buffer
-// (tests/test_kernel_bounds_gpu.py puts guard bands around it).
-void check_out(const at::Tensor& out, at::IntArrayRef shape, const at::Tensor& like, const char* op) {
-  TORCH_CHECK(out.defined() && out.sizes() == shape && out.scalar_type() == like.scalar_type() &&
-                  out.device() == like.device() && out.is_contiguous(),
-              op, ": out must be a contiguous ", like.scalar_type(), " tensor of shape ", shape, " on ", like.device(),
-              ", got ", out.scalar_type(), " ", out.sizes(), " on ", out.device(),
-              out.is_contiguous() ? "" : " (not contiguous)");
-}
-void check_out_aligned(const at::Tensor& out, uintptr_t bytes, const char* op) {
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % bytes == 0, op, ": out must start on a ", bytes,
-              "-byte boundary (the kernel's stores)");
-}
+// The families with an `_out` op (afno_mlp, fno_mix, fno_pointwise, fno_c2r_pw, legendre, legendre_vec, disco,
+// sfno_mix, instance_norm) are described once each, in a struct after their check, reference and launch path;
+// op_family.h makes the six backend forms of the description.
 
 // ------------------------------------------------------------------ AFNO spectral filter
 // xw [B, H, KM, C, 2] fp32 (W-direction half spectrum), w1t/w2t [NB, 2BS, 2BS] bf16 ([n][k]),
@@ -59,13 +47,8 @@ at::Tensor afno_spectral_cpu(const at::Tensor& xw, const at::Tensor& w1t, const 
   at::Tensor X = at::fft_fft(at::view_as_complex(xw.to(at::kFloat).contiguous()), std::nullopt, 1, "backward");
   at::Tensor Xr = at::view_as_real(X).reshape({B, H, KM, NB, BS, 2});
   at::Tensor A = at::cat({Xr.select(-1, 0), Xr.select(-1, 1)}, -1);  // [..., NB, 2BS]
-  auto unsplit = [&](const at::Tensor& w) {  // k32-interleaved split rows -> fp32
-    if (w.size(2) == w.size(1)) return w.to(at::kFloat);
-    const int64_t k = w.size(1);
-    return w.to(at::kFloat).reshape({w.size(0), w.size(1), k / 32, 2, 32}).sum(3).reshape({w.size(0), w.size(1), k});
-  };
-  at::Tensor W1 = unsplit(w1t).transpose(1, 2);                      // [NB, k, n]
-  at::Tensor W2 = unsplit(w2t).transpose(1, 2);
+  at::Tensor W1 = unsplit_k32(w1t, "afno_spectral").transpose(1, 2);  // [NB, k, n]
+  at::Tensor W2 = unsplit_k32(w2t, "afno_spectral").transpose(1, 2);
   at::Tensor H1 = at::relu(at::einsum("...bk,bkn->...bn", {A, W1}) + b1);
   at::Tensor O = at::einsum("...bk,bkn->...bn", {H1, W2}) + b2;
   O = at::softshrink(O, lam);
@@ -109,7 +92,7 @@ at::Tensor afno_spectral_cuda(const at::Tensor& xw_, const at::Tensor& w1t_, con
   p.C = static_cast<int>(C);
   p.NB = static_cast<int>(NB);
   p.lambda = static_cast<float>(lam);
-  launch_afno_spectral(p, c10::hip::getCurrentHIPStream(xw.device().index()).stream());
+  launch_afno_spectral(p, current_stream(xw));
   return checked(y, "afno_spectral");
 }
 
@@ -143,42 +126,22 @@ void check_afno_mlp(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor
   TORCH_CHECK(b1.sizes() == at::IntArrayRef({NB, K}) && b2.sizes() == b1.sizes(), "afno_mlp: bad bias shapes");
 }
 
-void check_afno_mlp_out(const at::Tensor& x, const at::Tensor& out) {
-  TORCH_CHECK(out.sizes() == x.sizes() && out.scalar_type() == at::kFloat && out.is_contiguous() &&
-                  out.device() == x.device(),
-              "afno_mlp_out: out must be a contiguous float32 tensor of x's shape on x's device");
-}
-
-at::Tensor afno_mlp_cpu(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
+at::Tensor afno_mlp_ref(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
                         const at::Tensor& b2, double lam) {
-  check_afno_mlp(x, w1t, w2t, b1, b2);
   const int64_t C = x.size(-2), NB = w1t.size(0), BS = C / NB;
   at::Tensor Xr = x.contiguous().reshape({-1, NB, BS, 2});
   at::Tensor A = at::cat({Xr.select(-1, 0), Xr.select(-1, 1)}, -1);  // [T, NB, 2BS]
-  auto unsplit = [&](const at::Tensor& w) {  // k32-interleaved split rows -> fp32
-    if (w.size(2) == w.size(1)) return w.to(at::kFloat);
-    const int64_t k = w.size(1);
-    TORCH_CHECK(k % 32 == 0, "afno_mlp: split weights need 2 * block_size % 32 == 0");
-    return w.to(at::kFloat).reshape({w.size(0), k, k / 32, 2, 32}).sum(3).reshape({w.size(0), k, k});
-  };
-  at::Tensor W1 = unsplit(w1t).transpose(1, 2), W2 = unsplit(w2t).transpose(1, 2);  // [NB, k, n]
-  at::Tensor H1 = at::relu(at::einsum("tbk,bkn->tbn", {A, W1}) + b1.to(at::kFloat));
+  at::Tensor W1 = unsplit_k32(w1t, "afno_mlp").transpose(1, 2), W2 = unsplit_k32(w2t, "afno_mlp").transpose(1, 2);
+  at::Tensor H1 = at::relu(at::einsum("tbk,bkn->tbn", {A, W1}) + b1.to(at::kFloat));  // W1, W2 [NB, k, n]
   at::Tensor O = at::softshrink(at::einsum("tbk,bkn->tbn", {H1, W2}) + b2.to(at::kFloat), lam);
   return at::stack({O.narrow(-1, 0, BS), O.narrow(-1, BS, BS)}, -1).reshape(x.sizes()).contiguous();
 }
 
-at::Tensor& afno_mlp_out_cpu(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
-                             const at::Tensor& b2, double lam, at::Tensor& out) {
-  check_afno_mlp_out(x, out);
-  out.copy_(afno_mlp_cpu(x, w1t, w2t, b1, b2, lam));
-  return out;
-}
-
+// the launch path of afno_mlp and afno_mlp_out: y is the contiguous fp32 result, 16-byte aligned
 void afno_mlp_run(const at::Tensor& x_, const at::Tensor& w1t_, const at::Tensor& w2t_, const at::Tensor& b1_,
-                  const at::Tensor& b2_, double lam, at::Tensor& y) {
-  at::Tensor x = x_.contiguous();
+                  const at::Tensor& b2_, double lam, const at::Tensor& y) {
   // 16-byte loads of two channels' (re, im): a view at an odd offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone();
+  at::Tensor x = aligned_to(x_.contiguous(), 16);
   at::Tensor w1t = w1t_.to(at::kBFloat16).contiguous(), w2t = w2t_.to(at::kBFloat16).contiguous();
   at::Tensor b1 = b1_.to(at::kFloat).contiguous(), b2 = b2_.to(at::kFloat).contiguous();
   const int64_t C = x.size(-2), NB = w1t.size(0), BS = C / NB;
@@ -186,8 +149,7 @@ void afno_mlp_run(const at::Tensor& x_, const at::Tensor& w1t_, const at::Tensor
   const int64_t T = x.numel() / (2 * C);
   const AfnoMlpRoute r = afno_mlp_route(BS, x3, T);
   TORCH_CHECK(r.ok, "afno_mlp: no kernel for block size ", BS, " (", r.why ? r.why : "", "); use the generic path");
-  TORCH_CHECK(C < (1 << 28) && reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
-              "afno_mlp: channel count too large or misaligned output");
+  TORCH_CHECK(C < (1 << 28), "afno_mlp: channel count too large");
   if (T == 0) return;
   AfnoMlpLaunch p;
   p.x = x.data_ptr<float>();
@@ -201,37 +163,29 @@ void afno_mlp_run(const at::Tensor& x_, const at::Tensor& w1t_, const at::Tensor
   p.NB = static_cast<int>(NB);
   p.x3 = x3 ? 1 : 0;
   p.lambda = static_cast<float>(lam);
-  launch_afno_mlp(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  launch_afno_mlp(p, current_stream(x));
 }
 
-at::Tensor afno_mlp_cuda(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
-                         const at::Tensor& b2, double lam) {
-  check_afno_mlp(x, w1t, w2t, b1, b2);
-  const c10::DeviceGuard guard(x.device());
-  at::Tensor y = at::empty(x.sizes(), x.options());
-  afno_mlp_run(x, w1t, w2t, b1, b2, lam, y);
-  return checked(y, "afno_mlp");
-}
-
-at::Tensor& afno_mlp_out_cuda(const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t, const at::Tensor& b1,
-                              const at::Tensor& b2, double lam, at::Tensor& out) {
-  check_afno_mlp(x, w1t, w2t, b1, b2);
-  check_afno_mlp_out(x, out);
-  const c10::DeviceGuard guard(x.device());
-  afno_mlp_run(x, w1t, w2t, b1, b2, lam, out);
-  checked(out, "afno_mlp_out");
-  return out;
-}
-
-at::Tensor afno_mlp_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
-                         double) {
-  return at::empty(x.sizes(), x.options());
-}
-
-at::Tensor& afno_mlp_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
-                              const at::Tensor&, double, at::Tensor& out) {
-  return out;
-}
+struct AfnoMlp : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                         double);
+  static constexpr const char *name = "afno_mlp", *out_name = "afno_mlp_out";
+  static void check(const char*, const at::Tensor& x, const at::Tensor& w1t, const at::Tensor& w2t,
+                    const at::Tensor& b1, const at::Tensor& b2, double) {
+    check_afno_mlp(x, w1t, w2t, b1, b2);
+  }
+  template <class... A>
+  static OpResult result(const at::Tensor& x, const A&...) {
+    return {x.sizes(), x.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const A&...) {
+    return 16;
+  }
+  static constexpr auto& reference = afno_mlp_ref;
+  static constexpr auto& run = afno_mlp_run;
+};
+AMD_DFT_OP_FAMILY(afno_mlp, AfnoMlp)
 
 // Which kernel afno_mlp runs for (block size, packing, tokens) -- host only, no device (the companion of
 // fno_pointwise_info): "mfma TOK=32 ksteps=6 x3=1 lds=51200 tiles=512" or "none <reason>"
@@ -255,27 +209,12 @@ void check_fno_mix(const at::Tensor& x, const at::Tensor& w) {
 bool fno_mix_bf16(const at::Tensor& x, const at::Tensor& w) {
   return x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16;
 }
-std::vector<int64_t> fno_mix_out_shape(const at::Tensor& x, const at::Tensor& w) {
-  return {x.size(0), w.size(1), x.size(2), 2};
-}
-// what the result is like: dtype by the rule above, on x's device
-at::Tensor fno_mix_like(const at::Tensor& x, const at::Tensor& w) {
-  return at::empty({0}, x.options().dtype(fno_mix_bf16(x, w) ? at::kBFloat16 : at::kFloat));
-}
 
-at::Tensor fno_mix_cpu(const at::Tensor& x, const at::Tensor& w, int64_t /*path*/) {
-  check_fno_mix(x, w);
+at::Tensor fno_mix_ref(const at::Tensor& x, const at::Tensor& w, int64_t /*path*/) {
   at::Tensor xc = at::view_as_complex(x.to(at::kFloat).contiguous());
   at::Tensor wc = at::view_as_complex(w.to(at::kFloat).contiguous());
   at::Tensor y = at::view_as_real(at::einsum("bim,iom->bom", {xc, wc})).contiguous();
   return fno_mix_bf16(x, w) ? y.to(at::kBFloat16) : y;  // the product of the upcast operands, rounded once
-}
-
-at::Tensor& fno_mix_out_cpu(const at::Tensor& x, const at::Tensor& w, int64_t path, at::Tensor& out) {
-  check_fno_mix(x, w);
-  check_out(out, fno_mix_out_shape(x, w), fno_mix_like(x, w), "fno_mix_out");
-  out.copy_(fno_mix_cpu(x, w, path));
-  return out;
 }
 
 // the launch path of fno_mix and fno_mix_out: y is the contiguous result, aligned to one (re, im) pair (8 bytes fp32,
@@ -288,11 +227,9 @@ void fno_mix_run(const at::Tensor& x_, const at::Tensor& w_, int64_t path, const
                   Cout * M < (int64_t(1) << 37),
               "fno_mix: tensor too large");
   const at::ScalarType dt = bf16 ? at::kBFloat16 : at::kFloat;
-  at::Tensor x = x_.to(dt).contiguous(), w = w_.to(dt).contiguous();
   // one load per (re, im) pair: a view at an odd element offset gets its own copy
   const uintptr_t al = bf16 ? 4 : 8;
-  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % al != 0) x = x.clone();
-  if (reinterpret_cast<uintptr_t>(w.data_ptr()) % al != 0) w = w.clone();
+  at::Tensor x = aligned_to(x_.to(dt).contiguous(), al), w = aligned_to(w_.to(dt).contiguous(), al);
   if (y.numel() == 0) return;
   FnoMixLaunch p;
   p.x = x.data_ptr();
@@ -304,35 +241,24 @@ void fno_mix_run(const at::Tensor& x_, const at::Tensor& w_, int64_t path, const
   p.M = static_cast<int>(M);
   p.mfma = path == 2 ? 1 : 0;
   p.bf16 = bf16 ? 1 : 0;
-  launch_fno_mix(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  launch_fno_mix(p, current_stream(x));
 }
 
-at::Tensor fno_mix_cuda(const at::Tensor& x, const at::Tensor& w, int64_t path) {
-  const c10::DeviceGuard guard(x.device());
-  check_fno_mix(x, w);
-  TORCH_CHECK(w.device() == x.device(), "fno_mix: w must be on the device of x");
-  at::Tensor y = at::empty(fno_mix_out_shape(x, w), fno_mix_like(x, w).options());
-  fno_mix_run(x, w, path, y);
-  return checked(y, "fno_mix");
-}
-
-at::Tensor& fno_mix_out_cuda(const at::Tensor& x, const at::Tensor& w, int64_t path, at::Tensor& out) {
-  check_fno_mix(x, w);
-  TORCH_CHECK(w.device() == x.device(), "fno_mix_out: w must be on the device of x");
-  check_out(out, fno_mix_out_shape(x, w), fno_mix_like(x, w), "fno_mix_out");
-  check_out_aligned(out, fno_mix_bf16(x, w) ? 4 : 8, "fno_mix_out");
-  const c10::DeviceGuard guard(x.device());
-  fno_mix_run(x, w, path, out);
-  checked(out, "fno_mix_out");
-  return out;
-}
-
-at::Tensor fno_mix_meta(const at::Tensor& x, const at::Tensor& w, int64_t) {
-  return at::empty({x.size(0), w.size(1), x.size(2), 2},
-                   x.options().dtype(fno_mix_bf16(x, w) ? at::kBFloat16 : at::kFloat));
-}
-
-at::Tensor& fno_mix_out_meta(const at::Tensor&, const at::Tensor&, int64_t, at::Tensor& out) { return out; }
+struct FnoMix : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, int64_t);
+  static constexpr const char *name = "fno_mix", *out_name = "fno_mix_out";
+  static void check(const char*, const at::Tensor& x, const at::Tensor& w, int64_t) { check_fno_mix(x, w); }
+  static void check_device(const char* op, const at::Tensor& x, const at::Tensor& w, int64_t) {
+    TORCH_CHECK(w.device() == x.device(), op, ": w must be on the device of x");
+  }
+  static OpResult result(const at::Tensor& x, const at::Tensor& w, int64_t) {  // dtype by the rule above, on x's device
+    return {{x.size(0), w.size(1), x.size(2), 2}, x.options().dtype(fno_mix_bf16(x, w) ? at::kBFloat16 : at::kFloat)};
+  }
+  static uintptr_t out_align(const at::Tensor& x, const at::Tensor& w, int64_t) { return fno_mix_bf16(x, w) ? 4 : 8; }
+  static constexpr auto& reference = fno_mix_ref;
+  static constexpr auto& run = fno_mix_run;
+};
+AMD_DFT_OP_FAMILY(fno_mix, FnoMix)
 
 // Which kernel fno_mix runs for (B, Cin, Cout, M, dtype, path) -- host only, no device (the companion of
 // sfno_mix_info): "stream NB=4 vec=1 lds=6144 wgs=640 launches=1", "mfma MT=8 lds=151552 wgs=256 launches=1" or
@@ -352,7 +278,7 @@ std::string fno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t M, bool b
 
 // ------------------------------------------------------------------ FNO pointwise epilogue
 // y = act(spec + conv1x1(x, w) + bias); x [B, Cin, *S], spec [B, Cout, *S] (or None), w [Cout, Cin(,1,1)]
-at::Tensor fno_pointwise_cpu(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
+at::Tensor fno_pointwise_ref(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
                              const c10::optional<at::Tensor>& bias, bool gelu) {
   TORCH_CHECK(x.dim() >= 2, "fno_pointwise: x [B, Cin, ...]");
   const int64_t B = x.size(0), Cin = x.size(1);
@@ -366,20 +292,6 @@ at::Tensor fno_pointwise_cpu(const c10::optional<at::Tensor>& spec, const at::Te
   std::vector<int64_t> shape = x.sizes().vec();
   shape[1] = w2.size(0);
   return y.reshape(shape).to(x.scalar_type());
-}
-
-std::vector<int64_t> fno_pointwise_out_shape(const at::Tensor& x, const at::Tensor& w) {
-  TORCH_CHECK(x.dim() >= 2 && w.dim() >= 1, "fno_pointwise: x [B, Cin, ...], w [Cout, Cin]");
-  std::vector<int64_t> shape = x.sizes().vec();
-  shape[1] = w.size(0);
-  return shape;
-}
-
-at::Tensor& fno_pointwise_out_cpu(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
-                                  const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
-  check_out(out, fno_pointwise_out_shape(x, w), x, "fno_pointwise_out");
-  out.copy_(fno_pointwise_cpu(spec, x, w, bias, gelu));
-  return out;
 }
 
 // the launch path of fno_pointwise and fno_pointwise_out: y is the contiguous [B, Cout, ...] result in x's dtype
@@ -415,26 +327,26 @@ void fno_pointwise_run(const c10::optional<at::Tensor>& spec_, const at::Tensor&
   p.P = static_cast<int>(P);
   p.bf16 = x.scalar_type() == at::kBFloat16;
   p.gelu = gelu;
-  launch_fno_pointwise(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  launch_fno_pointwise(p, current_stream(x));
 }
 
-at::Tensor fno_pointwise_cuda(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
-                              const c10::optional<at::Tensor>& bias, bool gelu) {
-  const c10::DeviceGuard guard(x.device());
-  at::Tensor y = at::empty(fno_pointwise_out_shape(x, w), x.options());
-  fno_pointwise_run(spec, x, w, bias, gelu, y);
-  return checked(y, "fno_pointwise");
-}
-
-// out: any element-aligned start -- the kernels fall to per-element I/O off the 4-element boundary
-at::Tensor& fno_pointwise_out_cuda(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
-                                   const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
-  const c10::DeviceGuard guard(x.device());
-  check_out(out, fno_pointwise_out_shape(x, w), x, "fno_pointwise_out");
-  fno_pointwise_run(spec, x, w, bias, gelu, out);
-  checked(out, "fno_pointwise_out");
-  return out;
-}
+// no check beyond result's (the reference and the launch path make their own) and no out_align: out starts at any
+// element -- the kernels fall to per-element I/O off the 4-element boundary
+struct FnoPointwise : OpFamily {
+  using Sig = at::Tensor(const c10::optional<at::Tensor>&, const at::Tensor&, const at::Tensor&,
+                         const c10::optional<at::Tensor>&, bool);
+  static constexpr const char *name = "fno_pointwise", *out_name = "fno_pointwise_out";
+  template <class... A>
+  static OpResult result(const c10::optional<at::Tensor>&, const at::Tensor& x, const at::Tensor& w, const A&...) {
+    TORCH_CHECK(x.dim() >= 2 && w.dim() >= 1, "fno_pointwise: x [B, Cin, ...], w [Cout, Cin]");
+    OpResult r(x.sizes(), x.options());
+    r.shape[1] = w.size(0);
+    return r;
+  }
+  static constexpr auto& reference = fno_pointwise_ref;
+  static constexpr auto& run = fno_pointwise_run;
+};
+AMD_DFT_OP_FAMILY(fno_pointwise, FnoPointwise)
 
 // Which kernel fno_pointwise runs for (Cin, Cout, dtype, P) on aligned tensors -- host only, no device
 // (the companion of fft_pass_info): "fixed cin=20 vp=4" or "mfma slabs=2 otiles=3 groups=1 x3=1 vp=4"
@@ -447,18 +359,6 @@ std::string fno_pointwise_info(int64_t cin, int64_t cout, bool bf16, int64_t P) 
          " groups=" + std::to_string(r.groups) + " x3=" + std::to_string(r.x3 ? 1 : 0) + " vp=" + std::to_string(r.vp);
 }
 
-at::Tensor fno_pointwise_meta(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
-                              const c10::optional<at::Tensor>& bias, bool gelu) {
-  std::vector<int64_t> shape = x.sizes().vec();
-  shape[1] = w.size(0);
-  return at::empty(shape, x.options());
-}
-
-at::Tensor& fno_pointwise_out_meta(const c10::optional<at::Tensor>&, const at::Tensor&, const at::Tensor&,
-                                   const c10::optional<at::Tensor>&, bool, at::Tensor& out) {
-  return out;
-}
-
 // ------------------------------------------------------------------ FNO layer tail (C2R-W + pointwise)
 // yw [B, Cout, H, m, 2] fp32 (inverse-H-transformed kept modes, carrying the 1/(H W) scale),
 // x [B, Cin, H, W] -> y [B, Cout, H, W] = act(irfft_W(yw) + conv1x1(x, wc) + bias), dtype of x.
@@ -469,100 +369,94 @@ void check_fno_c2r(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& 
   TORCH_CHECK(2 * (yw.size(3) - 1) <= x.size(3), "fno_c2r_pw: more modes than the half spectrum");
 }
 
-at::Tensor fno_c2r_pw_cpu(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
+at::Tensor fno_c2r_pw_ref(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
                           const c10::optional<at::Tensor>& bias, bool gelu) {
-  check_fno_c2r(yw, x, wc);
   const int64_t W = x.size(3), m = yw.size(3);
   at::Tensor full = at::zeros({yw.size(0), yw.size(1), yw.size(2), W / 2 + 1}, yw.options().dtype(at::kComplexDouble));
   full.narrow(3, 0, m).copy_(at::view_as_complex(yw.to(at::kDouble).contiguous()));
   at::Tensor spec = at::fft_irfft(full, W, 3, "forward").to(at::kFloat);
-  return fno_pointwise_cpu(spec, x, wc.reshape({yw.size(1), x.size(1)}), bias, gelu);
+  return fno_pointwise_ref(spec, x, wc.reshape({yw.size(1), x.size(1)}), bias, gelu);
 }
 
-std::vector<int64_t> fno_c2r_pw_out_shape(const at::Tensor& yw, const at::Tensor& x) {
-  return {x.size(0), yw.size(1), x.size(2), x.size(3)};
+// shapes outside both fused kernels (m > 64, W % 8 != 0, a rotation table beyond LDS): C2R on the FFT kernels
+at::Tensor fno_tail_c2r(const at::Tensor& yw, int64_t W, at::ScalarType dt) {
+  static auto c2r = c10::Dispatcher::singleton()
+                        .findSchemaOrThrow("amd_dft::c2r", "")
+                        .typed<at::Tensor(const at::Tensor&, at::IntArrayRef, at::IntArrayRef, double, at::IntArrayRef,
+                                          std::optional<at::ScalarType>)>();
+  const std::vector<int64_t> dim{3}, out_size{W};
+  return c2r.call(yw.to(at::kFloat).contiguous(), dim, out_size, 1.0, {}, dt);
 }
 
-at::Tensor& fno_c2r_pw_out_cpu(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
-                               const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
-  check_fno_c2r(yw, x, wc);
-  check_out(out, fno_c2r_pw_out_shape(yw, x), x, "fno_c2r_pw_out");
-  out.copy_(fno_c2r_pw_cpu(yw, x, wc, bias, gelu));
-  return out;
-}
-
-// the launch path of fno_c2r_pw and fno_c2r_pw_out: y is the contiguous [B, Cout, H, W] result in x's dtype
-void fno_c2r_pw_run(const at::Tensor& yw_, const at::Tensor& x_, const at::Tensor& wc_,
-                    const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
-  TORCH_CHECK(x_.scalar_type() == at::kFloat || x_.scalar_type() == at::kBFloat16,
-              "fno_c2r_pw: x must be float32 or bfloat16");
-  const int64_t B = x_.size(0), Cin = x_.size(1), H = x_.size(2), W = x_.size(3), Cout = yw_.size(1),
-                m = yw_.size(3);
-  const bool is_bf = x_.scalar_type() == at::kBFloat16;
-  const FnoTailRoute route = fno_c2r_pw_route(static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(m),
-                                              static_cast<int>(W), is_bf);
-  if (route.kind == FnoTailKind::Split) {
-    // shapes outside both fused kernels (m > 64, W % 8 != 0, a rotation table beyond LDS): C2R on the FFT
-    // kernels + the pointwise kernel, which takes any channel counts (fixed instance or MFMA, fno_pointwise_route)
-    static auto c2r = c10::Dispatcher::singleton()
-                          .findSchemaOrThrow("amd_dft::c2r", "")
-                          .typed<at::Tensor(const at::Tensor&, at::IntArrayRef, at::IntArrayRef, double,
-                                            at::IntArrayRef, std::optional<at::ScalarType>)>();
-    const std::vector<int64_t> dim{3}, out_size{W};
-    at::Tensor spec = c2r.call(yw_.to(at::kFloat).contiguous(), dim, out_size, 1.0, {}, x_.scalar_type());
-    return fno_pointwise_run(spec, x_, wc_.reshape({Cout, Cin}), bias, gelu, y);
-  }
-  const bool wide = route.kind == FnoTailKind::Wide;  // Cin or Cout > 32: fno_c2r_pw_wide.hip, 64-pixel chunks
-  TORCH_CHECK(B * Cin * H * W < (int64_t(1) << 31) && B * Cout * H * W < (int64_t(1) << 31),
-              "fno_c2r_pw: tensor too large");
-  at::Tensor x = x_.contiguous();
-  at::Tensor yw = yw_.to(at::kFloat).contiguous();
+// the one launch of the fused tail kernels, narrow or wide (Cin or Cout > 32: fno_c2r_pw_wide.hip, 64-pixel chunks):
+// y = act(irfft_W(yw) + conv1x1(x, wc) + bias) in y's dtype; x and wc null: the spectral part alone (fno_c2r, Cin = 0)
+void fno_tail_launch(bool wide, const at::Tensor& yw_, const at::Tensor* x_, const at::Tensor* wc_,
+                     const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
+  const int64_t Cin = x_ ? x_->size(1) : 0, Cout = y.size(1), W = y.size(3), m = yw_.size(3);
+  const bool bf16 = y.scalar_type() == at::kBFloat16;
   // the tail kernel reads 4 modes per 16-byte load: a view at an odd float2 offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(yw.data_ptr()) % 16 != 0) yw = yw.clone();
-  at::Tensor wc = wc_.to(at::kFloat).reshape({Cout, Cin}).contiguous();
-  at::Tensor bf = f32_or_undef(bias);
-  auto tabs = get_dft_gemm_tables(is_bf && !wide ? DftTable::C2R_BF16 : DftTable::C2R_F32, static_cast<int>(W),
-                                  static_cast<int>(m), x.device());
+  at::Tensor yw = aligned_to(yw_.to(at::kFloat).contiguous(), 16);
+  at::Tensor x, wc, bf = f32_or_undef(bias);
+  if (x_) {
+    x = x_->contiguous();
+    wc = wc_->to(at::kFloat).reshape({Cout, Cin}).contiguous();
+  }
+  auto tabs = get_dft_gemm_tables(bf16 && !wide ? DftTable::C2R_BF16 : DftTable::C2R_F32, static_cast<int>(W),
+                                  static_cast<int>(m), y.device());
   FnoC2RPwLaunch p;
   p.yw = yw.data_ptr();
-  p.x = x.data_ptr();
-  p.wc = wc.data_ptr<float>();
+  p.x = x_ ? x.data_ptr() : nullptr;
+  p.wc = x_ ? wc.data_ptr<float>() : nullptr;
   p.bias = bf.defined() ? bf.data_ptr<float>() : nullptr;
   p.y = y.data_ptr();
   p.g0 = tabs.first.data_ptr();
   p.rot = tabs.second.data_ptr();
-  p.B = static_cast<int>(B);
+  p.B = static_cast<int>(y.size(0));
   p.Cin = static_cast<int>(Cin);
   p.Cout = static_cast<int>(Cout);
-  p.H = static_cast<int>(H);
+  p.H = static_cast<int>(y.size(2));
   p.W = static_cast<int>(W);
   p.m = static_cast<int>(m);
-  p.bf16 = x.scalar_type() == at::kBFloat16;
+  p.bf16 = bf16;
   p.gelu = gelu;
-  if (wide) launch_fno_c2r_pw_wide(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-  else launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  if (wide) launch_fno_c2r_pw_wide(p, current_stream(y));
+  else launch_fno_c2r_pw(p, current_stream(y));
 }
 
-at::Tensor fno_c2r_pw_cuda(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
-                           const c10::optional<at::Tensor>& bias, bool gelu) {
-  const c10::DeviceGuard guard(x.device());
-  check_fno_c2r(yw, x, wc);
-  at::Tensor y = at::empty(fno_c2r_pw_out_shape(yw, x), x.options());
-  fno_c2r_pw_run(yw, x, wc, bias, gelu, y);
-  return checked(y, "fno_c2r_pw");
+// the launch path of fno_c2r_pw and fno_c2r_pw_out: y is the contiguous [B, Cout, H, W] result in x's dtype
+void fno_c2r_pw_run(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
+                    const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16,
+              "fno_c2r_pw: x must be float32 or bfloat16");
+  const int64_t Cin = x.size(1), W = x.size(3), Cout = yw.size(1), m = yw.size(3);
+  const FnoTailRoute route = fno_c2r_pw_route(static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(m),
+                                              static_cast<int>(W), x.scalar_type() == at::kBFloat16);
+  if (route.kind == FnoTailKind::Split)  // + the pointwise kernel, which takes any channel counts (fno_pointwise_route)
+    return fno_pointwise_run(fno_tail_c2r(yw, W, x.scalar_type()), x, wc.reshape({Cout, Cin}), bias, gelu, y);
+  TORCH_CHECK(x.numel() < (int64_t(1) << 31) && y.numel() < (int64_t(1) << 31), "fno_c2r_pw: tensor too large");
+  fno_tail_launch(route.kind == FnoTailKind::Wide, yw, &x, &wc, bias, gelu, y);
 }
 
-// out: 16-byte aligned, the store width of both fused kernels in either dtype
-at::Tensor& fno_c2r_pw_out_cuda(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
-                                const c10::optional<at::Tensor>& bias, bool gelu, at::Tensor& out) {
-  const c10::DeviceGuard guard(x.device());
-  check_fno_c2r(yw, x, wc);
-  check_out(out, fno_c2r_pw_out_shape(yw, x), x, "fno_c2r_pw_out");
-  check_out_aligned(out, 16, "fno_c2r_pw_out");
-  fno_c2r_pw_run(yw, x, wc, bias, gelu, out);
-  checked(out, "fno_c2r_pw_out");
-  return out;
-}
+struct FnoC2rPw : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&,
+                         bool);
+  static constexpr const char *name = "fno_c2r_pw", *out_name = "fno_c2r_pw_out";
+  template <class... A>
+  static void check(const char*, const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc, const A&...) {
+    check_fno_c2r(yw, x, wc);
+  }
+  template <class... A>
+  static OpResult result(const at::Tensor& yw, const at::Tensor& x, const A&...) {
+    return {{x.size(0), yw.size(1), x.size(2), x.size(3)}, x.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const A&...) {  // the store width of both fused kernels in either dtype
+    return 16;
+  }
+  static constexpr auto& reference = fno_c2r_pw_ref;
+  static constexpr auto& run = fno_c2r_pw_run;
+};
+AMD_DFT_OP_FAMILY(fno_c2r_pw, FnoC2rPw)
 
 // Which route fno_c2r_pw (cin >= 1) or fno_c2r (cin = 0) takes for a shape -- host only, no device (the
 // companion of fno_pointwise_info): "fused ks=2 co=2 chunk=128", "wide slabs=2 otiles=4 groups=1 ks=2 chunk=64
@@ -580,16 +474,6 @@ std::string fno_c2r_pw_info(int64_t cin, int64_t cout, int64_t m, int64_t W, boo
            " groups=" + std::to_string(r.groups) + " ks=" + std::to_string(r.ks) + " chunk=" + std::to_string(r.chunk) +
            " x3=" + std::to_string(r.x3 ? 1 : 0) + " wl=" + std::to_string(r.wl ? 1 : 0);
   return "split";
-}
-
-at::Tensor fno_c2r_pw_meta(const at::Tensor& yw, const at::Tensor& x, const at::Tensor& wc,
-                           const c10::optional<at::Tensor>&, bool) {
-  return at::empty({x.size(0), yw.size(1), x.size(2), x.size(3)}, x.options());
-}
-
-at::Tensor& fno_c2r_pw_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&,
-                                const c10::optional<at::Tensor>&, bool, at::Tensor& out) {
-  return out;
 }
 
 // ------------------------------------------------------------------ SpectralConv2d tail (C2R-W only)
@@ -619,40 +503,9 @@ at::Tensor fno_c2r_cuda(const at::Tensor& yw_, int64_t W, std::optional<at::Scal
   const int64_t B = yw_.size(0), Cout = yw_.size(1), H = yw_.size(2), m = yw_.size(3);
   const FnoTailRoute route =
       fno_c2r_pw_route(0, static_cast<int>(Cout), static_cast<int>(m), static_cast<int>(W), dt == at::kBFloat16);
-  const bool wide = route.kind == FnoTailKind::Wide;  // Cout > 32: fno_c2r_pw_wide.hip, 64-pixel chunks
-  if (route.kind == FnoTailKind::Split || B * Cout * H * W >= (int64_t(1) << 31)) {
-    // shapes outside the fused kernel: C2R on the FFT kernels
-    static auto c2r = c10::Dispatcher::singleton()
-                          .findSchemaOrThrow("amd_dft::c2r", "")
-                          .typed<at::Tensor(const at::Tensor&, at::IntArrayRef, at::IntArrayRef, double,
-                                            at::IntArrayRef, std::optional<at::ScalarType>)>();
-    const std::vector<int64_t> dim{3}, out_size{W};
-    return c2r.call(yw_.to(at::kFloat).contiguous(), dim, out_size, 1.0, {}, dt);
-  }
-  at::Tensor yw = yw_.to(at::kFloat).contiguous();
-  // the tail kernel reads 4 modes per 16-byte load: a view at an odd float2 offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(yw.data_ptr()) % 16 != 0) yw = yw.clone();
-  at::Tensor y = at::empty({B, Cout, H, W}, yw.options().dtype(dt));
-  auto tabs = get_dft_gemm_tables(dt == at::kBFloat16 && !wide ? DftTable::C2R_BF16 : DftTable::C2R_F32,
-                                  static_cast<int>(W), static_cast<int>(m), yw.device());
-  FnoC2RPwLaunch p;
-  p.yw = yw.data_ptr();
-  p.x = nullptr;  // spectral path only
-  p.wc = nullptr;
-  p.bias = nullptr;
-  p.y = y.data_ptr();
-  p.g0 = tabs.first.data_ptr();
-  p.rot = tabs.second.data_ptr();
-  p.B = static_cast<int>(B);
-  p.Cin = 0;
-  p.Cout = static_cast<int>(Cout);
-  p.H = static_cast<int>(H);
-  p.W = static_cast<int>(W);
-  p.m = static_cast<int>(m);
-  p.bf16 = dt == at::kBFloat16;
-  p.gelu = 0;
-  if (wide) launch_fno_c2r_pw_wide(p, c10::hip::getCurrentHIPStream(yw.device().index()).stream());
-  else launch_fno_c2r_pw(p, c10::hip::getCurrentHIPStream(yw.device().index()).stream());
+  if (route.kind == FnoTailKind::Split || B * Cout * H * W >= (int64_t(1) << 31)) return fno_tail_c2r(yw_, W, dt);
+  at::Tensor y = at::empty({B, Cout, H, W}, yw_.options().dtype(dt));
+  fno_tail_launch(route.kind == FnoTailKind::Wide, yw_, nullptr, nullptr, c10::nullopt, false, y);
   return checked(y, "fno_c2r");
 }
 
@@ -673,7 +526,7 @@ void check_legendre_common(bool vec, const at::Tensor& x, const at::Tensor& tabl
   TORCH_CHECK(tri >= 0 && tri <= 2, op, ": tri must be 0, 1 or 2");
   TORCH_CHECK(table.size(0) < (1 << 30) && table.size(1) < (1 << 30) && table.size(2) >= 1 && table.size(2) < (1 << 30),
               op, ": bad table size");
-  const int64_t Rp = (table.size(1) + 15) / 16 * 16, Qp = (table.size(2) + 31) / 32 * 32;
+  const int64_t Rp = ceil16(table.size(1)), Qp = ceil32(table.size(2));
   for (const c10::optional<at::Tensor>* ts : splits) {
     if (!present(*ts)) continue;
     TORCH_CHECK((*ts)->scalar_type() == at::kBFloat16 &&
@@ -698,7 +551,8 @@ void check_legendre_common(bool vec, const at::Tensor& x, const at::Tensor& tabl
 // table zero-padded to [M, ceil16(R), ceil32(Q)] -> bf16 [2, M, Rp, Qp]; built per call when absent.  For a bf16
 // table it is the padded table itself, [1, M, Rp, Qp].
 // legendre_out writes into a given contiguous tensor of the result's shape and dtype.
-void check_legendre(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
+void check_legendre(const char*, const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
+                    int64_t tri) {
   const bool bf16 = x.scalar_type() == at::kBFloat16;
   TORCH_CHECK((x.scalar_type() == at::kFloat || bf16) && table.scalar_type() == x.scalar_type(),
               "legendre: x and table must both be float32 or both be bfloat16, got ", x.scalar_type(), " and ",
@@ -713,11 +567,10 @@ std::vector<int64_t> legendre_out_shape(const at::Tensor& x, const at::Tensor& t
   return shape;
 }
 
-at::Tensor legendre_cpu(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
-  check_legendre(x, table, ts, tri);
+at::Tensor legendre_ref(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri) {
   const int64_t M = table.size(0), R = table.size(1), Q = table.size(2);
   if (x.scalar_type() == at::kBFloat16)  // the bf16 operands as they are, the product in fp32, rounded once
-    return legendre_cpu(x.to(at::kFloat), table.to(at::kFloat), c10::nullopt, tri).to(at::kBFloat16);
+    return legendre_ref(x.to(at::kFloat), table.to(at::kFloat), c10::nullopt, tri).to(at::kBFloat16);
   at::Tensor t = table, xs = x.reshape({-1, Q, M, 2});
   if (tri != 0) {
     at::Tensor m = at::arange(M, table.options().dtype(at::kLong)).unsqueeze(1);
@@ -731,14 +584,6 @@ at::Tensor legendre_cpu(const at::Tensor& x, const at::Tensor& table, const c10:
   return y.reshape(legendre_out_shape(x, table)).contiguous();
 }
 
-at::Tensor& legendre_out_cpu(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
-                             int64_t tri, at::Tensor& out) {
-  check_legendre(x, table, ts, tri);
-  check_out(out, legendre_out_shape(x, table), x, "legendre_out");
-  out.copy_(legendre_cpu(x, table, ts, tri));
-  return out;
-}
-
 // a table as the kernel reads it: its split form where the caller gave one, else the table zero-padded to
 // [M, Rp, Qp] and split into bf16 planes [2, M, Rp, Qp] (a bf16 table: the padded table itself, [1, M, Rp, Qp])
 at::Tensor legendre_table_planes(bool vec, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
@@ -747,7 +592,7 @@ at::Tensor legendre_table_planes(bool vec, const at::Tensor& table, const c10::o
   TORCH_CHECK(table.device() == x.device(),
               vec ? "legendre_vec: ta and tb must be on the device of x" : "legendre: table must be on the device of x");
   const int64_t M = table.size(0), R = table.size(1), Q = table.size(2);
-  const int64_t Rp = (R + 15) / 16 * 16, Qp = (Q + 31) / 32 * 32;
+  const int64_t Rp = ceil16(R), Qp = ceil32(Q);
   at::Tensor tp = at::constant_pad_nd(table, {0, Qp - Q, 0, Rp - R}).contiguous();
   if (x.scalar_type() == at::kBFloat16) return tp.unsqueeze(0);
   at::Tensor planes = at::empty({2, M, Rp, Qp}, tp.options().dtype(at::kBFloat16));
@@ -763,12 +608,11 @@ void legendre_run(const at::Tensor& x_, const at::Tensor& ta, const c10::optiona
                   const at::Tensor* tb, const c10::optional<at::Tensor>& tbs, int64_t tri, const at::Tensor& y) {
   const bool vec = tb != nullptr;
   const int64_t M = ta.size(0), R = ta.size(1), Q = ta.size(2);
-  const int64_t plane = M * ((R + 15) / 16 * 16) * ((Q + 31) / 32 * 32);
-  auto stream = c10::hip::getCurrentHIPStream(x_.device().index()).stream();
+  const int64_t plane = M * ceil16(R) * ceil32(Q);
+  auto stream = current_stream(x_);
   const bool bf16 = x_.scalar_type() == at::kBFloat16;
-  at::Tensor x = x_.contiguous();
   // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % (bf16 ? 4 : 8) != 0) x = x.clone();
+  at::Tensor x = aligned_to(x_.contiguous(), bf16 ? 4 : 8);
   at::Tensor ap = legendre_table_planes(vec, ta, tas, x, stream), bp;
   if (vec) bp = legendre_table_planes(vec, *tb, tbs, x, stream);
   if (y.numel() == 0) return;
@@ -793,34 +637,25 @@ void legendre_run(const at::Tensor& x_, const at::Tensor& ta, const c10::optiona
   else launch_legendre(p, stream);
 }
 
-at::Tensor legendre_cuda(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
-                         int64_t tri) {
-  check_legendre(x, table, ts, tri);
-  const c10::DeviceGuard guard(x.device());
-  at::Tensor y = at::empty(legendre_out_shape(x, table), x.options());
-  legendre_run(x, table, ts, nullptr, c10::nullopt, tri, y);
-  return checked(y, "legendre");
-}
-
-at::Tensor& legendre_out_cuda(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts,
-                              int64_t tri, at::Tensor& out) {
-  check_legendre(x, table, ts, tri);
-  check_out(out, legendre_out_shape(x, table), x, "legendre_out");
-  check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 4 : 8, "legendre_out");
-  const c10::DeviceGuard guard(x.device());
-  legendre_run(x, table, ts, nullptr, c10::nullopt, tri, out);
-  checked(out, "legendre_out");
-  return out;
-}
-
-at::Tensor legendre_meta(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>&, int64_t) {
-  return at::empty(legendre_out_shape(x, table), x.options());
-}
-
-at::Tensor& legendre_out_meta(const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&, int64_t,
-                              at::Tensor& out) {
-  return out;
-}
+struct Legendre : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&, int64_t);
+  static constexpr const char *name = "legendre", *out_name = "legendre_out";
+  static constexpr auto& check = check_legendre;
+  template <class... A>
+  static OpResult result(const at::Tensor& x, const at::Tensor& table, const A&...) {
+    return {legendre_out_shape(x, table), x.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& x, const A&...) {  // one (re, im) pair
+    return 2 * x.element_size();
+  }
+  static constexpr auto& reference = legendre_ref;
+  static void run(const at::Tensor& x, const at::Tensor& table, const c10::optional<at::Tensor>& ts, int64_t tri,
+                  const at::Tensor& y) {
+    legendre_run(x, table, ts, nullptr, c10::nullopt, tri, y);
+  }
+};
+AMD_DFT_OP_FAMILY(legendre, Legendre)
 
 // Which tiling legendre runs for (Q, R, M, real columns = 2 x fields, tri) -- host only, no device (the companion
 // of fno_pointwise_info): "mfma MT=8 CT=2 slabs=23 rtiles=4 rgroups=1 mgroups=8 ctiles=3 lds=41472 wgs=24 tri=1";
@@ -854,7 +689,7 @@ std::string legendre_vec_info(int64_t Q, int64_t R, int64_t M, int64_t cols, int
 //   y[n, 1, r, m] = sum_q ta[m, r, q] x[n, 1, q, m] + i tb[m, r, q] x[n, 0, q, m]
 // All float32 (bf16x3) or all bfloat16, as legendre; tri, the split forms and the _out variant are legendre's too,
 // with tri declaring the same zero part of both tables.
-void check_legendre_vec(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+void check_legendre_vec(const char*, const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
                         const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
   const bool bf16 = x.scalar_type() == at::kBFloat16;
   TORCH_CHECK((x.scalar_type() == at::kFloat || bf16) && ta.scalar_type() == x.scalar_type() &&
@@ -869,15 +704,14 @@ void check_legendre_vec(const at::Tensor& x, const at::Tensor& ta, const at::Ten
   check_legendre_common(true, x, ta, {&tas, &tbs}, tri);
 }
 
-at::Tensor legendre_vec_cpu(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
+at::Tensor legendre_vec_ref(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
                             const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
-  check_legendre_vec(x, ta, tb, tas, tbs, tri);
   // the definition: four plain transforms and the two rotations; y0 = A x0 - i B x1, y1 = A x1 + i B x0
   if (x.scalar_type() == at::kBFloat16)  // the bf16 operands as they are, everything in fp32, rounded once
-    return legendre_vec_cpu(x.to(at::kFloat), ta.to(at::kFloat), tb.to(at::kFloat), c10::nullopt, c10::nullopt, tri)
+    return legendre_vec_ref(x.to(at::kFloat), ta.to(at::kFloat), tb.to(at::kFloat), c10::nullopt, c10::nullopt, tri)
         .to(at::kBFloat16);
-  at::Tensor a = legendre_cpu(x, ta, c10::nullopt, tri);  // [..., 2, R, M, 2]: (A x0, A x1)
-  at::Tensor b = legendre_cpu(x, tb, c10::nullopt, tri);  //                    (B x0, B x1)
+  at::Tensor a = legendre_ref(x, ta, c10::nullopt, tri);  // [..., 2, R, M, 2]: (A x0, A x1)
+  at::Tensor b = legendre_ref(x, tb, c10::nullopt, tri);  //                    (B x0, B x1)
   at::Tensor b0 = b.select(-4, 0), b1 = b.select(-4, 1);
   // -i (re, im) = (im, -re);  +i (re, im) = (-im, re)
   at::Tensor r0 = at::stack({b1.select(-1, 1), b1.select(-1, 0).neg()}, -1);
@@ -885,46 +719,18 @@ at::Tensor legendre_vec_cpu(const at::Tensor& x, const at::Tensor& ta, const at:
   return (a + at::stack({r0, r1}, -4)).contiguous();
 }
 
-at::Tensor& legendre_vec_out_cpu(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
-                                 const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs,
-                                 int64_t tri, at::Tensor& out) {
-  check_legendre_vec(x, ta, tb, tas, tbs, tri);
-  check_out(out, legendre_out_shape(x, ta), x, "legendre_vec_out");
-  out.copy_(legendre_vec_cpu(x, ta, tb, tas, tbs, tri));
-  return out;
-}
-
-at::Tensor legendre_vec_cuda(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
-                             const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs, int64_t tri) {
-  check_legendre_vec(x, ta, tb, tas, tbs, tri);
-  const c10::DeviceGuard guard(x.device());
-  at::Tensor y = at::empty(legendre_out_shape(x, ta), x.options());
-  legendre_run(x, ta, tas, &tb, tbs, tri, y);
-  return checked(y, "legendre_vec");
-}
-
-at::Tensor& legendre_vec_out_cuda(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb,
-                                  const c10::optional<at::Tensor>& tas, const c10::optional<at::Tensor>& tbs,
-                                  int64_t tri, at::Tensor& out) {
-  check_legendre_vec(x, ta, tb, tas, tbs, tri);
-  check_out(out, legendre_out_shape(x, ta), x, "legendre_vec_out");
-  check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 4 : 8, "legendre_vec_out");
-  const c10::DeviceGuard guard(x.device());
-  legendre_run(x, ta, tas, &tb, tbs, tri, out);
-  checked(out, "legendre_vec_out");
-  return out;
-}
-
-at::Tensor legendre_vec_meta(const at::Tensor& x, const at::Tensor& ta, const at::Tensor&,
-                             const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t) {
-  return at::empty(legendre_out_shape(x, ta), x.options());
-}
-
-at::Tensor& legendre_vec_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&,
-                                  const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t,
-                                  at::Tensor& out) {
-  return out;
-}
+struct LegendreVec : Legendre {  // result and out_align are legendre's, from x and the first table
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&,
+                         const c10::optional<at::Tensor>&, int64_t);
+  static constexpr const char *name = "legendre_vec", *out_name = "legendre_vec_out";
+  static constexpr auto& check = check_legendre_vec;
+  static constexpr auto& reference = legendre_vec_ref;
+  static void run(const at::Tensor& x, const at::Tensor& ta, const at::Tensor& tb, const c10::optional<at::Tensor>& tas,
+                  const c10::optional<at::Tensor>& tbs, int64_t tri, const at::Tensor& y) {
+    legendre_run(x, ta, tas, &tb, tbs, tri, y);
+  }
+};
+AMD_DFT_OP_FAMILY(legendre_vec, LegendreVec)
 
 // ------------------------------------------------------------------ DISCO convolution on the sphere (gather half)
 // x [..., nlat_in, nlon_in], a longitude-invariant filter tensor in CSR over rows p * nlat_out + k' (row_ptr int32
@@ -959,14 +765,14 @@ void check_disco(const char* op, const at::Tensor& x, const at::Tensor& row_ptr,
 }
 
 std::vector<int64_t> disco_out_shape(const at::Tensor& x, int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  TORCH_CHECK(x.dim() >= 2, "disco: x must be [..., nlat_in, nlon_in]");
   std::vector<int64_t> s(x.sizes().begin(), x.sizes().end() - 2);
   s.insert(s.end(), {K, nlat_out, nlon_out});
   return s;
 }
 
-at::Tensor disco_cpu(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+at::Tensor disco_ref(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
                      int64_t K, int64_t nlat_out, int64_t nlon_out) {
-  check_disco("disco", x, row_ptr, idx, val, K, nlat_out, nlon_out);
   const int64_t nlat_in = x.size(-2), nlon_in = x.size(-1), s = nlon_in / nlon_out, rows = K * nlat_out;
   const int64_t nnz = idx.size(0), pin = nlat_in * nlon_in;
   const at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vd = val.to(at::kDouble).contiguous();
@@ -1003,14 +809,6 @@ at::Tensor disco_cpu(const at::Tensor& x, const at::Tensor& row_ptr, const at::T
   return y.to(x.scalar_type());
 }
 
-at::Tensor& disco_out_cpu(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
-                          int64_t K, int64_t nlat_out, int64_t nlon_out, at::Tensor& out) {
-  check_disco("disco_out", x, row_ptr, idx, val, K, nlat_out, nlon_out);
-  check_out(out, disco_out_shape(x, K, nlat_out, nlon_out), x, "disco_out");
-  out.copy_(disco_cpu(x, row_ptr, idx, val, K, nlat_out, nlon_out));
-  return out;
-}
-
 // the launch path of disco and disco_out (y contiguous, x's dtype)
 void disco_run(const at::Tensor& x_, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val, int64_t K,
                int64_t nlat_out, int64_t nlon_out, const at::Tensor& y) {
@@ -1031,47 +829,34 @@ void disco_run(const at::Tensor& x_, const at::Tensor& row_ptr, const at::Tensor
   p.nlon_out = static_cast<int>(nlon_out);
   p.nnz = idx.size(0);
   p.bf16 = x.scalar_type() == at::kBFloat16 ? 1 : 0;
-  launch_disco(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  launch_disco(p, current_stream(x));
 }
 
-void check_disco_device(const char* op, const at::Tensor& x, int64_t nlat_out, int64_t nlon_out) {
+void check_disco_device(const char* op, const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                        int64_t, int64_t nlat_out, int64_t nlon_out) {
   TORCH_CHECK(x.size(-1) * 4 <= kDiscoLdsBytes, op, ": nlon_in must be at most ", kDiscoLdsBytes / 4,
               " on the device (one input row per LDS chunk), got ", x.size(-1));
   TORCH_CHECK(nlon_out < (int64_t(1) << 28) && nlat_out < (int64_t(1) << 30), op, ": output grid too large");
 }
 
-at::Tensor disco_cuda(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
-                      int64_t K, int64_t nlat_out, int64_t nlon_out) {
-  check_disco("disco", x, row_ptr, idx, val, K, nlat_out, nlon_out);
-  check_disco_device("disco", x, nlat_out, nlon_out);
-  const c10::DeviceGuard guard(x.device());
-  at::Tensor y = at::empty(disco_out_shape(x, K, nlat_out, nlon_out), x.options());
-  disco_run(x, row_ptr, idx, val, K, nlat_out, nlon_out, y);
-  return checked(y, "disco");
-}
-
-at::Tensor& disco_out_cuda(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx,
-                           const at::Tensor& val, int64_t K, int64_t nlat_out, int64_t nlon_out, at::Tensor& out) {
-  check_disco("disco_out", x, row_ptr, idx, val, K, nlat_out, nlon_out);
-  check_disco_device("disco_out", x, nlat_out, nlon_out);
-  check_out(out, disco_out_shape(x, K, nlat_out, nlon_out), x, "disco_out");
-  check_out_aligned(out, x.scalar_type() == at::kBFloat16 ? 2 : 4, "disco_out");
-  const c10::DeviceGuard guard(x.device());
-  disco_run(x, row_ptr, idx, val, K, nlat_out, nlon_out, out);
-  checked(out, "disco_out");
-  return out;
-}
-
-at::Tensor disco_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t K,
-                      int64_t nlat_out, int64_t nlon_out) {
-  TORCH_CHECK(x.dim() >= 2, "disco: x must be [..., nlat_in, nlon_in]");
-  return at::empty(disco_out_shape(x, K, nlat_out, nlon_out), x.options());
-}
-
-at::Tensor& disco_out_meta(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t,
-                           int64_t, at::Tensor& out) {
-  return out;
-}
+struct Disco : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t,
+                         int64_t);
+  static constexpr const char *name = "disco", *out_name = "disco_out";
+  static constexpr auto& check = check_disco;
+  static constexpr auto& check_device = check_disco_device;
+  static OpResult result(const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t K,
+                         int64_t nlat_out, int64_t nlon_out) {
+    return {disco_out_shape(x, K, nlat_out, nlon_out), x.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& x, const A&...) {  // element stores
+    return x.element_size();
+  }
+  static constexpr auto& reference = disco_ref;
+  static constexpr auto& run = disco_run;
+};
+AMD_DFT_OP_FAMILY(disco, Disco)
 
 // Which instance and grid disco runs -- host only, no device; from disco_route, which launch_disco dispatches on:
 // "PT=4 rows=11 lds=63360 ptiles=16 wgs=2880 passes=2 items=3 threads=256".  nnz_max: the entry count the launch is
@@ -1098,7 +883,8 @@ std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t
 // returns exact zeros.  w_split: the weights as the kernel reads them (sfno_mix_split); built per call when absent.
 // All three bfloat16 instead: bf16 operands as they are on one MFMA per fragment pair, fp32 accumulation, one rounding
 // at the store.  c and w of different dtypes raise.
-void check_sfno_mix(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
+void check_sfno_mix(const char*, const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws,
+                    int64_t tri) {
   const bool bf16 = c.scalar_type() == at::kBFloat16;
   TORCH_CHECK((c.scalar_type() == at::kFloat || bf16) && w.scalar_type() == c.scalar_type(),
               "sfno_mix: c and w must both be float32 or both be bfloat16, got ", c.scalar_type(), " and ",
@@ -1112,7 +898,7 @@ void check_sfno_mix(const at::Tensor& c, const at::Tensor& w, const c10::optiona
                   c.size(0) * c.size(3) < (int64_t(1) << 30),
               "sfno_mix: tensor too large");
   if (present(ws)) {
-    const int64_t Op = (w.size(1) + 15) / 16 * 16, Kp = (2 * w.size(0) + 31) / 32 * 32;
+    const int64_t Op = ceil16(w.size(1)), Kp = ceil32(2 * w.size(0));
     TORCH_CHECK(ws->scalar_type() == at::kBFloat16 &&
                     ws->sizes() == at::IntArrayRef({bf16 ? 1 : 2, w.size(2), Op, Kp}) && ws->device() == c.device(),
                 "sfno_mix: w_split must be bfloat16 [", bf16 ? 1 : 2,
@@ -1130,7 +916,7 @@ at::Tensor sfno_mix_split(const at::Tensor& w) {
               "sfno_mix_split: w must be float32 or bfloat16, got ", w.scalar_type());
   TORCH_CHECK(w.dim() == 4 && w.size(3) == 2 && w.size(0) >= 1, "sfno_mix_split: w [Cin, Cout, L, 2]");
   const int64_t Cin = w.size(0), Cout = w.size(1), L = w.size(2);
-  const int64_t Op = (Cout + 15) / 16 * 16, Kp = (2 * Cin + 31) / 32 * 32;
+  const int64_t Op = ceil16(Cout), Kp = ceil32(2 * Cin);
   at::Tensor wp = at::constant_pad_nd(w.detach().permute({2, 1, 0, 3}).reshape({L, Cout, 2 * Cin}),
                                       {0, Kp - 2 * Cin, 0, Op - Cout})
                       .contiguous();
@@ -1140,7 +926,7 @@ at::Tensor sfno_mix_split(const at::Tensor& w) {
     at::Tensor ts = at::empty({2, L, Op, Kp}, wp.options().dtype(at::kBFloat16));
     if (wp.numel() > 0)
       launch_split_bf16(wp.data_ptr<float>(), reinterpret_cast<uint16_t*>(ts.data_ptr()), wp.numel(),
-                        static_cast<int>(Kp), false, c10::hip::getCurrentHIPStream(wp.device().index()).stream());
+                        static_cast<int>(Kp), false, current_stream(wp));
     return ts;
   }
   at::Tensor hi = wp.to(at::kBFloat16);
@@ -1148,10 +934,9 @@ at::Tensor sfno_mix_split(const at::Tensor& w) {
   return at::stack({hi, lo}, 0).contiguous();
 }
 
-at::Tensor sfno_mix_cpu(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
-  check_sfno_mix(c, w, ws, tri);
+at::Tensor sfno_mix_ref(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
   if (c.scalar_type() == at::kBFloat16)  // the bf16 operands as they are, the product in fp32, rounded once
-    return sfno_mix_cpu(c.to(at::kFloat), w.to(at::kFloat), c10::nullopt, tri).to(at::kBFloat16);
+    return sfno_mix_ref(c.to(at::kFloat), w.to(at::kFloat), c10::nullopt, tri).to(at::kBFloat16);
   at::Tensor y = at::view_as_real(at::einsum("bilm,iol->bolm", {at::view_as_complex(c.contiguous()),
                                                                at::view_as_complex(w.contiguous())}))
                      .contiguous();
@@ -1163,27 +948,14 @@ at::Tensor sfno_mix_cpu(const at::Tensor& c, const at::Tensor& w, const c10::opt
   return y;
 }
 
-std::vector<int64_t> sfno_mix_out_shape(const at::Tensor& c, const at::Tensor& w) {
-  return {c.size(0), w.size(1), c.size(2), c.size(3), 2};
-}
-
-at::Tensor& sfno_mix_out_cpu(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri,
-                             at::Tensor& out) {
-  check_sfno_mix(c, w, ws, tri);
-  check_out(out, sfno_mix_out_shape(c, w), c, "sfno_mix_out");
-  out.copy_(sfno_mix_cpu(c, w, ws, tri));
-  return out;
-}
-
 // the launch path of sfno_mix and sfno_mix_out: y is the contiguous result, aligned to one (re, im) pair (8 bytes
 // fp32, 4 bytes bf16: the kernel's stores)
 void sfno_mix_run(const at::Tensor& c_, const at::Tensor& w_, const c10::optional<at::Tensor>& ws_, int64_t tri,
                   const at::Tensor& y) {
   const int64_t B = c_.size(0), Cin = c_.size(1), L = c_.size(2), M = c_.size(3), Cout = w_.size(1);
   const bool bf16 = c_.scalar_type() == at::kBFloat16;
-  at::Tensor c = c_.contiguous();
   // one load per order's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy
-  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % (bf16 ? 4 : 8) != 0) c = c.clone();
+  at::Tensor c = aligned_to(c_.contiguous(), bf16 ? 4 : 8);
   at::Tensor ws = present(ws_) ? ws_->contiguous() : sfno_mix_split(w_);
   if (y.numel() == 0) return;
   SfnoMixLaunch p;
@@ -1198,36 +970,25 @@ void sfno_mix_run(const at::Tensor& c_, const at::Tensor& w_, const c10::optiona
   p.L = static_cast<int>(L);
   p.M = static_cast<int>(M);
   p.tri = static_cast<int>(tri);
-  launch_sfno_mix(p, c10::hip::getCurrentHIPStream(c.device().index()).stream());
+  launch_sfno_mix(p, current_stream(c));
 }
 
-at::Tensor sfno_mix_cuda(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws, int64_t tri) {
-  check_sfno_mix(c, w, ws, tri);
-  const c10::DeviceGuard guard(c.device());
-  at::Tensor y = at::empty(sfno_mix_out_shape(c, w), c.options());
-  sfno_mix_run(c, w, ws, tri, y);
-  return checked(y, "sfno_mix");
-}
-
-at::Tensor& sfno_mix_out_cuda(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>& ws,
-                              int64_t tri, at::Tensor& out) {
-  check_sfno_mix(c, w, ws, tri);
-  check_out(out, sfno_mix_out_shape(c, w), c, "sfno_mix_out");
-  check_out_aligned(out, c.scalar_type() == at::kBFloat16 ? 4 : 8, "sfno_mix_out");
-  const c10::DeviceGuard guard(c.device());
-  sfno_mix_run(c, w, ws, tri, out);
-  checked(out, "sfno_mix_out");
-  return out;
-}
-
-at::Tensor sfno_mix_meta(const at::Tensor& c, const at::Tensor& w, const c10::optional<at::Tensor>&, int64_t) {
-  return at::empty({c.size(0), w.size(1), c.size(2), c.size(3), 2}, c.options());
-}
-
-at::Tensor& sfno_mix_out_meta(const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&, int64_t,
-                              at::Tensor& out) {
-  return out;
-}
+struct SfnoMix : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&, int64_t);
+  static constexpr const char *name = "sfno_mix", *out_name = "sfno_mix_out";
+  static constexpr auto& check = check_sfno_mix;
+  template <class... A>
+  static OpResult result(const at::Tensor& c, const at::Tensor& w, const A&...) {
+    return {{c.size(0), w.size(1), c.size(2), c.size(3), 2}, c.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& c, const A&...) {  // one (re, im) pair
+    return 2 * c.element_size();
+  }
+  static constexpr auto& reference = sfno_mix_ref;
+  static constexpr auto& run = sfno_mix_run;
+};
+AMD_DFT_OP_FAMILY(sfno_mix, SfnoMix)
 
 // The tiling sfno_mix runs for (B, Cin, Cout, L, M, tri) -- host only, no device (the companion of legendre_info):
 // "mfma coltile=64 slabs=4 otiles=4 ogroups=1 ctiles=3 lds=20480 wgs=363 grid=540 tri=1"; bf16: the same tiling with
@@ -1251,13 +1012,17 @@ std::string sfno_mix_info(int64_t B, int64_t Cin, int64_t Cout, int64_t L, int64
 struct InDims {
   int64_t B, C, P;
 };
+InDims instance_norm_dims(const at::Tensor& x) {
+  InDims d{x.size(0), x.size(1), 1};
+  for (int64_t i = 2; i < x.dim(); ++i) d.P *= x.size(i);
+  return d;
+}
 InDims check_instance_norm(const char* op, const at::Tensor& x, const c10::optional<at::Tensor>& w,
                            const c10::optional<at::Tensor>& b) {
   TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, op,
               ": x must be float32 or bfloat16, got ", x.scalar_type());
   TORCH_CHECK(x.dim() >= 3, op, ": x must be [B, C, *spatial] with at least one spatial dimension, got ", x.sizes());
-  InDims d{x.size(0), x.size(1), 1};
-  for (int64_t i = 2; i < x.dim(); ++i) d.P *= x.size(i);
+  const InDims d = instance_norm_dims(x);
   TORCH_CHECK(d.C >= 1, op, ": x has no channels");
   TORCH_CHECK(d.P >= 2, op, ": expected more than 1 spatial element per channel, got input of size ", x.sizes());
   TORCH_CHECK(d.P < (int64_t(1) << 31) && d.C < (int64_t(1) << 31), op, ": tensor too large");
@@ -1283,23 +1048,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> instance_norm_moments_cpu(const a
   return {xc, mean, rstd};
 }
 
-at::Tensor instance_norm_cpu(const at::Tensor& x, const c10::optional<at::Tensor>& w,
+at::Tensor instance_norm_ref(const at::Tensor& x, const c10::optional<at::Tensor>& w,
                              const c10::optional<at::Tensor>& b, double eps) {
-  const InDims d = check_instance_norm("instance_norm", x, w, b);
+  const InDims d = instance_norm_dims(x);
   if (x.numel() == 0) return at::empty_like(x, at::MemoryFormat::Contiguous);
   auto [xc, mean, rstd] = instance_norm_moments_cpu(x, d, eps);
   at::Tensor y = xc * rstd;
   if (present(w)) y = y * w->to(at::kDouble).reshape({1, d.C, 1});
   if (present(b)) y = y + b->to(at::kDouble).reshape({1, d.C, 1});
   return y.reshape(x.sizes()).to(x.scalar_type());
-}
-
-at::Tensor& instance_norm_out_cpu(const at::Tensor& x, const c10::optional<at::Tensor>& w,
-                                  const c10::optional<at::Tensor>& b, double eps, at::Tensor& out) {
-  check_instance_norm("instance_norm_out", x, w, b);
-  check_out(out, x.sizes(), x, "instance_norm_out");
-  out.copy_(instance_norm_cpu(x, w, b, eps));
-  return out;
 }
 
 at::Tensor instance_norm_stats_cpu(const at::Tensor& x, double eps) {
@@ -1332,28 +1089,31 @@ void instance_norm_run(const InDims& d, const at::Tensor& x_, const c10::optiona
   p.C = static_cast<int>(d.C);
   p.eps = static_cast<float>(eps);
   p.bf16 = bf16 ? 1 : 0;
-  launch_instance_norm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  launch_instance_norm(p, current_stream(x));
 }
 
-at::Tensor instance_norm_cuda(const at::Tensor& x, const c10::optional<at::Tensor>& w,
-                              const c10::optional<at::Tensor>& b, double eps) {
-  const InDims d = check_instance_norm("instance_norm", x, w, b);
-  const c10::DeviceGuard guard(x.device());
-  at::Tensor y = at::empty(x.sizes(), x.options());
-  instance_norm_run(d, x, w, b, eps, y, at::Tensor());
-  return checked(y, "instance_norm");
-}
-
-at::Tensor& instance_norm_out_cuda(const at::Tensor& x, const c10::optional<at::Tensor>& w,
-                                   const c10::optional<at::Tensor>& b, double eps, at::Tensor& out) {
-  const InDims d = check_instance_norm("instance_norm_out", x, w, b);
-  check_out(out, x.sizes(), x, "instance_norm_out");
-  check_out_aligned(out, 16, "instance_norm_out");
-  const c10::DeviceGuard guard(x.device());
-  instance_norm_run(d, x, w, b, eps, out, at::Tensor());
-  checked(out, "instance_norm_out");
-  return out;
-}
+struct InstanceNorm : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, double);
+  static constexpr const char *name = "instance_norm", *out_name = "instance_norm_out";
+  static void check(const char* op, const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                    const c10::optional<at::Tensor>& b, double) {
+    check_instance_norm(op, x, w, b);
+  }
+  template <class... A>
+  static OpResult result(const at::Tensor& x, const A&...) {
+    return {x.sizes(), x.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const A&...) {
+    return 16;
+  }
+  static constexpr auto& reference = instance_norm_ref;
+  static void run(const at::Tensor& x, const c10::optional<at::Tensor>& w, const c10::optional<at::Tensor>& b,
+                  double eps, const at::Tensor& y) {
+    instance_norm_run(instance_norm_dims(x), x, w, b, eps, y, at::Tensor());
+  }
+};
+AMD_DFT_OP_FAMILY(instance_norm, InstanceNorm)
 
 at::Tensor instance_norm_stats_cuda(const at::Tensor& x, double eps) {
   const InDims d = check_instance_norm("instance_norm_stats", x, c10::nullopt, c10::nullopt);
@@ -1361,16 +1121,6 @@ at::Tensor instance_norm_stats_cuda(const at::Tensor& x, double eps) {
   at::Tensor st = at::empty({d.B, d.C, 2}, x.options().dtype(at::kFloat));
   instance_norm_run(d, x, c10::nullopt, c10::nullopt, eps, at::Tensor(), st);
   return checked(st, "instance_norm_stats");
-}
-
-at::Tensor instance_norm_meta(const at::Tensor& x, const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
-                              double) {
-  return at::empty(x.sizes(), x.options());
-}
-
-at::Tensor& instance_norm_out_meta(const at::Tensor&, const c10::optional<at::Tensor>&,
-                                   const c10::optional<at::Tensor>&, double, at::Tensor& out) {
-  return out;
 }
 
 at::Tensor instance_norm_stats_meta(const at::Tensor& x, double) {
@@ -1443,7 +1193,7 @@ std::tuple<at::Tensor, at::Tensor> layer_norm_cuda(const at::Tensor& x_, const a
   p.rows = x.numel() / p.cols;
   p.eps = static_cast<float>(eps);
   p.bf16 = bf16 ? 1 : 0;
-  if (p.rows > 0) launch_layernorm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  if (p.rows > 0) launch_layernorm(p, current_stream(x));
   return {y, xs};
 }
 
@@ -1495,7 +1245,7 @@ at::Tensor layer_norm_split_cuda(const at::Tensor& x_, const at::Tensor& w_, con
   p.bf16 = 0;
   p.split_out = 1;
   p.pre = pre.defined() ? pre.data_ptr<float>() : nullptr;
-  if (p.rows > 0) launch_layernorm(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  if (p.rows > 0) launch_layernorm(p, current_stream(x));
   return y;
 }
 
@@ -1542,7 +1292,7 @@ at::Tensor ln_stats_cuda(const at::Tensor& x_, const std::optional<at::Tensor>& 
   p.cols = static_cast<int>(C);
   p.eps = static_cast<float>(eps);
   p.f32 = f32 ? 1 : 0;
-  if (rows > 0) launch_ln_stats(p, c10::hip::getCurrentHIPStream(x.device().index()).stream());
+  if (rows > 0) launch_ln_stats(p, current_stream(x));
   return checked(st, "ln_stats");
 }
 
@@ -1579,7 +1329,7 @@ at::Tensor ln_stats_merge_cuda(const at::Tensor& part_, double eps, const std::o
   at::Tensor shift = vec_aligned(f32_or_undef(shift_));  // read as float2: 8 bytes would do, the one helper serves
   at::Tensor st = at::empty({part.size(0), 2}, part.options());
   launch_ln_stats_merge(part.data_ptr<float>(), st.data_ptr<float>(), part.size(0), static_cast<int>(part.size(1)), 64,
-                        static_cast<float>(eps), c10::hip::getCurrentHIPStream(part.device().index()).stream(),
+                        static_cast<float>(eps), current_stream(part),
                         shift.defined() ? shift.data_ptr<float>() : nullptr);
   return checked(st, "ln_stats_merge");
 }
@@ -1617,133 +1367,58 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
 }  // namespace
 }  // namespace amd_dft
 
+// The dispatched ops of this file, once: name and schema.  Each has name_cuda, name_cpu and name_meta above (a
+// family's come from AMD_DFT_OP_FAMILY), so an op missing from one backend fails to compile.
+#define AMD_DFT_SPECTRAL_OPS(X)                                                                                       \
+  X(afno_spectral, "(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam) -> Tensor")                   \
+  X(afno_mlp, "(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam) -> Tensor")                        \
+  X(afno_mlp_out, "(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam, Tensor(a!) out) -> Tensor(a!)") \
+  X(layer_norm, "(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? residual=None) -> (Tensor, Tensor)")       \
+  X(ln_stats, "(Tensor x, Tensor? pre=None, float eps=1e-6) -> Tensor")                                               \
+  X(ln_stats_merge, "(Tensor part, float eps=1e-6, Tensor? shift=None) -> Tensor")                                    \
+  X(layer_norm_split, "(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? pre=None) -> Tensor")                \
+  X(instance_norm, "(Tensor x, Tensor? weight=None, Tensor? bias=None, float eps=1e-5) -> Tensor")                    \
+  X(instance_norm_out, "(Tensor x, Tensor? weight, Tensor? bias, float eps, Tensor(a!) out) -> Tensor(a!)")           \
+  X(instance_norm_stats, "(Tensor x, float eps=1e-5) -> Tensor")                                                      \
+  X(fno_mix, "(Tensor x, Tensor w, int path=0) -> Tensor")                                                            \
+  X(fno_mix_out, "(Tensor x, Tensor w, int path, Tensor(a!) out) -> Tensor(a!)")                                      \
+  X(fno_pointwise, "(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor")                 \
+  X(fno_pointwise_out, "(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)")   \
+  X(fno_c2r_pw, "(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor")                      \
+  X(fno_c2r_pw_out, "(Tensor yw, Tensor x, Tensor wc, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)")        \
+  X(fno_c2r, "(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor")                                              \
+  X(legendre, "(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor")                              \
+  X(legendre_out, "(Tensor x, Tensor table, Tensor? table_split, int tri, Tensor(a!) out) -> Tensor(a!)")             \
+  X(legendre_vec, "(Tensor x, Tensor ta, Tensor tb, Tensor? ta_split=None, Tensor? tb_split=None, int tri=0) -> Tensor") \
+  X(legendre_vec_out, "(Tensor x, Tensor ta, Tensor tb, Tensor? ta_split, Tensor? tb_split, int tri, Tensor(a!) out) " \
+                      "-> Tensor(a!)")                                                                                \
+  X(disco, "(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out) -> Tensor")         \
+  X(disco_out, "(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out, Tensor(a!) out) " \
+               "-> Tensor(a!)")                                                                                       \
+  X(sfno_mix, "(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor")                                      \
+  X(sfno_mix_out, "(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)")
+
 TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
-  m.def("afno_spectral(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam) -> Tensor");
+  AMD_DFT_SPECTRAL_OPS(AMD_DFT_DEF)
+  // host only: no dispatch
   m.def("afno_spectral_supported(int H, int block_size) -> bool", &amd_dft::afno_spectral_ok);
   m.def("afno_spectral_shapes() -> int[]", &amd_dft::afno_spectral_shape_list);
-  m.def("afno_mlp(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam) -> Tensor");
-  m.def("afno_mlp_out(Tensor x, Tensor w1t, Tensor w2t, Tensor b1, Tensor b2, float lam, Tensor(a!) out) -> Tensor(a!)");
   m.def("afno_mlp_info(int block_size, bool split, int tokens) -> str", &amd_dft::afno_mlp_info);
-  m.def("layer_norm(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? residual=None) -> (Tensor, Tensor)");
-  m.def("ln_stats(Tensor x, Tensor? pre=None, float eps=1e-6) -> Tensor");
-  m.def("ln_stats_merge(Tensor part, float eps=1e-6, Tensor? shift=None) -> Tensor");
-  m.def("layer_norm_split(Tensor x, Tensor weight, Tensor bias, float eps, Tensor? pre=None) -> Tensor");
   m.def("ln_info(str op, int C, bool bf16) -> str", &amd_dft::ln_info);
-  m.def("instance_norm(Tensor x, Tensor? weight=None, Tensor? bias=None, float eps=1e-5) -> Tensor");
-  m.def("instance_norm_out(Tensor x, Tensor? weight, Tensor? bias, float eps, Tensor(a!) out) -> Tensor(a!)");
-  m.def("instance_norm_stats(Tensor x, float eps=1e-5) -> Tensor");
   m.def("instance_norm_info(int planes, int P, bool bf16) -> str", &amd_dft::instance_norm_info);
-  m.def("fno_mix(Tensor x, Tensor w, int path=0) -> Tensor");
-  m.def("fno_mix_out(Tensor x, Tensor w, int path, Tensor(a!) out) -> Tensor(a!)");
   m.def("fno_mix_info(int B, int Cin, int Cout, int M, bool bf16=False, int path=0) -> str", &amd_dft::fno_mix_info);
-  m.def("fno_pointwise(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor");
-  m.def("fno_pointwise_out(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");
   m.def("fno_pointwise_info(int cin, int cout, bool bf16, int P) -> str", &amd_dft::fno_pointwise_info);
-  m.def("fno_c2r_pw(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor");
-  m.def("fno_c2r_pw_out(Tensor yw, Tensor x, Tensor wc, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)");
   m.def("fno_c2r_pw_info(int cin, int cout, int m, int W, bool bf16) -> str", &amd_dft::fno_c2r_pw_info);
-  m.def("fno_c2r(Tensor yw, int W, ScalarType? out_dtype=None) -> Tensor");
-  m.def("legendre(Tensor x, Tensor table, Tensor? table_split=None, int tri=0) -> Tensor");
-  m.def("legendre_out(Tensor x, Tensor table, Tensor? table_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("legendre_info(int Q, int R, int M, int cols, int tri, bool bf16=False) -> str", &amd_dft::legendre_info);
-  m.def("legendre_vec(Tensor x, Tensor ta, Tensor tb, Tensor? ta_split=None, Tensor? tb_split=None, int tri=0) -> Tensor");
-  m.def("legendre_vec_out(Tensor x, Tensor ta, Tensor tb, Tensor? ta_split, Tensor? tb_split, int tri, Tensor(a!) out) "
-        "-> Tensor(a!)");
   m.def("legendre_vec_info(int Q, int R, int M, int cols, int tri, bool bf16=False) -> str",
         &amd_dft::legendre_vec_info);
-  m.def("disco(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out) -> Tensor");
-  m.def("disco_out(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out, Tensor(a!) out) "
-        "-> Tensor(a!)");
   m.def("disco_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int nnz_max, "
         "bool bf16=False) -> str",
         &amd_dft::disco_info);
-  m.def("sfno_mix(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor");
-  m.def("sfno_mix_out(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)");
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
   m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri, bool bf16=False) -> str",
         &amd_dft::sfno_mix_info);
 }
-
-TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
-  m.impl("afno_spectral", AMD_DFT_TRACED("amd_dft::afno_spectral", amd_dft::afno_spectral_cuda));
-  m.impl("afno_mlp", AMD_DFT_TRACED("amd_dft::afno_mlp", amd_dft::afno_mlp_cuda));
-  m.impl("afno_mlp_out", AMD_DFT_TRACED("amd_dft::afno_mlp_out", amd_dft::afno_mlp_out_cuda));
-  m.impl("layer_norm", AMD_DFT_TRACED("amd_dft::layer_norm", amd_dft::layer_norm_cuda));
-  m.impl("ln_stats", AMD_DFT_TRACED("amd_dft::ln_stats", amd_dft::ln_stats_cuda));
-  m.impl("ln_stats_merge", AMD_DFT_TRACED("amd_dft::ln_stats_merge", amd_dft::ln_stats_merge_cuda));
-  m.impl("layer_norm_split", AMD_DFT_TRACED("amd_dft::layer_norm_split", amd_dft::layer_norm_split_cuda));
-  m.impl("instance_norm", AMD_DFT_TRACED("amd_dft::instance_norm", amd_dft::instance_norm_cuda));
-  m.impl("instance_norm_out", AMD_DFT_TRACED("amd_dft::instance_norm_out", amd_dft::instance_norm_out_cuda));
-  m.impl("instance_norm_stats", AMD_DFT_TRACED("amd_dft::instance_norm_stats", amd_dft::instance_norm_stats_cuda));
-  m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cuda));
-  m.impl("fno_mix_out", AMD_DFT_TRACED("amd_dft::fno_mix_out", amd_dft::fno_mix_out_cuda));
-  m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cuda));
-  m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cuda));
-  m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cuda));
-  m.impl("fno_c2r_pw_out", AMD_DFT_TRACED("amd_dft::fno_c2r_pw_out", amd_dft::fno_c2r_pw_out_cuda));
-  m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cuda));
-  m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cuda));
-  m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cuda));
-  m.impl("legendre_vec", AMD_DFT_TRACED("amd_dft::legendre_vec", amd_dft::legendre_vec_cuda));
-  m.impl("legendre_vec_out", AMD_DFT_TRACED("amd_dft::legendre_vec_out", amd_dft::legendre_vec_out_cuda));
-  m.impl("disco", AMD_DFT_TRACED("amd_dft::disco", amd_dft::disco_cuda));
-  m.impl("disco_out", AMD_DFT_TRACED("amd_dft::disco_out", amd_dft::disco_out_cuda));
-  m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cuda));
-  m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cuda));
-}
-
-TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
-  m.impl("afno_spectral", AMD_DFT_TRACED("amd_dft::afno_spectral", amd_dft::afno_spectral_cpu));
-  m.impl("afno_mlp", AMD_DFT_TRACED("amd_dft::afno_mlp", amd_dft::afno_mlp_cpu));
-  m.impl("afno_mlp_out", AMD_DFT_TRACED("amd_dft::afno_mlp_out", amd_dft::afno_mlp_out_cpu));
-  m.impl("layer_norm", AMD_DFT_TRACED("amd_dft::layer_norm", amd_dft::layer_norm_cpu));
-  m.impl("ln_stats", AMD_DFT_TRACED("amd_dft::ln_stats", amd_dft::ln_stats_cpu));
-  m.impl("ln_stats_merge", AMD_DFT_TRACED("amd_dft::ln_stats_merge", amd_dft::ln_stats_merge_cpu));
-  m.impl("layer_norm_split", AMD_DFT_TRACED("amd_dft::layer_norm_split", amd_dft::layer_norm_split_cpu));
-  m.impl("instance_norm", AMD_DFT_TRACED("amd_dft::instance_norm", amd_dft::instance_norm_cpu));
-  m.impl("instance_norm_out", AMD_DFT_TRACED("amd_dft::instance_norm_out", amd_dft::instance_norm_out_cpu));
-  m.impl("instance_norm_stats", AMD_DFT_TRACED("amd_dft::instance_norm_stats", amd_dft::instance_norm_stats_cpu));
-  m.impl("fno_mix", AMD_DFT_TRACED("amd_dft::fno_mix", amd_dft::fno_mix_cpu));
-  m.impl("fno_mix_out", AMD_DFT_TRACED("amd_dft::fno_mix_out", amd_dft::fno_mix_out_cpu));
-  m.impl("fno_pointwise", AMD_DFT_TRACED("amd_dft::fno_pointwise", amd_dft::fno_pointwise_cpu));
-  m.impl("fno_pointwise_out", AMD_DFT_TRACED("amd_dft::fno_pointwise_out", amd_dft::fno_pointwise_out_cpu));
-  m.impl("fno_c2r_pw", AMD_DFT_TRACED("amd_dft::fno_c2r_pw", amd_dft::fno_c2r_pw_cpu));
-  m.impl("fno_c2r_pw_out", AMD_DFT_TRACED("amd_dft::fno_c2r_pw_out", amd_dft::fno_c2r_pw_out_cpu));
-  m.impl("fno_c2r", AMD_DFT_TRACED("amd_dft::fno_c2r", amd_dft::fno_c2r_cpu));
-  m.impl("legendre", AMD_DFT_TRACED("amd_dft::legendre", amd_dft::legendre_cpu));
-  m.impl("legendre_out", AMD_DFT_TRACED("amd_dft::legendre_out", amd_dft::legendre_out_cpu));
-  m.impl("legendre_vec", AMD_DFT_TRACED("amd_dft::legendre_vec", amd_dft::legendre_vec_cpu));
-  m.impl("legendre_vec_out", AMD_DFT_TRACED("amd_dft::legendre_vec_out", amd_dft::legendre_vec_out_cpu));
-  m.impl("disco", AMD_DFT_TRACED("amd_dft::disco", amd_dft::disco_cpu));
-  m.impl("disco_out", AMD_DFT_TRACED("amd_dft::disco_out", amd_dft::disco_out_cpu));
-  m.impl("sfno_mix", AMD_DFT_TRACED("amd_dft::sfno_mix", amd_dft::sfno_mix_cpu));
-  m.impl("sfno_mix_out", AMD_DFT_TRACED("amd_dft::sfno_mix_out", amd_dft::sfno_mix_out_cpu));
-}
-
-TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
-  m.impl("afno_spectral", &amd_dft::afno_spectral_meta);
-  m.impl("afno_mlp", &amd_dft::afno_mlp_meta);
-  m.impl("afno_mlp_out", &amd_dft::afno_mlp_out_meta);
-  m.impl("layer_norm", &amd_dft::layer_norm_meta);
-  m.impl("ln_stats", &amd_dft::ln_stats_meta);
-  m.impl("ln_stats_merge", &amd_dft::ln_stats_merge_meta);
-  m.impl("layer_norm_split", &amd_dft::layer_norm_split_meta);
-  m.impl("instance_norm", &amd_dft::instance_norm_meta);
-  m.impl("instance_norm_out", &amd_dft::instance_norm_out_meta);
-  m.impl("instance_norm_stats", &amd_dft::instance_norm_stats_meta);
-  m.impl("fno_mix", &amd_dft::fno_mix_meta);
-  m.impl("fno_mix_out", &amd_dft::fno_mix_out_meta);
-  m.impl("fno_pointwise", &amd_dft::fno_pointwise_meta);
-  m.impl("fno_pointwise_out", &amd_dft::fno_pointwise_out_meta);
-  m.impl("fno_c2r_pw", &amd_dft::fno_c2r_pw_meta);
-  m.impl("fno_c2r_pw_out", &amd_dft::fno_c2r_pw_out_meta);
-  m.impl("fno_c2r", &amd_dft::fno_c2r_meta);
-  m.impl("legendre", &amd_dft::legendre_meta);
-  m.impl("legendre_out", &amd_dft::legendre_out_meta);
-  m.impl("legendre_vec", &amd_dft::legendre_vec_meta);
-  m.impl("legendre_vec_out", &amd_dft::legendre_vec_out_meta);
-  m.impl("disco", &amd_dft::disco_meta);
-  m.impl("disco_out", &amd_dft::disco_out_meta);
-  m.impl("sfno_mix", &amd_dft::sfno_mix_meta);
-  m.impl("sfno_mix_out", &amd_dft::sfno_mix_out_meta);
-}
+TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) { AMD_DFT_SPECTRAL_OPS(AMD_DFT_IMPL_CUDA) }
+TORCH_LIBRARY_IMPL(amd_dft, CPU, m) { AMD_DFT_SPECTRAL_OPS(AMD_DFT_IMPL_CPU) }
+TORCH_LIBRARY_IMPL(amd_dft, Meta, m) { AMD_DFT_SPECTRAL_OPS(AMD_DFT_IMPL_META) }

@@ -77,3 +77,11 @@ inline auto traced(const char* name) {
 }  // namespace amd_dft
 
 #define AMD_DFT_TRACED(NAME, FN) ::amd_dft::traced<&FN>(NAME)
+
+// Registration from an op table X(name, schema), one row per op: a file lists its ops once and applies these to the
+// list inside TORCH_LIBRARY_FRAGMENT / TORCH_LIBRARY_IMPL(amd_dft, CUDA | CPU | Meta, m).  Each row needs
+// amd_dft::name_cuda, name_cpu and name_meta, so an op missing from one backend fails to compile.
+#define AMD_DFT_DEF(op, schema) m.def(#op schema);
+#define AMD_DFT_IMPL_CUDA(op, schema) m.impl(#op, AMD_DFT_TRACED("amd_dft::" #op, amd_dft::op##_cuda));
+#define AMD_DFT_IMPL_CPU(op, schema) m.impl(#op, AMD_DFT_TRACED("amd_dft::" #op, amd_dft::op##_cpu));
+#define AMD_DFT_IMPL_META(op, schema) m.impl(#op, &amd_dft::op##_meta);
