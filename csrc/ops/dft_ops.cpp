@@ -113,6 +113,31 @@ struct MixIO {
   int cin = 0, cout = 0;
 };
 
+// Everything of a pass descriptor that the kernel selection reads (apply_plan, set_axis_geometry, the mode windows,
+// choose_tiling, finalize_vec_flags), on the host alone.  run_pass launches from it; fft_pass_info and afno_w_info
+// describe from it, so what they report is what a launch decides.  `in` / `out` only have their alignment tested
+// (the info ops pass none: taken as aligned).  Returns false when no tiling of the length fits LDS.
+bool build_pass_desc(PassDesc& d, Kind kind, const Plan1D& plan, const std::vector<int64_t>& in_shape,
+                     const std::vector<int64_t>& out_shape, int axis, int64_t in_lo, int64_t in_hi, int64_t out_lo,
+                     int64_t out_hi, bool inverse, DType tin, DType tout, const void* in = nullptr,
+                     void* out = nullptr) {
+  d.kind = kind;
+  apply_plan(d, plan);
+  set_axis_geometry(d, in_shape, out_shape, axis, kind != Kind::R2C, kind != Kind::C2R);
+  d.in_lo = static_cast<int32_t>(in_lo);
+  d.in_hi = static_cast<int32_t>(in_hi);
+  d.out_lo = static_cast<int32_t>(out_lo);
+  d.out_hi = static_cast<int32_t>(out_hi);
+  d.inverse = inverse ? 1 : 0;
+  d.tin = tin;
+  d.tout = tout;
+  d.in = in;
+  d.out = out;
+  if (!choose_tiling(d)) return false;
+  finalize_vec_flags(d, tin == DType::BF16 ? 2 : 4, tout == DType::BF16 ? 2 : 4);
+  return true;
+}
+
 // Returns false only for an LnIO / MixIO pass that no specialised kernel covers (nothing launched).
 bool run_pass(Kind kind, const at::Tensor& in, const at::Tensor& out, const std::vector<int64_t>& in_shape,
               const std::vector<int64_t>& out_shape, int axis, int64_t L, int in_lo, int in_hi, int out_lo,
@@ -126,25 +151,13 @@ bool run_pass(Kind kind, const at::Tensor& in, const at::Tensor& out, const std:
   }
   auto dp = get_plan(L, in.device());
   PassDesc d;
-  d.kind = kind;
-  apply_plan(d, dp->plan);
+  TORCH_CHECK(build_pass_desc(d, kind, dp->plan, in_shape, out_shape, axis, in_lo, in_hi, out_lo, out_hi, inverse,
+                              to_dtype(in.scalar_type()), to_dtype(out.scalar_type()), in.data_ptr(), out.data_ptr()),
+              "amd_dft: transform length ", L, " exceeds the LDS-resident limit (", max_lds_length(), ")");
   d.tw = dp->tw.data_ptr();
-  set_axis_geometry(d, in_shape, out_shape, axis, kind != Kind::R2C, kind != Kind::C2R);
-  d.in_lo = in_lo;
-  d.in_hi = in_hi;
-  d.out_lo = out_lo;
-  d.out_hi = out_hi;
   d.scale = scale;
-  d.inverse = inverse ? 1 : 0;
-  d.tin = to_dtype(in.scalar_type());
-  d.tout = to_dtype(out.scalar_type());
-  d.in = in.data_ptr();
-  d.out = out.data_ptr();
   d.add1 = add1;
   d.add2 = add2;
-  TORCH_CHECK(choose_tiling(d), "amd_dft: transform length ", L, " exceeds the LDS-resident limit (",
-              max_lds_length(), ")");
-  finalize_vec_flags(d, static_cast<int>(in.element_size()), static_cast<int>(out.element_size()));
   void* stream = c10::hip::getCurrentHIPStream(in.device().index()).stream();
   if (ln) {
     d.ln_stats = ln->stats;
@@ -560,14 +573,24 @@ at::Tensor c2c_cuda(const at::Tensor& x_, at::IntArrayRef dim, bool inverse, dou
 
 // Pruned C2C along one axis: input stores modes [0, in_lo) u [n - in_hi, n) of a length-n
 // transform, output keeps [0, out_lo) u [n - out_hi, n).  Unnormalised, times `scale`.
-void check_c2c_axis(const at::Tensor& x, int64_t dim, int64_t n, int64_t in_lo, int64_t in_hi, int64_t out_lo,
-                    int64_t out_hi) {
+int64_t c2c_axis_dim(const at::Tensor& x, int64_t dim) {  // `dim` among the logical dims (without re/im), from 0
+  const int64_t nd = x.dim() - 1;
+  dim = dim < 0 ? dim + nd : dim;
+  TORCH_CHECK(dim >= 0 && dim < nd, "amd_dft.c2c_axis: dim out of range");
+  return dim;
+}
+
+// Returns the transformed dim, normalised.
+int64_t check_c2c_axis(const at::Tensor& x, int64_t dim, int64_t n, int64_t in_lo, int64_t in_hi, int64_t out_lo,
+                       int64_t out_hi) {
   TORCH_CHECK(x.dim() >= 2 && x.size(-1) == 2, "amd_dft.c2c_axis: complex input needs a trailing dim of size 2");
+  dim = c2c_axis_dim(x, dim);
   TORCH_CHECK(n >= 1 && in_lo >= 0 && in_hi >= 0 && out_lo >= 0 && out_hi >= 0 && in_lo + in_hi <= n &&
                   out_lo + out_hi <= n && in_lo + in_hi >= 1,
               "amd_dft.c2c_axis: bad mode windows");
   TORCH_CHECK(x.size(dim) == in_lo + in_hi, "amd_dft.c2c_axis: dim ", dim, " stores ", x.size(dim),
               " modes, expected in_lo + in_hi = ", in_lo + in_hi);
+  return dim;
 }
 
 at::Tensor c2c_axis_cuda(const at::Tensor& x_, int64_t dim, int64_t n, int64_t in_lo, int64_t in_hi, int64_t out_lo,
@@ -575,10 +598,7 @@ at::Tensor c2c_axis_cuda(const at::Tensor& x_, int64_t dim, int64_t n, int64_t i
   const c10::DeviceGuard guard(x_.device());
   at::Tensor x = pair_aligned(x_.contiguous());
   to_dtype(x.scalar_type());
-  const int64_t nd = x.dim() - 1;
-  dim = dim < 0 ? dim + nd : dim;
-  TORCH_CHECK(dim >= 0 && dim < nd, "amd_dft.c2c_axis: dim out of range");
-  check_c2c_axis(x, dim, n, in_lo, in_hi, out_lo, out_hi);
+  dim = check_c2c_axis(x, dim, n, in_lo, in_hi, out_lo, out_hi);
   std::vector<int64_t> cur(x.sizes().begin(), x.sizes().end() - 1);
   std::vector<int64_t> nxt = cur;
   nxt[dim] = out_lo + out_hi;
@@ -591,9 +611,7 @@ at::Tensor c2c_axis_cuda(const at::Tensor& x_, int64_t dim, int64_t n, int64_t i
 
 at::Tensor c2c_axis_cpu(const at::Tensor& x, int64_t dim, int64_t n, int64_t in_lo, int64_t in_hi, int64_t out_lo,
                         int64_t out_hi, bool inverse, double scale) {
-  const int64_t nd = x.dim() - 1;
-  dim = dim < 0 ? dim + nd : dim;
-  check_c2c_axis(x, dim, n, in_lo, in_hi, out_lo, out_hi);
+  dim = check_c2c_axis(x, dim, n, in_lo, in_hi, out_lo, out_hi);
   at::Tensor xc = at::view_as_complex(x.to(at::kDouble).contiguous());
   std::vector<int64_t> full_shape(xc.sizes().begin(), xc.sizes().end());
   full_shape[dim] = n;
@@ -686,418 +704,8 @@ at::Tensor fno_mix_c2c_meta(const at::Tensor& xm, const at::Tensor& w, int64_t n
 at::Tensor c2c_axis_meta(const at::Tensor& x, int64_t dim, int64_t n, int64_t in_lo, int64_t in_hi, int64_t out_lo,
                          int64_t out_hi, bool, double) {
   std::vector<int64_t> s(x.sizes().begin(), x.sizes().end());
-  const int64_t nd = x.dim() - 1;
-  s[dim < 0 ? dim + nd : dim] = out_lo + out_hi;
+  s[c2c_axis_dim(x, dim)] = out_lo + out_hi;
   return at::empty(s, x.options().dtype(at::kFloat));
-}
-
-// ------------------------------------------------------------------ LayerNorm-fused AFNO W passes
-// x' = x + pre (per channel), LN(x') = (x' - mean) * rstd * gamma + beta with per-token stats
-// from ln_stats.  Channel-last [..., W, C]: the transform axis is dim -2, channels last.
-at::Tensor ln_apply(const at::Tensor& x, const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
-                    const std::optional<at::Tensor>& pre, at::Tensor* xp_out) {
-  at::Tensor xp = x.to(at::kFloat);
-  if (pre.has_value()) xp = xp + pre->to(at::kFloat);
-  std::vector<int64_t> ss(x.sizes().begin(), x.sizes().end());
-  ss.back() = 1;
-  at::Tensor st = stats.to(at::kFloat).reshape({-1, 2});
-  at::Tensor mean = st.select(1, 0).reshape(ss), rstd = st.select(1, 1).reshape(ss);
-  if (xp_out) *xp_out = xp;
-  return (xp - mean) * rstd * g.to(at::kFloat) + b.to(at::kFloat);
-}
-
-void check_ln_args(const at::Tensor& x, int64_t dim, const at::Tensor& stats, const at::Tensor& g,
-                   const at::Tensor& b, const std::optional<at::Tensor>& pre, const char* op) {
-  TORCH_CHECK(x.dim() >= 2, "amd_dft.", op, ": needs a [..., W, C] channel-last tensor");
-  TORCH_CHECK(dim == x.dim() - 2 || dim == -2, "amd_dft.", op, ": the transform axis must be dim -2 (channel-last)");
-  const int64_t C = x.size(-1);
-  TORCH_CHECK(g.numel() == C && b.numel() == C && (!pre.has_value() || pre->numel() == C), "amd_dft.", op,
-              ": gamma/beta/pre must have one entry per channel");
-  TORCH_CHECK(stats.numel() == 2 * (x.numel() / std::max<int64_t>(C, 1)), "amd_dft.", op,
-              ": stats must hold (mean, rstd) per token");
-}
-
-// MI_DFT_NO_AFNO_W=1 (A/B, read once): LayerNorm-fused AFNO W-transforms on the generic fixed
-// Stockham kernels instead of afno_wfft.hip (same results)
-bool afno_w_enabled() {
-  static const bool on = tuning_env("MI_DFT_NO_AFNO_W") == nullptr;
-  return on;
-}
-
-// Whether a call of the four LayerNorm-fused ops whose dtypes an instance of afno_wfft.hip covers runs there
-// (the ops and afno_w_info both ask here): the specialised shape, and O = the number of [L, C] planes
-bool afno_w_takes(int64_t L, int64_t C, int64_t KM, int64_t O) {
-  return afno_w_enabled() && L < (int64_t(1) << 31) && C < (int64_t(1) << 31) && KM < (int64_t(1) << 31) &&
-         afno_w_supported(static_cast<int>(L), static_cast<int>(C), static_cast<int>(KM)) && O < (int64_t(1) << 31);
-}
-
-at::Tensor r2c_cpu(const at::Tensor& x, at::IntArrayRef dim, double scale, at::IntArrayRef keep,
-                   std::optional<at::ScalarType> out_dtype);
-at::Tensor c2r_cpu(const at::Tensor& x, at::IntArrayRef dim, at::IntArrayRef out_size, double scale,
-                   at::IntArrayRef keep, std::optional<at::ScalarType> out_dtype);
-
-at::Tensor r2c_ln_cuda(const at::Tensor& x_, int64_t dim, double scale, int64_t keep, const at::Tensor& stats_,
-                       const at::Tensor& g_, const at::Tensor& b_, const std::optional<at::Tensor>& pre_,
-                       std::optional<at::ScalarType> out_dtype) {
-  const c10::DeviceGuard guard(x_.device());
-  check_ln_args(x_, dim, stats_, g_, b_, pre_, "r2c_ln");
-  const int64_t axis = x_.dim() - 2;
-  at::Tensor x = vec_aligned(x_.contiguous());
-  const at::ScalarType odt = out_dtype.value_or(x.scalar_type());
-  to_dtype(x.scalar_type());
-  to_dtype(odt);
-  const std::vector<int64_t> dv{axis}, kv{keep, 0};
-  R2CShape sh = r2c_shape(x.sizes(), dv, kv);
-  const DimSpec& s = sh.specs[0];
-  std::vector<int64_t> cur(x.sizes().begin(), x.sizes().end()), nxt = cur;
-  nxt[axis] = s.lo;
-  at::Tensor out = alloc_complex(nxt, x.options(), odt);
-  if (x.numel() == 0) return out.zero_();
-  at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
-             b = vec_aligned(b_.to(at::kFloat).contiguous());
-  at::Tensor pre;
-  if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
-  LnIO ln{stats.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(),
-          pre_.has_value() ? pre.data_ptr<float>() : nullptr};
-  const int64_t C = x.size(-1);
-  const bool w_f32 = x.scalar_type() == at::kFloat && odt == at::kFloat;
-  if (((x.scalar_type() == at::kBFloat16 && odt == at::kBFloat16) || w_f32) && afno_w_takes(s.n, C, s.lo, x.numel() / (s.n * C))) {
-    AfnoWLaunch p;  // 16-byte-lane two-pass kernel (afno_wfft.hip)
-    p.x = x.data_ptr();
-    p.stats = ln.stats;
-    p.gamma = ln.gamma;
-    p.beta = ln.beta;
-    p.pre = ln.pre;
-    p.out = out.data_ptr();
-    p.O = static_cast<int>(x.numel() / (s.n * C));
-    p.L = static_cast<int>(s.n);
-    p.C = static_cast<int>(C);
-    p.KM = static_cast<int>(s.lo);
-    p.scale = static_cast<float>(scale);
-    p.f32 = w_f32 ? 1 : 0;
-    launch_afno_w_r2c_ln(p, current_stream(x));
-    return checked(out, "r2c_ln");
-  }
-  if (x.scalar_type() == at::kBFloat16 && odt == at::kBFloat16 &&
-      run_pass(Kind::R2C, x, out, cur, nxt, static_cast<int>(axis), s.n, static_cast<int>(s.n), 0,
-               static_cast<int>(s.lo), 0, static_cast<float>(scale), false, nullptr, nullptr, &ln))
-    return checked(out, "r2c_ln");
-  // no specialised kernel for this shape: normalise with ATen, then the plain R2C
-  fallback_note("r2c_ln", "no LayerNorm-fused W-transform for this shape/dtype: ATen LayerNorm + the plain R2C");
-  at::Tensor h = ln_apply(x, stats, g, b, pre_, nullptr).to(x.scalar_type());
-  return r2c_cuda(h, dv, scale, kv, odt);
-}
-
-at::Tensor r2c_ln_cpu(const at::Tensor& x, int64_t dim, double scale, int64_t keep, const at::Tensor& stats,
-                      const at::Tensor& g, const at::Tensor& b, const std::optional<at::Tensor>& pre,
-                      std::optional<at::ScalarType> out_dtype) {
-  check_ln_args(x, dim, stats, g, b, pre, "r2c_ln");
-  at::Tensor h = ln_apply(x, stats, g, b, pre, nullptr).to(x.scalar_type());
-  const std::vector<int64_t> dv{x.dim() - 2}, kv{keep, 0};
-  return r2c_cpu(h, dv, scale, kv, out_dtype);
-}
-
-at::Tensor r2c_ln_meta(const at::Tensor& x, int64_t dim, double scale, int64_t keep, const at::Tensor&,
-                       const at::Tensor&, const at::Tensor&, const std::optional<at::Tensor>&,
-                       std::optional<at::ScalarType> out_dtype) {
-  std::vector<int64_t> s(x.sizes().begin(), x.sizes().end());
-  s[x.dim() - 2] = keep;
-  s.push_back(2);
-  return at::empty(s, x.options().dtype(out_dtype.value_or(x.scalar_type())));
-}
-
-// out = scale * irfft_W(X) + x' + LN(x'),  X = [..., km, C, 2], x = stored residual stream [..., W, C]
-at::Tensor c2r_ln_add_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double scale, const at::Tensor& x_,
-                           const at::Tensor& stats_, const at::Tensor& g_, const at::Tensor& b_,
-                           const std::optional<at::Tensor>& pre_) {
-  const c10::DeviceGuard guard(X_.device());
-  check_ln_args(x_, dim, stats_, g_, b_, pre_, "c2r_ln_add");
-  const int64_t axis = x_.dim() - 2;
-  TORCH_CHECK(X_.dim() == x_.dim() + 1 && X_.size(-1) == 2 && x_.size(axis) == n, "amd_dft.c2r_ln_add: shape mismatch "
-              "(X must be [..., km, C, 2] with the leading dims and C of x)");
-  at::Tensor X = vec_aligned(X_.contiguous()), x = vec_aligned(x_.contiguous());
-  const int64_t km = X.size(axis);
-  const std::vector<int64_t> dv{axis}, nv{n}, kv{km, 0};
-  at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
-             b = vec_aligned(b_.to(at::kFloat).contiguous());
-  at::Tensor pre;
-  if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
-  TORCH_CHECK(X.sizes().slice(0, axis) == x.sizes().slice(0, axis) && X.size(axis + 1) == x.size(-1) &&
-                  X.size(axis) <= n / 2 + 1,
-              "amd_dft.c2r_ln_add: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
-  const bool w_f32 = X.scalar_type() == at::kFloat && x.scalar_type() == at::kFloat;
-  if (w_f32 && X.numel() > 0) {
-    const int64_t C = x.size(-1);
-    if (afno_w_takes(n, C, km, x.numel() / (n * C))) {
-      at::Tensor out = at::empty_like(x);
-      AfnoWLaunch p;  // fp32 instantiation of the two-pass kernel (afno_wfft.hip)
-      p.x = x.data_ptr();
-      p.stats = stats.data_ptr<float>();
-      p.gamma = g.data_ptr<float>();
-      p.beta = b.data_ptr<float>();
-      p.pre = pre_.has_value() ? pre.data_ptr<float>() : nullptr;
-      p.spec = X.data_ptr();
-      p.out = out.data_ptr();
-      p.O = static_cast<int>(x.numel() / (n * C));
-      p.L = static_cast<int>(n);
-      p.C = static_cast<int>(C);
-      p.KM = static_cast<int>(km);
-      p.scale = static_cast<float>(scale);
-      p.f32 = 1;
-      launch_afno_w_c2r_ln(p, current_stream(x));
-      return checked(out, "c2r_ln_add");
-    }
-  }
-  if (X.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16 && X.numel() > 0) {
-    C2RShape sh = c2r_shape(X.sizes(), dv, nv, kv);
-    const DimSpec& s = sh.specs[0];
-    std::vector<int64_t> cur = sh.in_logical, nxt = cur;
-    nxt[axis] = s.n;
-    at::Tensor out = at::empty(nxt, x.options());
-    const int64_t half = s.n / 2 + 1;
-    const int in_lo = static_cast<int>(std::min<int64_t>(s.lo, half));
-    LnIO ln{stats.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(),
-            pre_.has_value() ? pre.data_ptr<float>() : nullptr};
-    const int64_t C = x.size(-1);
-    if (afno_w_takes(s.n, C, km, x.numel() / (s.n * C))) {
-      AfnoWLaunch p;  // 16-byte-lane two-pass kernel (afno_wfft.hip)
-      p.x = x.data_ptr();
-      p.stats = ln.stats;
-      p.gamma = ln.gamma;
-      p.beta = ln.beta;
-      p.pre = ln.pre;
-      p.spec = X.data_ptr();
-      p.out = out.data_ptr();
-      p.O = static_cast<int>(x.numel() / (s.n * C));
-      p.L = static_cast<int>(s.n);
-      p.C = static_cast<int>(C);
-      p.KM = static_cast<int>(km);
-      p.scale = static_cast<float>(scale);
-      launch_afno_w_c2r_ln(p, current_stream(x));
-      return checked(out, "c2r_ln_add");
-    }
-    if (run_pass(Kind::C2R, X, out, cur, nxt, static_cast<int>(axis), s.n, in_lo, 0, static_cast<int>(s.n), 0,
-                 static_cast<float>(scale), true, x.data_ptr(), nullptr, &ln))
-      return checked(out, "c2r_ln_add");
-  }
-  fallback_note("c2r_ln_add", "no LayerNorm-fused W-transform for this shape/dtype: ATen LayerNorm + the plain C2R");
-  at::Tensor xp;
-  at::Tensor h = ln_apply(x, stats, g, b, pre_, &xp);
-  return c2r_add_cuda(X, dv, nv, scale, kv, xp.to(x.scalar_type()).contiguous(), h.to(x.scalar_type()).contiguous(),
-                      x.scalar_type());
-}
-
-at::Tensor c2r_ln_add_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale, const at::Tensor& x,
-                          const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
-                          const std::optional<at::Tensor>& pre) {
-  check_ln_args(x, dim, stats, g, b, pre, "c2r_ln_add");
-  const int64_t axis = x.dim() - 2;
-  TORCH_CHECK(X.dim() == x.dim() + 1 && X.size(-1) == 2 && x.size(axis) == n && X.sizes().slice(0, axis) == x.sizes().slice(0, axis) &&
-                  X.size(axis + 1) == x.size(-1) && X.size(axis) <= n / 2 + 1,
-              "amd_dft.c2r_ln_add: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
-  at::Tensor xp;
-  at::Tensor h = ln_apply(x, stats, g, b, pre, &xp);
-  const std::vector<int64_t> dv{axis}, nv{n}, kv{X.size(axis), 0};
-  at::Tensor y = c2r_cpu(X, dv, nv, scale, kv, at::kFloat);
-  return (y + xp + h).to(x.scalar_type()).contiguous();
-}
-
-at::Tensor c2r_ln_add_meta(const at::Tensor&, int64_t, int64_t, double, const at::Tensor& x, const at::Tensor&,
-                           const at::Tensor&, const at::Tensor&, const std::optional<at::Tensor>&) {
-  return at::empty_like(x);
-}
-
-// c2r_ln_add + the residual stream's bf16x3 split-pair rows and per-64-channel LayerNorm partials
-// (mean, M2), all from the one C2R epilogue (afno_wfft.hip SPLIT instantiation): the fp32 block's
-// fc1 then reads the pairs with LN2 folded in (linear3_ln) -- no LayerNorm / split pass.
-// The pairs hold out - mean(x) per token (stats[:, 0], the input's LayerNorm mean): centred, the
-// split keeps 2^-17 of the deviation rather than of |out|, and ln_stats_merge(part, eps, stats)
-// gives fc1 the matching centred mean.
-// Returns (out [..., W, C] fp32, pairs [tokens, 2C] bf16, part [tokens, C/64, 2] fp32).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> split_and_partials(const at::Tensor& y, const at::Tensor& stats) {
-  const int64_t C = y.size(-1);
-  at::Tensor rows = y.reshape({-1, C}).to(at::kFloat);
-  const int64_t M = rows.size(0);
-  at::Tensor z = rows - stats.reshape({-1, 2}).select(1, 0).to(at::kFloat).unsqueeze(1);
-  at::Tensor hi = z.to(at::kBFloat16);
-  at::Tensor lo = (z - hi.to(at::kFloat)).to(at::kBFloat16);
-  at::Tensor pairs = at::cat({hi.reshape({M, C / 32, 32}), lo.reshape({M, C / 32, 32})}, -1).reshape({M, 2 * C}).contiguous();
-  at::Tensor w = rows.reshape({M, C / 64, 64});
-  at::Tensor mean = w.mean(2);
-  at::Tensor m2 = (w - mean.unsqueeze(2)).pow(2).sum(2);
-  return {y, pairs, at::stack({mean, m2}, 2).contiguous()};
-}
-
-at::Tensor c2r_ln_add_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale, const at::Tensor& x,
-                          const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
-                          const std::optional<at::Tensor>& pre);
-
-void check_split_out(const at::Tensor& X, const at::Tensor& x, const char* op) {
-  TORCH_CHECK(X.scalar_type() == at::kFloat && x.scalar_type() == at::kFloat, "amd_dft.", op,
-              ": split-pair outputs come with the fp32 residual stream");
-  TORCH_CHECK(x.size(-1) % 64 == 0, "amd_dft.", op, ": C must be a multiple of 64");
-}
-
-// (out, pairs, part) of the ATen paths -> out_mode's first result: out (1), its lo2 term
-// bf16(out - m - (hi + lo)) (2, m = stats[:, 0], the pairs' centring) or nothing (0)
-std::tuple<at::Tensor, at::Tensor, at::Tensor> out_mode_result(std::tuple<at::Tensor, at::Tensor, at::Tensor> r,
-                                                                const at::Tensor& stats, int64_t out_mode) {
-  TORCH_CHECK(out_mode >= 0 && out_mode <= 2, "amd_dft.c2r_ln_add_split: out_mode must be 0, 1 or 2");
-  if (out_mode == 1) return r;
-  at::Tensor& out = std::get<0>(r);
-  if (out_mode == 0) {
-    out = at::empty({0}, out.options());
-    return r;
-  }
-  const int64_t C = out.size(-1);
-  at::Tensor z = out.reshape({-1, C}).to(at::kFloat) - stats.to(at::kFloat).reshape({-1, 2}).select(1, 0).unsqueeze(1);
-  at::Tensor pr = std::get<1>(r).to(at::kFloat).reshape({-1, C / 32, 2, 32});
-  out = (z - (pr.select(2, 0) + pr.select(2, 1)).reshape({-1, C})).to(at::kBFloat16);
-  return r;
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double scale,
-                                                                     const at::Tensor& x_, const at::Tensor& stats_,
-                                                                     const at::Tensor& g_, const at::Tensor& b_,
-                                                                     const std::optional<at::Tensor>& pre_, int64_t out_mode) {
-  const c10::DeviceGuard guard(X_.device());
-  check_ln_args(x_, dim, stats_, g_, b_, pre_, "c2r_ln_add_split");
-  check_split_out(X_, x_, "c2r_ln_add_split");
-  const int64_t axis = x_.dim() - 2;
-  TORCH_CHECK(X_.dim() == x_.dim() + 1 && X_.size(-1) == 2 && x_.size(axis) == n &&
-                  X_.sizes().slice(0, axis) == x_.sizes().slice(0, axis) && X_.size(axis + 1) == x_.size(-1) &&
-                  X_.size(axis) <= n / 2 + 1,
-              "amd_dft.c2r_ln_add_split: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
-  at::Tensor X = vec_aligned(X_.contiguous()), x = vec_aligned(x_.contiguous());
-  const int64_t km = X.size(axis), C = x.size(-1);
-  if (X.numel() > 0 && afno_w_takes(n, C, km, x.numel() / (n * C))) {
-    at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
-               b = vec_aligned(b_.to(at::kFloat).contiguous());
-    at::Tensor pre;
-    if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
-    const int64_t M = x.numel() / C;
-    // out_mode 1: the fp32 output; 2: instead its bf16 third split term (lo2, [M, C]); 0: neither
-    TORCH_CHECK(out_mode >= 0 && out_mode <= 2, "amd_dft.c2r_ln_add_split: out_mode must be 0, 1 or 2");
-    at::Tensor out = out_mode == 1 ? at::empty_like(x)
-                                   : out_mode == 2 ? at::empty({M, C}, x.options().dtype(at::kBFloat16)) : at::empty({0}, x.options());
-    at::Tensor pairs = at::empty({M, 2 * C}, x.options().dtype(at::kBFloat16));
-    at::Tensor part = at::empty({M, C / 64, 2}, x.options());
-    AfnoWLaunch p;  // fp32 two-pass kernel with the split / statistics epilogue (afno_wfft.hip)
-    p.x = x.data_ptr();
-    p.stats = stats.data_ptr<float>();
-    p.gamma = g.data_ptr<float>();
-    p.beta = b.data_ptr<float>();
-    p.pre = pre_.has_value() ? pre.data_ptr<float>() : nullptr;
-    p.spec = X.data_ptr();
-    p.out = out_mode == 1 ? out.data_ptr() : nullptr;
-    p.lo2 = out_mode == 2 ? reinterpret_cast<uint16_t*>(out.data_ptr()) : nullptr;
-    p.pairs = reinterpret_cast<uint16_t*>(pairs.data_ptr());
-    p.part = part.data_ptr<float>();
-    p.O = static_cast<int>(M / n);
-    p.L = static_cast<int>(n);
-    p.C = static_cast<int>(C);
-    p.KM = static_cast<int>(km);
-    p.scale = static_cast<float>(scale);
-    p.f32 = 1;
-    launch_afno_w_c2r_ln(p, current_stream(x));
-    return {checked(out, "c2r_ln_add_split"), pairs, part};
-  }
-  fallback_note("c2r_ln_add_split", "no fused W-transform for this shape: c2r_ln_add + ATen split / statistics");
-  auto r = split_and_partials(c2r_ln_add_cuda(X, dim, n, scale, x, stats_, g_, b_, pre_), stats_);
-  return out_mode_result(r, stats_, out_mode);
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale,
-                                                                    const at::Tensor& x, const at::Tensor& stats,
-                                                                    const at::Tensor& g, const at::Tensor& b,
-                                                                    const std::optional<at::Tensor>& pre, int64_t out_mode) {
-  check_split_out(X, x, "c2r_ln_add_split");
-  auto r = split_and_partials(c2r_ln_add_cpu(X, dim, n, scale, x, stats, g, b, pre), stats);
-  return out_mode_result(r, stats, out_mode);
-}
-
-// bf16 block: c2r_ln_add + the next LayerNorm's per-64-channel partials (mean, M2) of the STORED
-// (bf16-rounded) output, from the one C2R epilogue (afno_wfft.hip PART instantiation); ln_stats_merge
-// turns them into LN2's (mean, rstd) without an ln_stats pass over the residual stream.
-// Returns (out [..., W, C] bf16, part [tokens, C/64, 2] fp32).
-std::tuple<at::Tensor, at::Tensor> out_and_partials(const at::Tensor& y) {
-  const int64_t C = y.size(-1);
-  at::Tensor w = y.reshape({-1, C / 64, 64}).to(at::kFloat);
-  at::Tensor mean = w.mean(2);
-  at::Tensor m2 = (w - mean.unsqueeze(2)).pow(2).sum(2);
-  return {y, at::stack({mean, m2}, 2).contiguous()};
-}
-
-void check_part_out(const at::Tensor& X, const at::Tensor& x, const char* op) {
-  TORCH_CHECK(X.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16, "amd_dft.", op,
-              ": bf16 spectrum and residual stream (the fp32 block uses c2r_ln_add_split)");
-  TORCH_CHECK(x.size(-1) % 64 == 0, "amd_dft.", op, ": C must be a multiple of 64");
-}
-
-std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_cuda(const at::Tensor& X_, int64_t dim, int64_t n, double scale,
-                                                        const at::Tensor& x_, const at::Tensor& stats_, const at::Tensor& g_,
-                                                        const at::Tensor& b_, const std::optional<at::Tensor>& pre_) {
-  const c10::DeviceGuard guard(X_.device());
-  check_ln_args(x_, dim, stats_, g_, b_, pre_, "c2r_ln_add_part");
-  check_part_out(X_, x_, "c2r_ln_add_part");
-  const int64_t axis = x_.dim() - 2;
-  TORCH_CHECK(X_.dim() == x_.dim() + 1 && X_.size(-1) == 2 && x_.size(axis) == n &&
-                  X_.sizes().slice(0, axis) == x_.sizes().slice(0, axis) && X_.size(axis + 1) == x_.size(-1) &&
-                  X_.size(axis) <= n / 2 + 1,
-              "amd_dft.c2r_ln_add_part: X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
-  at::Tensor X = vec_aligned(X_.contiguous()), x = vec_aligned(x_.contiguous());
-  const int64_t km = X.size(axis), C = x.size(-1);
-  if (X.numel() > 0 && afno_w_takes(n, C, km, x.numel() / (n * C))) {
-    at::Tensor stats = vec_aligned(stats_.to(at::kFloat).contiguous()), g = vec_aligned(g_.to(at::kFloat).contiguous()),
-               b = vec_aligned(b_.to(at::kFloat).contiguous());
-    at::Tensor pre;
-    if (pre_.has_value()) pre = vec_aligned(pre_->to(at::kFloat).contiguous());
-    const int64_t M = x.numel() / C;
-    at::Tensor out = at::empty_like(x);
-    at::Tensor part = at::empty({M, C / 64, 2}, x.options().dtype(at::kFloat));
-    AfnoWLaunch p;  // bf16 two-pass kernel with the partial-statistics epilogue (afno_wfft.hip PART)
-    p.x = x.data_ptr();
-    p.stats = stats.data_ptr<float>();
-    p.gamma = g.data_ptr<float>();
-    p.beta = b.data_ptr<float>();
-    p.pre = pre_.has_value() ? pre.data_ptr<float>() : nullptr;
-    p.spec = X.data_ptr();
-    p.out = out.data_ptr();
-    p.part = part.data_ptr<float>();
-    p.O = static_cast<int>(M / n);
-    p.L = static_cast<int>(n);
-    p.C = static_cast<int>(C);
-    p.KM = static_cast<int>(km);
-    p.scale = static_cast<float>(scale);
-    launch_afno_w_c2r_ln(p, current_stream(x));
-    return {checked(out, "c2r_ln_add_part"), part};
-  }
-  fallback_note("c2r_ln_add_part", "no fused W-transform for this shape: c2r_ln_add + ATen statistics");
-  return out_and_partials(c2r_ln_add_cuda(X, dim, n, scale, x, stats_, g_, b_, pre_));
-}
-
-std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale,
-                                                       const at::Tensor& x, const at::Tensor& stats, const at::Tensor& g,
-                                                       const at::Tensor& b, const std::optional<at::Tensor>& pre) {
-  check_part_out(X, x, "c2r_ln_add_part");
-  return out_and_partials(c2r_ln_add_cpu(X, dim, n, scale, x, stats, g, b, pre));
-}
-
-std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_meta(const at::Tensor&, int64_t, int64_t, double, const at::Tensor& x,
-                                                        const at::Tensor&, const at::Tensor&, const at::Tensor&,
-                                                        const std::optional<at::Tensor>&) {
-  const int64_t C = x.size(-1), M = x.numel() / std::max<int64_t>(C, 1);
-  return {at::empty_like(x), at::empty({M, C / 64, 2}, x.options().dtype(at::kFloat))};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_meta(const at::Tensor&, int64_t, int64_t, double,
-                                                                     const at::Tensor& x, const at::Tensor&, const at::Tensor&,
-                                                                     const at::Tensor&, const std::optional<at::Tensor>&,
-                                                                     int64_t out_mode) {
-  const int64_t C = x.size(-1), M = x.numel() / std::max<int64_t>(C, 1);
-  return {out_mode == 1 ? at::empty_like(x)
-                        : out_mode == 2 ? at::empty({M, C}, x.options().dtype(at::kBFloat16)) : at::empty({0}, x.options()),
-          at::empty({M, 2 * C}, x.options().dtype(at::kBFloat16)), at::empty({M, C / 64, 2}, x.options())};
 }
 
 // ------------------------------------------------------------------ CPU impls (torch.fft)
@@ -1195,6 +803,423 @@ at::Tensor c2c_meta(const at::Tensor& x, at::IntArrayRef, bool, double, std::opt
   return at::empty_like(x, x.options().dtype(out_dtype.value_or(x.scalar_type())));
 }
 
+// ------------------------------------------------------------------ LayerNorm-fused AFNO W passes
+// x' = x + pre (per channel), LN(x') = (x' - mean) * rstd * gamma + beta with per-token stats
+// from ln_stats.  Channel-last [..., W, C]: the transform axis is dim -2, channels last.  Four ops:
+//   r2c_ln            scale * rfft_W(LN(x'))[..., :keep, :, :]
+//   c2r_ln_add        out = scale * irfft_W(X) + x' + LN(x'),  X = [..., km, C, 2], x = stored residual stream [..., W, C]
+//   c2r_ln_add_split  fp32: (out, its bf16x3 split-pair rows, its per-64-channel LayerNorm partials)
+//   c2r_ln_add_part   bf16: (out, its per-64-channel LayerNorm partials)
+// They share their checks (check_wln), their canonical arguments (WlnArgs), their route (wln_route, which
+// afno_w_info reports) and the one launch of the kernels of afno_wfft.hip (launch_wln).
+enum class WlnOp { R2cLn, C2rLnAdd, C2rLnAddSplit, C2rLnAddPart };
+constexpr const char* kWlnNames[] = {"r2c_ln", "c2r_ln_add", "c2r_ln_add_split", "c2r_ln_add_part"};  // by WlnOp
+const char* wln_name(WlnOp op) { return kWlnNames[static_cast<int>(op)]; }
+
+// pre: undefined for none
+at::Tensor ln_apply(const at::Tensor& x, const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
+                    const at::Tensor& pre, at::Tensor* xp_out) {
+  at::Tensor xp = x.to(at::kFloat);
+  if (pre.defined()) xp = xp + pre.to(at::kFloat);
+  std::vector<int64_t> ss(x.sizes().begin(), x.sizes().end());
+  ss.back() = 1;
+  at::Tensor st = stats.to(at::kFloat).reshape({-1, 2});
+  at::Tensor mean = st.select(1, 0).reshape(ss), rstd = st.select(1, 1).reshape(ss);
+  if (xp_out) *xp_out = xp;
+  return (xp - mean) * rstd * g.to(at::kFloat) + b.to(at::kFloat);
+}
+
+// ---- checks, the same on every backend and before any work
+void check_ln_args(const at::Tensor& x, int64_t dim, const at::Tensor& stats, const at::Tensor& g,
+                   const at::Tensor& b, const std::optional<at::Tensor>& pre, const char* op) {
+  TORCH_CHECK(x.dim() >= 2, "amd_dft.", op, ": needs a [..., W, C] channel-last tensor");
+  TORCH_CHECK(dim == x.dim() - 2 || dim == -2, "amd_dft.", op, ": the transform axis must be dim -2 (channel-last)");
+  const int64_t C = x.size(-1);
+  TORCH_CHECK(g.numel() == C && b.numel() == C && (!pre.has_value() || pre->numel() == C), "amd_dft.", op,
+              ": gamma/beta/pre must have one entry per channel");
+  TORCH_CHECK(stats.numel() == 2 * (x.numel() / std::max<int64_t>(C, 1)), "amd_dft.", op,
+              ": stats must hold (mean, rstd) per token");
+}
+
+void check_c2r_ln_spec(const at::Tensor& X, const at::Tensor& x, int64_t n, const char* op) {
+  const int64_t axis = x.dim() - 2;
+  TORCH_CHECK(X.dim() == x.dim() + 1 && X.size(-1) == 2 && x.size(axis) == n &&
+                  X.sizes().slice(0, axis) == x.sizes().slice(0, axis) && X.size(axis + 1) == x.size(-1) &&
+                  X.size(axis) <= n / 2 + 1,
+              "amd_dft.", op, ": X must be [..., km, C, 2] with the leading dims and C of x and km <= n/2+1");
+}
+
+// Why an op takes no call of these dtypes / this channel count, on any backend (nullptr: it does).  `in` is the dtype
+// of the transform's input (x for r2c_ln, X for the C2R ops), `out` of its output (the C2R ops': the residual stream's).
+const char* wln_refusal(WlnOp op, int64_t C, at::ScalarType in, at::ScalarType out) {
+  const bool split = op == WlnOp::C2rLnAddSplit, part = op == WlnOp::C2rLnAddPart;
+  if (split && !(in == at::kFloat && out == at::kFloat)) return "split-pair outputs come with the fp32 residual stream";
+  if (part && !(in == at::kBFloat16 && out == at::kBFloat16))
+    return "bf16 spectrum and residual stream (the fp32 block uses c2r_ln_add_split)";
+  if ((split || part) && C % 64 != 0) return "C must be a multiple of 64";
+  return nullptr;
+}
+
+// X is not looked at for r2c_ln, nor n; out_mode only for c2r_ln_add_split
+void check_wln(WlnOp op, const at::Tensor& X, const at::Tensor& x, int64_t dim, int64_t n, const at::Tensor& stats,
+               const at::Tensor& g, const at::Tensor& b, const std::optional<at::Tensor>& pre, int64_t out_mode = 1) {
+  const char* name = wln_name(op);
+  check_ln_args(x, dim, stats, g, b, pre, name);
+  if (op == WlnOp::R2cLn) return;
+  const char* why = wln_refusal(op, x.size(-1), X.scalar_type(), x.scalar_type());
+  TORCH_CHECK(!why, "amd_dft.", name, ": ", why);
+  TORCH_CHECK(op != WlnOp::C2rLnAddSplit || (out_mode >= 0 && out_mode <= 2), "amd_dft.", name,
+              ": out_mode must be 0, 1 or 2");
+  check_c2r_ln_spec(X, x, n, name);
+}
+
+// ---- results, written once: the device forms allocate with these, the meta forms return them
+int64_t r2c_ln_kept(const at::Tensor& x, int64_t keep) {  // keep < 0: the whole half spectrum
+  const std::vector<int64_t> dv{x.dim() - 2}, kv{keep, 0};
+  return r2c_shape(x.sizes(), dv, kv).specs[0].lo;
+}
+
+at::Tensor r2c_ln_empty(const at::Tensor& x, int64_t km, std::optional<at::ScalarType> out_dtype) {
+  std::vector<int64_t> s(x.sizes().begin(), x.sizes().end());
+  s[x.dim() - 2] = km;
+  return alloc_complex(s, x.options(), out_dtype.value_or(x.scalar_type()));
+}
+
+at::Tensor c2r_ln_add_empty(const at::Tensor& x) { return at::empty(x.sizes(), x.options()); }
+
+at::Tensor ln_partials_empty(const at::Tensor& x) {  // [tokens, C/64, 2] fp32
+  const int64_t C = x.size(-1);
+  return at::empty({x.numel() / std::max<int64_t>(C, 1), C / 64, 2}, x.options().dtype(at::kFloat));
+}
+
+// (out [..., W, C] bf16, part)
+std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_empty(const at::Tensor& x) {
+  return {c2r_ln_add_empty(x), ln_partials_empty(x)};
+}
+
+// (first, pairs [tokens, 2C] bf16, part); first by out_mode: 1 the fp32 output [..., W, C]; 2 instead its bf16
+// third split term (lo2, [tokens, C]); 0 neither
+std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_empty(const at::Tensor& x, int64_t out_mode) {
+  const int64_t C = x.size(-1), M = x.numel() / std::max<int64_t>(C, 1);
+  const auto bf = x.options().dtype(at::kBFloat16);
+  return {out_mode == 1 ? c2r_ln_add_empty(x) : out_mode == 2 ? at::empty({M, C}, bf) : at::empty({0}, x.options()),
+          at::empty({M, 2 * C}, bf), ln_partials_empty(x)};
+}
+
+// ---- canonical arguments of a device call
+struct WlnArgs {
+  at::Tensor x, X;                     // contiguous, 16-byte aligned; X undefined for r2c_ln
+  at::Tensor stats, gamma, beta, pre;  // fp32, contiguous, 16-byte aligned; pre undefined when there is none
+  int64_t axis = 0, n = 0, C = 0;      // the transform axis (dim -2) and length, channels
+  int64_t km = 0;                      // modes kept (r2c_ln) or stored in X
+  int64_t M = 0, O = 0;                // tokens; [n, C] planes
+  const float* pre_ptr() const { return pre.defined() ? pre.data_ptr<float>() : nullptr; }
+  LnIO ln() const { return {stats.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), pre_ptr()}; }
+};
+
+// n: the C2R ops' output length; keep: r2c_ln's kept modes (each ignored by the other kind)
+WlnArgs wln_args(WlnOp op, const at::Tensor& X, const at::Tensor& x, int64_t dim, int64_t n, int64_t keep,
+                 const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
+                 const std::optional<at::Tensor>& pre, int64_t out_mode = 1) {
+  check_wln(op, X, x, dim, n, stats, g, b, pre, out_mode);
+  WlnArgs a;
+  a.x = vec_aligned(x.contiguous());
+  if (op != WlnOp::R2cLn) a.X = vec_aligned(X.contiguous());
+  a.stats = vec_aligned(stats.to(at::kFloat).contiguous());
+  a.gamma = vec_aligned(g.to(at::kFloat).contiguous());
+  a.beta = vec_aligned(b.to(at::kFloat).contiguous());
+  a.pre = vec_aligned(f32_or_undef(pre));
+  a.axis = a.x.dim() - 2;
+  a.n = a.x.size(a.axis);
+  a.C = a.x.size(-1);
+  a.km = op == WlnOp::R2cLn ? r2c_ln_kept(a.x, keep) : a.X.size(a.axis);
+  a.M = a.x.numel() / std::max<int64_t>(a.C, 1);
+  a.O = a.M / std::max<int64_t>(a.n, 1);
+  return a;
+}
+
+// The one launch of the two-pass kernels of afno_wfft.hip, and the only code that fills an AfnoWLaunch: the R2C when
+// the pack has no spectrum, else the C2R, whose instance follows from the dtype and the extra outputs (pairs and
+// part: SPLIT, with out or lo2 or neither; part alone: PART).
+void launch_wln(const WlnArgs& a, double scale, void* out, uint16_t* lo2 = nullptr, uint16_t* pairs = nullptr,
+                float* part = nullptr) {
+  AfnoWLaunch p;
+  p.x = a.x.data_ptr();
+  p.stats = a.stats.data_ptr<float>();
+  p.gamma = a.gamma.data_ptr<float>();
+  p.beta = a.beta.data_ptr<float>();
+  p.pre = a.pre_ptr();
+  p.spec = a.X.defined() ? a.X.data_ptr() : nullptr;
+  p.out = out;
+  p.lo2 = lo2;
+  p.pairs = pairs;
+  p.part = part;
+  p.O = static_cast<int>(a.O);
+  p.L = static_cast<int>(a.n);
+  p.C = static_cast<int>(a.C);
+  p.KM = static_cast<int>(a.km);
+  p.scale = static_cast<float>(scale);
+  p.f32 = a.x.scalar_type() == at::kFloat ? 1 : 0;  // these kernels take one dtype for x, the spectrum and out
+  (a.X.defined() ? launch_afno_w_c2r_ln : launch_afno_w_r2c_ln)(p, current_stream(a.x));
+}
+
+// ---- route
+// MI_DFT_NO_AFNO_W=1 (A/B, read once): LayerNorm-fused AFNO W-transforms on the generic fixed
+// Stockham kernels instead of afno_wfft.hip (same results)
+bool afno_w_enabled() {
+  static const bool on = tuning_env("MI_DFT_NO_AFNO_W") == nullptr;
+  return on;
+}
+
+// Whether afno_wfft.hip runs a call whose dtypes one of its instances covers: the specialised shape, and O = the
+// number of [L, C] planes
+bool afno_w_takes(int64_t L, int64_t C, int64_t KM, int64_t O) {
+  return afno_w_enabled() && L < (int64_t(1) << 31) && C < (int64_t(1) << 31) && KM < (int64_t(1) << 31) &&
+         afno_w_supported(static_cast<int>(L), static_cast<int>(C), static_cast<int>(KM)) && O < (int64_t(1) << 31);
+}
+
+enum class WlnKernel {
+  Wfft,      // the two-pass kernels of afno_wfft.hip
+  Stockham,  // the fixed Stockham kernels' LayerNorm pass, if one is compiled for the pass: launch_fft_fixed (inside
+             // run_pass) decides for the ops and describe_fft_fixed for afno_w_info, both on build_pass_desc's
+             // descriptor; a pass they decline goes the Aten way.  wln_route offers it up to lds_limit() only, the
+             // bound of run_pass's first line (a LayerNorm pass is never composed from shorter ones)
+  Aten,      // ATen LayerNorm + the plain transform (counted by fallback_counts)
+  None,      // the op raises
+};
+struct WlnRoute {
+  WlnKernel kernel;
+  const char* reason;  // None: why the op raises; Aten, and Stockham once declined: why no fused kernel ran
+};
+
+// Where a non-empty call of the family runs on the device.  The ops dispatch on it, afno_w_info prints it.
+// in / out: as for wln_refusal.
+WlnRoute wln_route(WlnOp op, int64_t L, int64_t C, int64_t KM, int64_t O, at::ScalarType in, at::ScalarType out) {
+  if (const char* why = wln_refusal(op, C, in, out)) return {WlnKernel::None, why};
+  const bool bf16 = in == at::kBFloat16 && out == at::kBFloat16, f32 = in == at::kFloat && out == at::kFloat;
+  if ((bf16 || f32) && afno_w_takes(L, C, KM, O)) return {WlnKernel::Wfft, ""};
+  // From here on c2r_ln_add_split and c2r_ln_add_part run c2r_ln_add and compute their extra outputs with ATen:
+  // the rest is c2r_ln_add's route for them.  The Stockham LayerNorm pass covers bf16 in and out only.
+  if (!bf16) return {WlnKernel::Aten, "no LayerNorm-fused fp32 kernel for this shape"};
+  return {L >= 1 && L <= lds_limit() ? WlnKernel::Stockham : WlnKernel::Aten, "no LayerNorm-fused kernel for this shape"};
+}
+
+// An empty spectrum skips the hand kernels
+WlnRoute c2r_ln_route(WlnOp op, const WlnArgs& a) {
+  if (a.X.numel() == 0) return {WlnKernel::Aten, "empty spectrum"};
+  return wln_route(op, a.n, a.C, a.km, a.O, a.X.scalar_type(), a.x.scalar_type());
+}
+
+// ---- r2c_ln
+at::Tensor r2c_ln_cuda(const at::Tensor& x_, int64_t dim, double scale, int64_t keep, const at::Tensor& stats_,
+                       const at::Tensor& g_, const at::Tensor& b_, const std::optional<at::Tensor>& pre_,
+                       std::optional<at::ScalarType> out_dtype) {
+  const c10::DeviceGuard guard(x_.device());
+  const WlnArgs a = wln_args(WlnOp::R2cLn, at::Tensor(), x_, dim, 0, keep, stats_, g_, b_, pre_);
+  const at::ScalarType idt = a.x.scalar_type(), odt = out_dtype.value_or(idt);
+  to_dtype(idt);
+  to_dtype(odt);
+  at::Tensor out = r2c_ln_empty(a.x, a.km, odt);
+  if (a.x.numel() == 0) return out.zero_();
+  const WlnKernel k = wln_route(WlnOp::R2cLn, a.n, a.C, a.km, a.O, idt, odt).kernel;
+  if (k == WlnKernel::Wfft) {
+    launch_wln(a, scale, out.data_ptr());
+    return checked(out, "r2c_ln");
+  }
+  if (k == WlnKernel::Stockham) {
+    const LnIO ln = a.ln();
+    const std::vector<int64_t> cur = a.x.sizes().vec(), nxt(out.sizes().begin(), out.sizes().end() - 1);
+    if (run_pass(Kind::R2C, a.x, out, cur, nxt, static_cast<int>(a.axis), a.n, static_cast<int>(a.n), 0,
+                 static_cast<int>(a.km), 0, static_cast<float>(scale), false, nullptr, nullptr, &ln))
+      return checked(out, "r2c_ln");
+  }
+  // no specialised kernel for this shape: normalise with ATen, then the plain R2C
+  fallback_note("r2c_ln", "no LayerNorm-fused W-transform for this shape/dtype: ATen LayerNorm + the plain R2C");
+  at::Tensor h = ln_apply(a.x, a.stats, a.gamma, a.beta, a.pre, nullptr).to(idt);
+  const std::vector<int64_t> dv{a.axis}, kv{a.km, 0};
+  return r2c_cuda(h, dv, scale, kv, odt);
+}
+
+at::Tensor r2c_ln_cpu(const at::Tensor& x, int64_t dim, double scale, int64_t keep, const at::Tensor& stats,
+                      const at::Tensor& g, const at::Tensor& b, const std::optional<at::Tensor>& pre,
+                      std::optional<at::ScalarType> out_dtype) {
+  check_wln(WlnOp::R2cLn, at::Tensor(), x, dim, 0, stats, g, b, pre);
+  at::Tensor h = ln_apply(x, stats, g, b, pre.value_or(at::Tensor()), nullptr).to(x.scalar_type());
+  const std::vector<int64_t> dv{x.dim() - 2}, kv{keep, 0};
+  return r2c_cpu(h, dv, scale, kv, out_dtype);
+}
+
+at::Tensor r2c_ln_meta(const at::Tensor& x, int64_t, double, int64_t keep, const at::Tensor&, const at::Tensor&,
+                       const at::Tensor&, const std::optional<at::Tensor>&, std::optional<at::ScalarType> out_dtype) {
+  return r2c_ln_empty(x, r2c_ln_kept(x, keep), out_dtype);
+}
+
+// ---- c2r_ln_add
+// On the device from checked arguments: the op itself, and what the split and part ops run outside the specialised
+// shape (counted as c2r_ln_add's fallback when ATen computes it).
+at::Tensor c2r_ln_add_device(const WlnArgs& a, double scale) {
+  const WlnKernel k = c2r_ln_route(WlnOp::C2rLnAdd, a).kernel;
+  if (k == WlnKernel::Wfft || k == WlnKernel::Stockham) {
+    at::Tensor out = c2r_ln_add_empty(a.x);
+    if (k == WlnKernel::Wfft) {
+      launch_wln(a, scale, out.data_ptr());
+      return checked(out, "c2r_ln_add");
+    }
+    const LnIO ln = a.ln();
+    const std::vector<int64_t> cur(a.X.sizes().begin(), a.X.sizes().end() - 1), nxt = a.x.sizes().vec();
+    if (run_pass(Kind::C2R, a.X, out, cur, nxt, static_cast<int>(a.axis), a.n, static_cast<int>(a.km), 0,
+                 static_cast<int>(a.n), 0, static_cast<float>(scale), true, a.x.data_ptr(), nullptr, &ln))
+      return checked(out, "c2r_ln_add");
+  }
+  fallback_note("c2r_ln_add", "no LayerNorm-fused W-transform for this shape/dtype: ATen LayerNorm + the plain C2R");
+  at::Tensor xp;
+  at::Tensor h = ln_apply(a.x, a.stats, a.gamma, a.beta, a.pre, &xp);
+  const std::vector<int64_t> dv{a.axis}, nv{a.n}, kv{a.km, 0};
+  const at::ScalarType dt = a.x.scalar_type();
+  return c2r_add_cuda(a.X, dv, nv, scale, kv, xp.to(dt).contiguous(), h.to(dt).contiguous(), dt);
+}
+
+// With ATen from checked arguments: the CPU forms of the three C2R ops
+at::Tensor c2r_ln_add_aten(const at::Tensor& X, int64_t n, double scale, const at::Tensor& x, const at::Tensor& stats,
+                           const at::Tensor& g, const at::Tensor& b, const std::optional<at::Tensor>& pre) {
+  const int64_t axis = x.dim() - 2;
+  at::Tensor xp;
+  at::Tensor h = ln_apply(x, stats, g, b, pre.value_or(at::Tensor()), &xp);
+  const std::vector<int64_t> dv{axis}, nv{n}, kv{X.size(axis), 0};
+  at::Tensor y = c2r_cpu(X, dv, nv, scale, kv, at::kFloat);
+  return (y + xp + h).to(x.scalar_type()).contiguous();
+}
+
+at::Tensor c2r_ln_add_cuda(const at::Tensor& X, int64_t dim, int64_t n, double scale, const at::Tensor& x,
+                           const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
+                           const std::optional<at::Tensor>& pre) {
+  const c10::DeviceGuard guard(X.device());
+  return c2r_ln_add_device(wln_args(WlnOp::C2rLnAdd, X, x, dim, n, 0, stats, g, b, pre), scale);
+}
+
+at::Tensor c2r_ln_add_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale, const at::Tensor& x,
+                          const at::Tensor& stats, const at::Tensor& g, const at::Tensor& b,
+                          const std::optional<at::Tensor>& pre) {
+  check_wln(WlnOp::C2rLnAdd, X, x, dim, n, stats, g, b, pre);
+  return c2r_ln_add_aten(X, n, scale, x, stats, g, b, pre);
+}
+
+at::Tensor c2r_ln_add_meta(const at::Tensor&, int64_t, int64_t, double, const at::Tensor& x, const at::Tensor&,
+                           const at::Tensor&, const at::Tensor&, const std::optional<at::Tensor>&) {
+  return c2r_ln_add_empty(x);
+}
+
+// ---- c2r_ln_add_split
+// c2r_ln_add + the residual stream's bf16x3 split-pair rows and per-64-channel LayerNorm partials
+// (mean, M2), all from the one C2R epilogue (afno_wfft.hip SPLIT instantiation): the fp32 block's
+// fc1 then reads the pairs with LN2 folded in (linear3_ln) -- no LayerNorm / split pass.
+// The pairs hold out - mean(x) per token (stats[:, 0], the input's LayerNorm mean): centred, the
+// split keeps 2^-17 of the deviation rather than of |out|, and ln_stats_merge(part, eps, stats)
+// gives fc1 the matching centred mean.
+// Returns (out [..., W, C] fp32, pairs [tokens, 2C] bf16, part [tokens, C/64, 2] fp32).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> split_and_partials(const at::Tensor& y, const at::Tensor& stats) {
+  const int64_t C = y.size(-1);
+  at::Tensor rows = y.reshape({-1, C}).to(at::kFloat);
+  const int64_t M = rows.size(0);
+  at::Tensor z = rows - stats.reshape({-1, 2}).select(1, 0).to(at::kFloat).unsqueeze(1);
+  at::Tensor hi = z.to(at::kBFloat16);
+  at::Tensor lo = (z - hi.to(at::kFloat)).to(at::kBFloat16);
+  at::Tensor pairs = at::cat({hi.reshape({M, C / 32, 32}), lo.reshape({M, C / 32, 32})}, -1).reshape({M, 2 * C}).contiguous();
+  at::Tensor w = rows.reshape({M, C / 64, 64});
+  at::Tensor mean = w.mean(2);
+  at::Tensor m2 = (w - mean.unsqueeze(2)).pow(2).sum(2);
+  return {y, pairs, at::stack({mean, m2}, 2).contiguous()};
+}
+
+// (out, pairs, part) of the ATen paths -> out_mode's first result: out (1), its lo2 term
+// bf16(out - m - (hi + lo)) (2, m = stats[:, 0], the pairs' centring) or nothing (0)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> out_mode_result(std::tuple<at::Tensor, at::Tensor, at::Tensor> r,
+                                                                const at::Tensor& stats, int64_t out_mode) {
+  if (out_mode == 1) return r;
+  at::Tensor& out = std::get<0>(r);
+  if (out_mode == 0) {
+    out = at::empty({0}, out.options());
+    return r;
+  }
+  const int64_t C = out.size(-1);
+  at::Tensor z = out.reshape({-1, C}).to(at::kFloat) - stats.to(at::kFloat).reshape({-1, 2}).select(1, 0).unsqueeze(1);
+  at::Tensor pr = std::get<1>(r).to(at::kFloat).reshape({-1, C / 32, 2, 32});
+  out = (z - (pr.select(2, 0) + pr.select(2, 1)).reshape({-1, C})).to(at::kBFloat16);
+  return r;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_cuda(const at::Tensor& X, int64_t dim, int64_t n, double scale,
+                                                                     const at::Tensor& x, const at::Tensor& stats,
+                                                                     const at::Tensor& g, const at::Tensor& b,
+                                                                     const std::optional<at::Tensor>& pre, int64_t out_mode) {
+  const c10::DeviceGuard guard(X.device());
+  const WlnArgs a = wln_args(WlnOp::C2rLnAddSplit, X, x, dim, n, 0, stats, g, b, pre, out_mode);
+  if (c2r_ln_route(WlnOp::C2rLnAddSplit, a).kernel == WlnKernel::Wfft) {
+    auto [out, pairs, part] = c2r_ln_add_split_empty(a.x, out_mode);
+    launch_wln(a, scale, out_mode == 1 ? out.data_ptr() : nullptr,
+               out_mode == 2 ? reinterpret_cast<uint16_t*>(out.data_ptr()) : nullptr,
+               reinterpret_cast<uint16_t*>(pairs.data_ptr()), part.data_ptr<float>());
+    return {checked(out, "c2r_ln_add_split"), pairs, part};
+  }
+  fallback_note("c2r_ln_add_split", "no fused W-transform for this shape: c2r_ln_add + ATen split / statistics");
+  return out_mode_result(split_and_partials(c2r_ln_add_device(a, scale), a.stats), a.stats, out_mode);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale,
+                                                                    const at::Tensor& x, const at::Tensor& stats,
+                                                                    const at::Tensor& g, const at::Tensor& b,
+                                                                    const std::optional<at::Tensor>& pre, int64_t out_mode) {
+  check_wln(WlnOp::C2rLnAddSplit, X, x, dim, n, stats, g, b, pre, out_mode);
+  return out_mode_result(split_and_partials(c2r_ln_add_aten(X, n, scale, x, stats, g, b, pre), stats), stats, out_mode);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> c2r_ln_add_split_meta(const at::Tensor&, int64_t, int64_t, double,
+                                                                     const at::Tensor& x, const at::Tensor&, const at::Tensor&,
+                                                                     const at::Tensor&, const std::optional<at::Tensor>&,
+                                                                     int64_t out_mode) {
+  return c2r_ln_add_split_empty(x, out_mode);
+}
+
+// ---- c2r_ln_add_part
+// bf16 block: c2r_ln_add + the next LayerNorm's per-64-channel partials (mean, M2) of the STORED
+// (bf16-rounded) output, from the one C2R epilogue (afno_wfft.hip PART instantiation); ln_stats_merge
+// turns them into LN2's (mean, rstd) without an ln_stats pass over the residual stream.
+// Returns (out [..., W, C] bf16, part [tokens, C/64, 2] fp32).
+std::tuple<at::Tensor, at::Tensor> out_and_partials(const at::Tensor& y) {
+  const int64_t C = y.size(-1);
+  at::Tensor w = y.reshape({-1, C / 64, 64}).to(at::kFloat);
+  at::Tensor mean = w.mean(2);
+  at::Tensor m2 = (w - mean.unsqueeze(2)).pow(2).sum(2);
+  return {y, at::stack({mean, m2}, 2).contiguous()};
+}
+
+std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_cuda(const at::Tensor& X, int64_t dim, int64_t n, double scale,
+                                                        const at::Tensor& x, const at::Tensor& stats, const at::Tensor& g,
+                                                        const at::Tensor& b, const std::optional<at::Tensor>& pre) {
+  const c10::DeviceGuard guard(X.device());
+  const WlnArgs a = wln_args(WlnOp::C2rLnAddPart, X, x, dim, n, 0, stats, g, b, pre);
+  if (c2r_ln_route(WlnOp::C2rLnAddPart, a).kernel == WlnKernel::Wfft) {
+    auto [out, part] = c2r_ln_add_part_empty(a.x);
+    launch_wln(a, scale, out.data_ptr(), nullptr, nullptr, part.data_ptr<float>());
+    return {checked(out, "c2r_ln_add_part"), part};
+  }
+  fallback_note("c2r_ln_add_part", "no fused W-transform for this shape: c2r_ln_add + ATen statistics");
+  return out_and_partials(c2r_ln_add_device(a, scale));
+}
+
+std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_cpu(const at::Tensor& X, int64_t dim, int64_t n, double scale,
+                                                       const at::Tensor& x, const at::Tensor& stats, const at::Tensor& g,
+                                                       const at::Tensor& b, const std::optional<at::Tensor>& pre) {
+  check_wln(WlnOp::C2rLnAddPart, X, x, dim, n, stats, g, b, pre);
+  return out_and_partials(c2r_ln_add_aten(X, n, scale, x, stats, g, b, pre));
+}
+
+std::tuple<at::Tensor, at::Tensor> c2r_ln_add_part_meta(const at::Tensor&, int64_t, int64_t, double, const at::Tensor& x,
+                                                        const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                                                        const std::optional<at::Tensor>&) {
+  return c2r_ln_add_part_empty(x);
+}
+
 // ------------------------------------------------------------------ ONNX-contrib parity ops
 void check_contrib_attrs(int64_t normalized, int64_t onesided, int64_t signal_ndim) {
   // dft_plugins.cpp:54-57 ("mimics limitations of ONNX Contrib ops").
@@ -1270,20 +1295,11 @@ std::string fft_pass_info(std::string kind_s, at::IntArrayRef shape, int64_t axi
   TORCH_CHECK(kind == Kind::C2R || stored == L, "amd_dft.fft_pass_info: shape[axis] must be the transform length");
   std::vector<int64_t> in_shape(shape.begin(), shape.end()), out_shape = in_shape;
   out_shape[axis] = kind == Kind::R2C ? half : L;
-  Plan1D plan = make_plan_1d(static_cast<int32_t>(L));
   PassDesc d;
-  d.kind = kind;
-  apply_plan(d, plan);
-  set_axis_geometry(d, in_shape, out_shape, static_cast<int>(axis), kind != Kind::R2C, kind != Kind::C2R);
-  d.in_lo = static_cast<int32_t>(kind == Kind::C2R ? std::min(stored, half) : L);
-  d.in_hi = 0;
-  d.out_lo = static_cast<int32_t>(kind == Kind::R2C ? half : L);
-  d.out_hi = 0;
-  d.inverse = kind == Kind::C2R ? 1 : 0;
-  d.tin = bf16_in ? DType::BF16 : DType::F32;
-  d.tout = bf16_out ? DType::BF16 : DType::F32;
-  TORCH_CHECK(choose_tiling(d), "amd_dft.fft_pass_info: length exceeds the LDS-resident limit");
-  finalize_vec_flags(d, bf16_in ? 2 : 4, bf16_out ? 2 : 4);
+  TORCH_CHECK(build_pass_desc(d, kind, make_plan_1d(static_cast<int32_t>(L)), in_shape, out_shape, static_cast<int>(axis),
+                              kind == Kind::C2R ? std::min(stored, half) : L, 0, kind == Kind::R2C ? half : L, 0,
+                              kind == Kind::C2R, bf16_in ? DType::BF16 : DType::F32, bf16_out ? DType::BF16 : DType::F32),
+              "amd_dft.fft_pass_info: length exceeds the LDS-resident limit");
   const int64_t nsig = kind == Kind::C2C ? d.I : (d.I + 1) / 2;
   std::ostringstream os;
   FixedLaunchInfo fi;
@@ -1305,7 +1321,7 @@ std::string fft_pass_info(std::string kind_s, at::IntArrayRef shape, int64_t axi
 }
 
 // Which route an aligned call of a LayerNorm-fused W-transform takes on the device (host only: no device, no
-// allocation), from the functions the ops decide with (afno_w_takes, afno_w_instance, the fixed kernels' selection):
+// allocation): wln_route's answer, the one the ops dispatch on, printed.
 //   "wfft c2r_bf16_part slabs=3 stage=fp16"                  the two-pass kernels of afno_wfft.hip and the instance
 //   "stockham L=180 TP=15 T=16 cfg=27 pairvec=1"              the fixed Stockham kernels' LayerNorm pass (bf16 only)
 //   "aten <reason>"                                           ATen LayerNorm + the plain transform (counted by
@@ -1313,43 +1329,33 @@ std::string fft_pass_info(std::string kind_s, at::IntArrayRef shape, int64_t axi
 //   "none <reason>"                                           the op raises
 // c2r_ln_add_split / c2r_ln_add_part outside the specialised shape compute their extra outputs with ATen on top of
 // c2r_ln_add: "aten epilogue; c2r_ln_add: <its route>".
-std::string afno_w_info(std::string op, int64_t L, int64_t C, int64_t KM, bool bf16) {
-  const bool r2c = op == "r2c_ln", split = op == "c2r_ln_add_split", part = op == "c2r_ln_add_part";
-  TORCH_CHECK(r2c || split || part || op == "c2r_ln_add",
+std::string afno_w_info(std::string op_s, int64_t L, int64_t C, int64_t KM, bool bf16) {
+  const auto* found = std::find(std::begin(kWlnNames), std::end(kWlnNames), op_s);
+  TORCH_CHECK(found != std::end(kWlnNames),
               "amd_dft.afno_w_info: op must be r2c_ln, c2r_ln_add, c2r_ln_add_split or c2r_ln_add_part");
   TORCH_CHECK(L >= 1 && L < (1 << 30) && C >= 1 && C < (1 << 30) && KM >= 1 && KM <= L / 2 + 1,
               "amd_dft.afno_w_info: needs L, C >= 1 and 1 <= KM <= L / 2 + 1");
-  if (split && bf16) return "none split-pair outputs come with the fp32 residual stream";
-  if (part && !bf16) return "none bf16 spectrum and residual stream (the fp32 block uses c2r_ln_add_split)";
-  if ((split || part) && C % 64 != 0) return "none C must be a multiple of 64";
+  const WlnOp op = static_cast<WlnOp>(found - std::begin(kWlnNames));
+  const bool r2c = op == WlnOp::R2cLn, split = op == WlnOp::C2rLnAddSplit, part = op == WlnOp::C2rLnAddPart;
+  const at::ScalarType dt = bf16 ? at::kBFloat16 : at::kFloat;
+  const WlnRoute r = wln_route(op, L, C, KM, 1, dt, dt);
   std::ostringstream os;
-  if (afno_w_takes(L, C, KM, 1)) {
+  if (r.kernel == WlnKernel::None) {
+    os << "none " << r.reason;
+    return os.str();
+  }
+  if (r.kernel == WlnKernel::Wfft) {
     os << "wfft " << afno_w_instance_name(afno_w_instance(!r2c, !bf16, split, split || part)) << " slabs=" << C / 64
        << " stage=" << (bf16 ? "fp16" : "fp32");
     return os.str();
   }
   if (split || part) os << "aten epilogue; c2r_ln_add: ";
-  if (!bf16) {
-    os << "aten no LayerNorm-fused fp32 kernel for this shape";
-    return os.str();
-  }
-  if (L <= lds_limit()) {
-    const Kind kind = r2c ? Kind::R2C : Kind::C2R;
+  if (r.kernel == WlnKernel::Stockham) {  // the pass the ops hand to run_pass, on one [L, C] plane
     const std::vector<int64_t> in_shape{1, r2c ? L : KM, C}, out_shape{1, r2c ? KM : L, C};
-    Plan1D plan = make_plan_1d(static_cast<int32_t>(L));
     PassDesc d;
-    d.kind = kind;
-    apply_plan(d, plan);
-    set_axis_geometry(d, in_shape, out_shape, 1, kind != Kind::R2C, kind != Kind::C2R);
-    d.in_lo = static_cast<int32_t>(r2c ? L : KM);
-    d.in_hi = 0;
-    d.out_lo = static_cast<int32_t>(r2c ? KM : L);
-    d.out_hi = 0;
-    d.inverse = r2c ? 0 : 1;
-    d.tin = d.tout = DType::BF16;
     FixedLaunchInfo fi;
-    if (choose_tiling(d)) {
-      finalize_vec_flags(d, 2, 2);
+    if (build_pass_desc(d, r2c ? Kind::R2C : Kind::C2R, make_plan_1d(static_cast<int32_t>(L)), in_shape, out_shape, 1,
+                        r2c ? L : KM, 0, r2c ? KM : L, 0, !r2c, DType::BF16, DType::BF16)) {
       alignas(16) static const float probe[4] = {0.f, 0.f, 0.f, 0.f};  // non-null, aligned stand-ins: only tested, never read
       d.ln_stats = d.ln_gamma = d.ln_beta = probe;
       if (!r2c) d.add1 = probe;
@@ -1360,7 +1366,7 @@ std::string afno_w_info(std::string op, int64_t L, int64_t C, int64_t KM, bool b
       }
     }
   }
-  os << "aten no LayerNorm-fused kernel for this shape";
+  os << "aten " << r.reason;
   return os.str();
 }
 
@@ -1410,24 +1416,30 @@ int64_t plan_cache_pinned_count() { return static_cast<int64_t>(plan_cache_pinne
 }  // namespace
 }  // namespace amd_dft
 
+// The dispatched ops of this file, once: name and schema.  Each has name_cuda, name_cpu and name_meta above, so an op
+// missing from one backend fails to compile.
+#define AMD_DFT_DFT_OPS(X)                                                                                            \
+  X(r2c, "(Tensor x, int[] dim, float scale=1.0, int[] keep=[], ScalarType? out_dtype=None) -> Tensor")               \
+  X(c2r, "(Tensor x, int[] dim, int[] out_size, float scale=1.0, int[] keep=[], ScalarType? out_dtype=None) -> Tensor") \
+  X(c2c, "(Tensor x, int[] dim, bool inverse=False, float scale=1.0, ScalarType? out_dtype=None) -> Tensor")          \
+  X(c2r_add, "(Tensor x, int[] dim, int[] out_size, float scale=1.0, int[] keep=[], Tensor? add1=None, "              \
+             "Tensor? add2=None, ScalarType? out_dtype=None) -> Tensor")                                              \
+  X(c2c_axis, "(Tensor x, int dim, int n, int in_lo, int in_hi, int out_lo, int out_hi, bool inverse=False, "         \
+              "float scale=1.0) -> Tensor")                                                                           \
+  X(dftw_r2c, "(Tensor x, int m, float scale=1.0) -> Tensor")                                                         \
+  X(fno_mix_c2c, "(Tensor xm, Tensor w, int n, int in_lo, int in_hi, float scale=1.0, int path=0) -> Tensor")         \
+  X(r2c_ln, "(Tensor x, int dim, float scale, int keep, Tensor stats, Tensor gamma, Tensor beta, Tensor? pre=None, "  \
+            "ScalarType? out_dtype=None) -> Tensor")                                                                  \
+  X(c2r_ln_add, "(Tensor X, int dim, int n, float scale, Tensor x, Tensor stats, Tensor gamma, Tensor beta, "         \
+                "Tensor? pre=None) -> Tensor")                                                                        \
+  X(c2r_ln_add_split, "(Tensor X, int dim, int n, float scale, Tensor x, Tensor stats, Tensor gamma, Tensor beta, "   \
+                      "Tensor? pre=None, int out_mode=1) -> (Tensor, Tensor, Tensor)")                                \
+  X(c2r_ln_add_part, "(Tensor X, int dim, int n, float scale, Tensor x, Tensor stats, Tensor gamma, Tensor beta, "    \
+                     "Tensor? pre=None) -> (Tensor, Tensor)")
+
 TORCH_LIBRARY(amd_dft, m) {
-  m.def("r2c(Tensor x, int[] dim, float scale=1.0, int[] keep=[], ScalarType? out_dtype=None) -> Tensor");
-  m.def("c2r(Tensor x, int[] dim, int[] out_size, float scale=1.0, int[] keep=[], ScalarType? out_dtype=None) -> Tensor");
-  m.def("c2c(Tensor x, int[] dim, bool inverse=False, float scale=1.0, ScalarType? out_dtype=None) -> Tensor");
-  m.def("c2r_add(Tensor x, int[] dim, int[] out_size, float scale=1.0, int[] keep=[], Tensor? add1=None, "
-        "Tensor? add2=None, ScalarType? out_dtype=None) -> Tensor");
-  m.def("c2c_axis(Tensor x, int dim, int n, int in_lo, int in_hi, int out_lo, int out_hi, bool inverse=False, "
-        "float scale=1.0) -> Tensor");
-  m.def("dftw_r2c(Tensor x, int m, float scale=1.0) -> Tensor");
-  m.def("fno_mix_c2c(Tensor xm, Tensor w, int n, int in_lo, int in_hi, float scale=1.0, int path=0) -> Tensor");
-  m.def("r2c_ln(Tensor x, int dim, float scale, int keep, Tensor stats, Tensor gamma, Tensor beta, Tensor? pre=None, "
-        "ScalarType? out_dtype=None) -> Tensor");
-  m.def("c2r_ln_add(Tensor X, int dim, int n, float scale, Tensor x, Tensor stats, Tensor gamma, Tensor beta, "
-        "Tensor? pre=None) -> Tensor");
-  m.def("c2r_ln_add_split(Tensor X, int dim, int n, float scale, Tensor x, Tensor stats, Tensor gamma, Tensor beta, "
-        "Tensor? pre=None, int out_mode=1) -> (Tensor, Tensor, Tensor)");
-  m.def("c2r_ln_add_part(Tensor X, int dim, int n, float scale, Tensor x, Tensor stats, Tensor gamma, Tensor beta, "
-        "Tensor? pre=None) -> (Tensor, Tensor)");
+  AMD_DFT_DFT_OPS(AMD_DFT_DEF)
+  // composite: they call r2c / c2r through the dispatcher
   m.def("Rfft(Tensor x, int normalized=0, int onesided=1, int signal_ndim=1) -> Tensor");
   m.def("Irfft(Tensor x, int normalized=0, int onesided=1, int signal_ndim=1) -> Tensor");
   m.def("plan_info(int n) -> str", &amd_dft::plan_info);
@@ -1441,49 +1453,9 @@ TORCH_LIBRARY(amd_dft, m) {
   m.def("plan_cache_clear() -> ()", &amd_dft::plan_cache_clear);
   m.def("plan_cache_pinned() -> int", &amd_dft::plan_cache_pinned_count);
 }
-
-TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) {
-  m.impl("r2c", AMD_DFT_TRACED("amd_dft::r2c", amd_dft::r2c_cuda));
-  m.impl("c2r", AMD_DFT_TRACED("amd_dft::c2r", amd_dft::c2r_cuda));
-  m.impl("c2c", AMD_DFT_TRACED("amd_dft::c2c", amd_dft::c2c_cuda));
-  m.impl("c2r_add", AMD_DFT_TRACED("amd_dft::c2r_add", amd_dft::c2r_add_cuda));
-  m.impl("c2c_axis", AMD_DFT_TRACED("amd_dft::c2c_axis", amd_dft::c2c_axis_cuda));
-  m.impl("dftw_r2c", AMD_DFT_TRACED("amd_dft::dftw_r2c", amd_dft::dftw_r2c_cuda));
-  m.impl("fno_mix_c2c", AMD_DFT_TRACED("amd_dft::fno_mix_c2c", amd_dft::fno_mix_c2c_cuda));
-  m.impl("r2c_ln", AMD_DFT_TRACED("amd_dft::r2c_ln", amd_dft::r2c_ln_cuda));
-  m.impl("c2r_ln_add", AMD_DFT_TRACED("amd_dft::c2r_ln_add", amd_dft::c2r_ln_add_cuda));
-  m.impl("c2r_ln_add_split", AMD_DFT_TRACED("amd_dft::c2r_ln_add_split", amd_dft::c2r_ln_add_split_cuda));
-  m.impl("c2r_ln_add_part", AMD_DFT_TRACED("amd_dft::c2r_ln_add_part", amd_dft::c2r_ln_add_part_cuda));
-}
-
-TORCH_LIBRARY_IMPL(amd_dft, CPU, m) {
-  m.impl("r2c", AMD_DFT_TRACED("amd_dft::r2c", amd_dft::r2c_cpu));
-  m.impl("c2r", AMD_DFT_TRACED("amd_dft::c2r", amd_dft::c2r_cpu));
-  m.impl("c2c", AMD_DFT_TRACED("amd_dft::c2c", amd_dft::c2c_cpu));
-  m.impl("c2r_add", AMD_DFT_TRACED("amd_dft::c2r_add", amd_dft::c2r_add_cpu));
-  m.impl("c2c_axis", AMD_DFT_TRACED("amd_dft::c2c_axis", amd_dft::c2c_axis_cpu));
-  m.impl("dftw_r2c", AMD_DFT_TRACED("amd_dft::dftw_r2c", amd_dft::dftw_r2c_cpu));
-  m.impl("fno_mix_c2c", AMD_DFT_TRACED("amd_dft::fno_mix_c2c", amd_dft::fno_mix_c2c_cpu));
-  m.impl("r2c_ln", AMD_DFT_TRACED("amd_dft::r2c_ln", amd_dft::r2c_ln_cpu));
-  m.impl("c2r_ln_add", AMD_DFT_TRACED("amd_dft::c2r_ln_add", amd_dft::c2r_ln_add_cpu));
-  m.impl("c2r_ln_add_split", AMD_DFT_TRACED("amd_dft::c2r_ln_add_split", amd_dft::c2r_ln_add_split_cpu));
-  m.impl("c2r_ln_add_part", AMD_DFT_TRACED("amd_dft::c2r_ln_add_part", amd_dft::c2r_ln_add_part_cpu));
-}
-
-TORCH_LIBRARY_IMPL(amd_dft, Meta, m) {
-  m.impl("r2c", &amd_dft::r2c_meta);
-  m.impl("c2r", &amd_dft::c2r_meta);
-  m.impl("c2c", &amd_dft::c2c_meta);
-  m.impl("c2r_add", &amd_dft::c2r_add_meta);
-  m.impl("c2c_axis", &amd_dft::c2c_axis_meta);
-  m.impl("dftw_r2c", &amd_dft::dftw_r2c_meta);
-  m.impl("fno_mix_c2c", &amd_dft::fno_mix_c2c_meta);
-  m.impl("r2c_ln", &amd_dft::r2c_ln_meta);
-  m.impl("c2r_ln_add", &amd_dft::c2r_ln_add_meta);
-  m.impl("c2r_ln_add_split", &amd_dft::c2r_ln_add_split_meta);
-  m.impl("c2r_ln_add_part", &amd_dft::c2r_ln_add_part_meta);
-}
-
+TORCH_LIBRARY_IMPL(amd_dft, CUDA, m) { AMD_DFT_DFT_OPS(AMD_DFT_IMPL_CUDA) }
+TORCH_LIBRARY_IMPL(amd_dft, CPU, m) { AMD_DFT_DFT_OPS(AMD_DFT_IMPL_CPU) }
+TORCH_LIBRARY_IMPL(amd_dft, Meta, m) { AMD_DFT_DFT_OPS(AMD_DFT_IMPL_META) }
 TORCH_LIBRARY_IMPL(amd_dft, CompositeImplicitAutograd, m) {
   m.impl("Rfft", &amd_dft::contrib_rfft);
   m.impl("Irfft", &amd_dft::contrib_irfft);
