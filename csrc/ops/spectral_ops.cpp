@@ -876,6 +876,173 @@ std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t
          " threads=" + std::to_string(kDiscoThreads) + (bf16 ? " bf16=1" : "");
 }
 
+// ------------------------------------------------------------------ DISCO convolution on the sphere (transposed half)
+// z [..., C, K, nlat_in, nlon_in], a gather CSR over rows k * s + rho, s = nlon_out / nlon_in (row_ptr int32
+// [nlat_out * s + 1], idx int32 [nnz] = (k' * K + p) * nlon_in + d sorted within a row, val [nnz]), bias [C] fp32 or
+// none -> y [..., C, nlat_out, nlon_out]:
+//   y[n, k, s t + rho] = sum_e val[e] * z[n, p_e, k'_e, (d_e + t) mod nlon_in] (+ bias[c]),  0 <= t < nlon_in
+// z float32 or bfloat16 with float32 val, fp32 accumulation, the bias added in fp32, one rounding to z's dtype.  CPU
+// tensors only: float64 z with float64 val.  The table is trusted to be what ops.disco.disco_transpose_tables builds
+// (the holder checks it on the host); the kernel reads nothing outside z whatever it holds, and the CPU kernel checks
+// every entry.
+void check_disco_t(const char* op, const at::Tensor& z, const at::Tensor& row_ptr, const at::Tensor& idx,
+                   const at::Tensor& val, int64_t nlat_out, int64_t nlon_out, const c10::optional<at::Tensor>& bias) {
+  const auto zt = z.scalar_type();
+  TORCH_CHECK(zt == at::kFloat || zt == at::kBFloat16 || (zt == at::kDouble && z.device().is_cpu()), op,
+              ": z must be float32 or bfloat16 (float64 on CPU tensors), got ", zt);
+  TORCH_CHECK(val.scalar_type() == (zt == at::kDouble ? at::kDouble : at::kFloat), op, ": val must be ",
+              zt == at::kDouble ? "float64 for a float64 z" : "float32", ", got ", val.scalar_type());
+  TORCH_CHECK(row_ptr.scalar_type() == at::kInt && idx.scalar_type() == at::kInt, op,
+              ": row_ptr and idx must be int32, got ", row_ptr.scalar_type(), " and ", idx.scalar_type());
+  TORCH_CHECK(z.dim() >= 4, op, ": z must be [..., C, K, nlat_in, nlon_in], got ", z.sizes());
+  const int64_t C = z.size(-4), K = z.size(-3), nlat_in = z.size(-2), nlon_in = z.size(-1);
+  TORCH_CHECK(K >= 1 && nlat_in >= 1 && nlon_in >= 1 && K * nlat_in * nlon_in < (int64_t(1) << 31), op,
+              ": K and the input grid must be non-empty and K * nlat_in * nlon_in below 2^31, got ", K, " x ", nlat_in,
+              " x ", nlon_in);
+  TORCH_CHECK(nlat_out >= 1 && nlon_out >= 1, op, ": nlat_out and nlon_out must be >= 1");
+  TORCH_CHECK(nlon_out % nlon_in == 0, op, ": nlon_out (", nlon_out, ") must be a multiple of nlon_in (", nlon_in, ")");
+  const int64_t s = nlon_out / nlon_in;
+  TORCH_CHECK(nlat_out * s < (int64_t(1) << 31) - 1, op, ": too many table rows");
+  TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.size(0) == nlat_out * s + 1, op, ": row_ptr must be [nlat_out * s + 1] = [",
+              nlat_out * s + 1, "], got ", row_ptr.sizes());
+  TORCH_CHECK(idx.dim() == 1 && val.dim() == 1 && idx.size(0) == val.size(0) && idx.size(0) < (int64_t(1) << 31), op,
+              ": idx and val must be [nnz] with nnz < 2^31, got ", idx.sizes(), " and ", val.sizes());
+  TORCH_CHECK(row_ptr.device() == z.device() && idx.device() == z.device() && val.device() == z.device(), op,
+              ": row_ptr, idx and val must be on the device of z");
+  if (present(bias)) {
+    TORCH_CHECK(bias->scalar_type() == (zt == at::kDouble ? at::kDouble : at::kFloat), op, ": bias must be ",
+                zt == at::kDouble ? "float64 for a float64 z" : "float32", ", got ", bias->scalar_type());
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == C, op, ": bias must be [C] = [", C, "], got ", bias->sizes());
+    TORCH_CHECK(bias->device() == z.device(), op, ": bias must be on the device of z");
+  }
+}
+
+std::vector<int64_t> disco_t_out_shape(const at::Tensor& z, int64_t nlat_out, int64_t nlon_out) {
+  TORCH_CHECK(z.dim() >= 4, "disco_t: z must be [..., C, K, nlat_in, nlon_in]");
+  std::vector<int64_t> s(z.sizes().begin(), z.sizes().end() - 3);
+  s.insert(s.end(), {nlat_out, nlon_out});
+  return s;
+}
+
+at::Tensor disco_t_ref(const at::Tensor& z, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+                       int64_t nlat_out, int64_t nlon_out, const c10::optional<at::Tensor>& bias) {
+  const int64_t C = z.size(-4), K = z.size(-3), nlat_in = z.size(-2), nlon_in = z.size(-1);
+  const int64_t s = nlon_out / nlon_in, rows = nlat_out * s, nnz = idx.size(0), pin = nlat_in * nlon_in;
+  const at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vd = val.to(at::kDouble).contiguous();
+  const int32_t* rpp = rp.data_ptr<int32_t>();
+  const int32_t* ixp = ix.data_ptr<int32_t>();
+  const double* vp = vd.data_ptr<double>();
+  TORCH_CHECK(rpp[0] >= 0 && rpp[rows] <= nnz, "disco_t: row_ptr must run from >= 0 to <= nnz");
+  for (int64_t r = 0; r < rows; ++r)
+    TORCH_CHECK(rpp[r] <= rpp[r + 1], "disco_t: row_ptr must not decrease (row ", r, ")");
+  for (int64_t e = rpp[0]; e < rpp[rows]; ++e)
+    TORCH_CHECK(ixp[e] >= 0 && ixp[e] < K * pin, "disco_t: idx[", e, "] = ", ixp[e], " is outside the input grid");
+  // the fp32 / bf16 values as they are, every sum in fp64 in table order, the bias last, one rounding to z's dtype
+  const at::Tensor zd = z.to(at::kDouble).contiguous();
+  const int64_t planes = zd.numel() / (K * pin);
+  at::Tensor bd;
+  if (present(bias)) bd = bias->to(at::kDouble).contiguous();
+  const double* bp = bd.defined() ? bd.data_ptr<double>() : nullptr;
+  at::Tensor y = at::zeros(disco_t_out_shape(z, nlat_out, nlon_out), zd.options());
+  const double* zp = zd.data_ptr<double>();
+  double* yp = y.data_ptr<double>();
+  at::parallel_for(0, planes * nlat_out, 1, [&](int64_t b, int64_t e_) {
+    for (int64_t u = b; u < e_; ++u) {
+      const int64_t n = u / nlat_out, k = u % nlat_out;
+      const double* zn = zp + n * K * pin;
+      double* yr = yp + u * nlon_out;
+      for (int64_t rho = 0; rho < s; ++rho) {
+        const int64_t r = k * s + rho;
+        for (int64_t e = rpp[r]; e < rpp[r + 1]; ++e) {
+          const int64_t q = ixp[e] / nlon_in, d = ixp[e] - q * nlon_in, kin = q / K, p = q - kin * K;
+          const double* zr = zn + p * pin + kin * nlon_in;
+          const double v = vp[e];
+          for (int64_t t = 0; t < nlon_in; ++t) {
+            int64_t c = d + t;
+            if (c >= nlon_in) c -= nlon_in;
+            yr[s * t + rho] += v * zr[c];
+          }
+        }
+      }
+      if (bp)
+        for (int64_t j = 0; j < nlon_out; ++j) yr[j] += bp[n % C];
+    }
+  });
+  return y.to(z.scalar_type());
+}
+
+// the launch path of disco_t and disco_t_out (y contiguous, z's dtype)
+void disco_t_run(const at::Tensor& z_, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+                 int64_t nlat_out, int64_t nlon_out, const c10::optional<at::Tensor>& bias, const at::Tensor& y) {
+  if (y.numel() == 0) return;
+  at::Tensor z = z_.contiguous();  // element loads: a view at any element offset is read where it is
+  at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vl = val.contiguous();
+  at::Tensor bf = f32_or_undef(bias);
+  DiscoTLaunch p;
+  p.z = z.data_ptr();
+  p.row_ptr = rp.data_ptr<int32_t>();
+  p.idx = ix.data_ptr<int32_t>();
+  p.val = vl.data_ptr<float>();
+  p.bias = bf.defined() ? bf.data_ptr<float>() : nullptr;
+  p.y = y.data_ptr();
+  p.C = z.size(-4);
+  p.K = static_cast<int>(z.size(-3));
+  p.nlat_in = static_cast<int>(z.size(-2));
+  p.nlon_in = static_cast<int>(z.size(-1));
+  p.planes = z.numel() / (z.size(-3) * z.size(-2) * z.size(-1));
+  p.nlat_out = static_cast<int>(nlat_out);
+  p.nlon_out = static_cast<int>(nlon_out);
+  p.nnz = idx.size(0);
+  p.bf16 = z.scalar_type() == at::kBFloat16 ? 1 : 0;
+  launch_disco_t(p, current_stream(z));
+}
+
+void check_disco_t_device(const char* op, const at::Tensor& z, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                          int64_t nlat_out, int64_t nlon_out, const c10::optional<at::Tensor>&) {
+  TORCH_CHECK(z.size(-3) * z.size(-1) * 4 <= kDiscoLdsBytes, op, ": K * nlon_in must be at most ", kDiscoLdsBytes / 4,
+              " on the device (the K basis planes of one input latitude per LDS chunk), got ", z.size(-3), " * ",
+              z.size(-1));
+  TORCH_CHECK(nlon_out < (int64_t(1) << 28) && nlat_out < (int64_t(1) << 30), op, ": output grid too large");
+}
+
+struct DiscoT : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t,
+                         const c10::optional<at::Tensor>&);
+  static constexpr const char *name = "disco_t", *out_name = "disco_t_out";
+  static constexpr auto& check = check_disco_t;
+  static constexpr auto& check_device = check_disco_t_device;
+  static OpResult result(const at::Tensor& z, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t nlat_out,
+                         int64_t nlon_out, const c10::optional<at::Tensor>&) {
+    return {disco_t_out_shape(z, nlat_out, nlon_out), z.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& z, const A&...) {  // element stores
+    return z.element_size();
+  }
+  static constexpr auto& reference = disco_t_ref;
+  static constexpr auto& run = disco_t_run;
+};
+AMD_DFT_OP_FAMILY(disco_t, DiscoT)
+
+// Which instance and grid disco_t runs -- host only, no device; from disco_t_route, which launch_disco_t dispatches
+// on: "PT=1 rows=7 lds=60480 ptiles=20 wgs=14400 passes=1 phases=2 items=3 threads=256".  As with disco_info the band
+// of an output latitude is in the table, so whether it is walked in chunks is not part of the answer.
+std::string disco_t_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out,
+                         int64_t nlon_out, int64_t nnz_max, bool bf16) {
+  TORCH_CHECK(planes >= 1 && nlat_in >= 1 && nlon_in >= 1 && K >= 1 && nlat_out >= 1 && nlon_out >= 1 &&
+                  K < (int64_t(1) << 31) && nlat_in * nlon_in < (int64_t(1) << 31) &&
+                  K * nlat_in * nlon_in < (int64_t(1) << 31) && nnz_max >= 0 && nnz_max < (int64_t(1) << 31),
+              "amd_dft.disco_t_info: sizes must be >= 1 and K * nlat_in * nlon_in and nnz_max below 2^31");
+  TORCH_CHECK(nlon_out % nlon_in == 0, "amd_dft.disco_t_info: nlon_out must be a multiple of nlon_in");
+  TORCH_CHECK(K * nlon_in * 4 <= kDiscoLdsBytes, "amd_dft.disco_t_info: K * nlon_in must be at most ",
+              kDiscoLdsBytes / 4);
+  const DiscoTRoute r = disco_t_route(planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
+  return "PT=" + std::to_string(r.pt) + " rows=" + std::to_string(r.rows) + " lds=" + std::to_string(r.lds) +
+         " ptiles=" + std::to_string(r.ptiles) + " wgs=" + std::to_string(r.wgs) +
+         " passes=" + std::to_string(r.passes) + " phases=" + std::to_string(r.phases) +
+         " items=" + std::to_string(kDiscoItems) + " threads=" + std::to_string(kDiscoThreads) + (bf16 ? " bf16=1" : "");
+}
+
 // ------------------------------------------------------------------ SFNO per-degree channel mixing
 // c [B, Cin, L, M, 2] fp32 (spherical harmonic coefficients, complex as trailing re/im), w [Cin, Cout, L, 2] fp32
 // -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
@@ -1395,6 +1562,10 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
   X(disco, "(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out) -> Tensor")         \
   X(disco_out, "(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out, Tensor(a!) out) " \
                "-> Tensor(a!)")                                                                                       \
+  X(disco_t, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias=None) "     \
+             "-> Tensor")                                                                                             \
+  X(disco_t_out, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias, "      \
+                 "Tensor(a!) out) -> Tensor(a!)")                                                                     \
   X(sfno_mix, "(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor")                                      \
   X(sfno_mix_out, "(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)")
 
@@ -1415,6 +1586,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("disco_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int nnz_max, "
         "bool bf16=False) -> str",
         &amd_dft::disco_info);
+  m.def("disco_t_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int nnz_max, "
+        "bool bf16=False) -> str",
+        &amd_dft::disco_t_info);
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
   m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri, bool bf16=False) -> str",
         &amd_dft::sfno_mix_info);

@@ -473,6 +473,52 @@ inline DiscoRoute disco_route(int64_t planes, int64_t nlat_in, int64_t nlon_in, 
 }
 void launch_disco(const DiscoLaunch& p, void* stream);
 
+// ---- DISCO convolution on the sphere, the transposed (upsampling) half (disco_t.hip): a gather CSR over rows
+// r = k * s + rho (output latitude k, longitude phase rho, s = nlon_out / nlon_in),
+//   y[n, k, s t + rho] = sum_e val[e] * z[n, p_e, k'_e, (d_e + t) mod nlon_in] (+ bias[n mod C]),  0 <= t < nlon_in,
+//   idx[e] = (k'_e * K + p_e) * nlon_in + d_e sorted within a row
+struct DiscoTLaunch {
+  const void* z = nullptr;           // [planes, K, nlat_in, nlon_in] fp32 (bf16 if bf16), element-aligned
+  const int32_t* row_ptr = nullptr;  // [nlat_out * s + 1]
+  const int32_t* idx = nullptr;      // [nnz]
+  const float* val = nullptr;        // [nnz]
+  const float* bias = nullptr;       // [C] or nullptr; plane n takes bias[n mod C]
+  void* y = nullptr;                 // [planes, nlat_out, nlon_out], z's dtype
+  int64_t planes = 0, C = 1;
+  int nlat_in = 0, nlon_in = 0, K = 0, nlat_out = 0, nlon_out = 0;
+  int64_t nnz = 0;
+  int bf16 = 0;
+};
+// The route (host only; launch_disco_t and the disco_t_info op both answer from here): disco_route's rule with an
+// LDS row of all K basis planes of one input latitude, K * nlon_in * 4 bytes.  A workgroup owns one output latitude,
+// all s phases and PT planes; lanes are (plane, t), so a pass covers kDiscoThreads * kDiscoItems of PT * nlon_in.
+struct DiscoTRoute {
+  int pt;          // planes per workgroup: 1 or 4
+  int rows;        // input latitudes per plane in LDS (the chunk), K basis planes each
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t ptiles;  // plane tiles
+  int64_t wgs;     // nlat_out * ptiles
+  int passes;      // ceil(pt * nlon_in / (kDiscoThreads * kDiscoItems)), per phase
+  int phases;      // s
+};
+inline DiscoTRoute disco_t_route(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out,
+                                 int64_t nlon_out, int64_t /*nnz_max*/, bool /*bf16*/) {
+  DiscoTRoute r{};
+  const int64_t row = K * nlon_in * 4;
+  r.pt = (planes >= 4 && 4 * kDiscoMinRows * row <= kDiscoLdsBytes) ? 4 : 1;
+  int64_t rows = kDiscoLdsBytes / (r.pt * row);
+  if (rows < 1) rows = 1;
+  if (rows > nlat_in) rows = nlat_in;
+  r.rows = static_cast<int>(rows);
+  r.lds = r.pt * rows * row;
+  r.ptiles = (planes + r.pt - 1) / r.pt;
+  r.wgs = nlat_out * r.ptiles;
+  r.passes = static_cast<int>((r.pt * nlon_in + kDiscoThreads * kDiscoItems - 1) / (kDiscoThreads * kDiscoItems));
+  r.phases = static_cast<int>(nlon_out / nlon_in);
+  return r;
+}
+void launch_disco_t(const DiscoTLaunch& p, void* stream);
+
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {
   const void* x = nullptr;        // [O, L, C] bf16 (fp32 if f32) stored residual stream

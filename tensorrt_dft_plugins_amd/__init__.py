@@ -13,7 +13,7 @@ from ._loader import (  # noqa: F401
 from .ops.dft import (  # noqa: F401
     contrib_irfft, contrib_rfft, fft, fftn, ifft, ifftn, irfft, irfft2, irfftn, rfft, rfft2, rfftn,
 )
-from .ops.disco import disco, disco_tables  # noqa: F401
+from .ops.disco import disco, disco_tables, disco_transpose, disco_transpose_tables  # noqa: F401
 from .ops.sht import isht, ivsht, sht, vsht  # noqa: F401
 
 __version__ = "1.0.0"

@@ -525,7 +525,8 @@ _AMD_NODE_DENY = frozenset({"wrap_device_ptr", "wrap_host_ptr", "plan_cache_clea
                             # test support, and the ops that write into a caller's tensor
                             "lds_poison", "lds_probe", "lds_poison_info", "afno_mlp_out", "legendre_out", "legendre_vec_out",
                             "sfno_mix_out",
-                            "fno_pointwise_out", "fno_c2r_pw_out", "instance_norm_out", "fno_mix_out", "disco_out"})
+                            "fno_pointwise_out", "fno_c2r_pw_out", "instance_norm_out", "fno_mix_out", "disco_out",
+                            "disco_t_out"})
 
 
 def _amd_node(opname: str):

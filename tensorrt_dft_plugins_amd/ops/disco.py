@@ -23,6 +23,28 @@ do not carry over):
   ``normalize`` divided by A_k' = sum_{p, k, d} Psi[p, k', k, d], so a constant field gives sum_p y_p = 1.
 * convolution: y[b, c, p, k', j'] = sum_{k, d} Psi[p, k', k, d] x[b, c, k, (d + s j') mod nlon_in] (the ``disco``
   op, ``csrc/spectral/disco.hip``), then out[b, o, k', j'] = sum_{c, p} W[o, c, p] y[b, c, p, k', j'] + bias[o].
+
+Transposed (upsampling) convolution (the layout of torch-harmonics' ``DiscreteContinuousConvTransposeS2``, NOT its
+normalisation), same grids of :mod:`.sht`, local coordinates, basis and K:
+
+* grids: input (coarse) ``(nlat_in, nlon_in, grid_in)``, output (fine) ``(nlat_out, nlon_out, grid_out)``;
+  ``nlon_out % nlon_in == 0``, ``s = nlon_out / nlon_in`` (1 allowed); input quadrature weight
+  q'_k' = w'_k' 2 pi / nlon_in.
+* filter: centred on the input point (theta'_k', 2 pi j' / nlon_in), evaluated at the output point
+  (theta_k, 2 pi j / nlon_out): psi_p(r, gamma) of the output point seen from the input point rotated to the pole,
+  the formulas above with the centre at the input point.  Default ``theta_cutoff = (nr + 1) pi / (nlat_in - 1)``:
+  the coarse grid sets the footprint.
+* filter tensor: PsiT[p, k', k, D] = psi_p q'_k' with the output point at longitude 2 pi D / nlon_out relative to
+  the centre, only where psi_p > 0.
+* operator: y[n, k, j] = sum_{p, k', j'} PsiT[p, k', k, (j - s j') mod nlon_out] z[n, p, k', j'] (+ bias).  With
+  ``normalize`` every output point is divided by its own sum A_{k, rho} = sum_{p, k', j'} PsiT, which depends on k
+  and the phase rho = j mod s only: z = 1 gives y = 1 (upsampling preserves constants); a point with A = 0 stays 0.
+* layer: z[b, o, p, k', j'] = sum_c W[o, c, p] x[b, c, k', j'], out[b, o] = disco_t(z)[b, o] + bias[o], W
+  ``[Cout, Cin, K]``.
+* table (``disco_transpose_tables``, the ``disco_t`` op, ``csrc/spectral/disco_t.hip``): a gather CSR over rows
+  r = k s + rho, idx[e] = (k'_e K + p_e) nlon_in + d_e sorted within a row,
+  y[n, k, s t + rho] = sum_{e in row r} val[e] z[n, p_e, k'_e, (d_e + t) mod nlon_in], 0 <= t < nlon_in; the entry of
+  PsiT with D = s m + rho lands in row k s + rho with d = (nlon_in - m) mod nlon_in.
 """
 from __future__ import annotations
 
@@ -35,7 +57,8 @@ import torch
 from .._loader import load_plugins
 from .sht import GRIDS, colatitudes
 
-__all__ = ["disco_tables", "disco_table_holder", "disco", "kernel_size", "default_cutoff"]
+__all__ = ["disco_tables", "disco_table_holder", "disco", "kernel_size", "default_cutoff", "disco_transpose_tables",
+           "disco_csr_transpose", "disco_transpose_table_holder", "disco_transpose"]
 
 KernelShape = Union[int, Sequence[int]]
 
@@ -103,6 +126,12 @@ def disco_tables(in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel_s
     float32 (``dtype=np.float64``: the unrounded values, what the fp64 definition and the CPU op's fp64 form read).
     Raises ``ValueError`` for a grid outside ``GRIDS``, ``nlon_in % nlon_out != 0`` and a bad ``kernel_shape``, and
     ``OverflowError`` where ``nlat_in * nlon_in`` or nnz does not fit int32."""
+    return _filter_csr(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, dtype, True)
+
+
+def _filter_csr(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, dtype, quad: bool):
+    """The filter evaluated at every input point about every output latitude, as ``disco_tables`` returns it.
+    ``quad=False`` (the transposed tables, which weight by the centre's grid): psi_p alone, without q_k."""
     nlat_in, nlon_in = (int(v) for v in in_shape)
     nlat_out, nlon_out = (int(v) for v in out_shape)
     for g in (grid_in, grid_out):
@@ -121,7 +150,7 @@ def disco_tables(in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel_s
         raise ValueError(f"theta_cutoff must be positive, got {cutoff}")
     th_in, w_in = colatitudes(nlat_in, grid_in)
     th_out, _ = colatitudes(nlat_out, grid_out)
-    q = w_in * (2.0 * np.pi / nlon_in)
+    q = w_in * (2.0 * np.pi / nlon_in) if quad else np.ones_like(w_in)
     phi = 2.0 * np.pi * np.arange(nlon_in, dtype=np.float64) / nlon_in
     cphi, sphi = np.cos(phi)[None, :], np.sin(phi)[None, :]
     rows_idx = [[None] * nlat_out for _ in range(K)]
@@ -197,6 +226,144 @@ def disco_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equian
         t = _CACHE[key] = _DiscoTables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize,
                                        device)
     return t
+
+
+def disco_csr_transpose(row_ptr, idx, val, K: int, fine_shape: Tuple[int, int], coarse_shape: Tuple[int, int]):
+    """The exact adjoint of a forward-form table, re-indexed for ``disco_t``: no reweighting, no normalisation.
+
+    In: rows ``p * nlat_coarse + k'``, ``idx = k * nlon_fine + D`` (a ``disco`` table from the fine grid to the coarse
+    one).  Out: ``(row_ptr int32 [nlat_fine * s + 1], idx int32, val)`` over rows ``k * s + rho`` with
+    ``idx = (k' * K + p) * nlon_coarse + d`` sorted within a row: the entry with ``D = s m + rho`` lands in row
+    ``k * s + rho`` with ``d = (nlon_coarse - m) mod nlon_coarse``."""
+    nlat_f, nlon_f = (int(v) for v in fine_shape)
+    nlat_c, nlon_c = (int(v) for v in coarse_shape)
+    K = int(K)
+    if nlat_f < 1 or nlon_f < 1 or nlat_c < 1 or nlon_c < 1 or K < 1 or nlon_f % nlon_c != 0:
+        raise ValueError(f"nlon_fine ({nlon_f}) must be a positive multiple of nlon_coarse ({nlon_c})")
+    if K * nlat_c * nlon_c >= 2 ** 31:
+        raise OverflowError(f"the input {K} x {nlat_c} x {nlon_c} does not fit int32 indices")
+    s = nlon_f // nlon_c
+    if nlat_f * s >= 2 ** 31 - 1:
+        raise OverflowError(f"{nlat_f} x {s} table rows do not fit int32")
+    rp = np.asarray(row_ptr).astype(np.int64)
+    idx = np.asarray(idx).astype(np.int64)
+    val = np.asarray(val)
+    if rp.shape != (K * nlat_c + 1,) or idx.shape != val.shape or idx.ndim != 1:
+        raise ValueError("disco_csr_transpose: row_ptr must be [K * nlat_coarse + 1], idx and val [nnz]")
+    if rp[0] != 0 or rp[-1] != len(idx) or np.any(np.diff(rp) < 0):
+        raise ValueError("disco_csr_transpose: row_ptr must run from 0 to nnz without decreasing")
+    if len(idx) and (idx.min() < 0 or idx.max() >= nlat_f * nlon_f):
+        raise ValueError("disco_csr_transpose: idx outside the fine grid")
+    rows = np.repeat(np.arange(K * nlat_c, dtype=np.int64), np.diff(rp))
+    p, kc = rows // nlat_c, rows % nlat_c
+    k, D = idx // nlon_f, idx % nlon_f
+    m, rho = D // s, D % s
+    new_row = k * s + rho
+    new_idx = (kc * K + p) * nlon_c + (nlon_c - m) % nlon_c
+    order = np.argsort(new_row * (K * nlat_c * nlon_c) + new_idx, kind="stable")
+    out_rp = np.zeros(nlat_f * s + 1, dtype=np.int32)
+    out_rp[1:] = np.cumsum(np.bincount(new_row, minlength=nlat_f * s))
+    return out_rp, new_idx[order].astype(np.int32), val[order]
+
+
+def disco_transpose_tables(in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel_shape: KernelShape,
+                           grid_in: str = "equiangular", grid_out: str = "equiangular",
+                           theta_cutoff: Optional[float] = None, normalize: bool = True, dtype=np.float32):
+    """The transposed (upsampling) filter tensor in the gather CSR ``disco_t`` takes, built in float64 numpy.
+
+    Definition (same grids, local coordinates r, gamma, basis psi_p and K as the forward layer; torch-harmonics'
+    ``DiscreteContinuousConvTransposeS2`` layout, NOT its normalisation): input (coarse) grid ``in_shape``, output
+    (fine) grid ``out_shape``, ``nlon_out % nlon_in == 0``, ``s = nlon_out / nlon_in`` (1 allowed), input quadrature
+    weight q'_k' = w'_k' 2 pi / nlon_in.  The filter is centred on the input point (theta'_k', 2 pi j' / nlon_in) and
+    evaluated at the output point (theta_k, 2 pi j / nlon_out): psi_p(r, gamma) of the output point seen from the
+    input point rotated to the pole (the forward formulas with the centre at the input point); default
+    ``theta_cutoff = (nr + 1) pi / (nlat_in - 1)``, the coarse grid sets the footprint.
+    PsiT[p, k', k, D] = psi_p q'_k' at relative longitude 2 pi D / nlon_out, only where psi_p > 0, and
+
+        y[n, k, j] = sum_{p, k', j'} PsiT[p, k', k, (j - s j') mod nlon_out] z[n, p, k', j'] (+ bias).
+
+    ``normalize``: every output point is divided by its own sum A_{k, rho} = sum_{p, k', j'} PsiT, which depends on
+    k and the phase rho = j mod s only, so z = 1 gives y = 1; a point with A = 0 stays 0.
+
+    Returns ``(row_ptr int32 [nlat_out * s + 1], idx int32 [nnz], val [nnz])`` over rows ``r = k * s + rho``:
+    ``idx = (k' * K + p) * nlon_in + d`` sorted within a row (k'-major: the rows of one output latitude touch one
+    contiguous band of input latitudes with all K basis planes), and
+
+        y[n, k, s t + rho] = sum_{e in row r} val[e] z[n, p_e, k'_e, (d_e + t) mod nlon_in],   0 <= t < nlon_in.
+
+    Raises like :func:`disco_tables`: ``ValueError`` for a grid outside ``GRIDS``, ``nlon_out % nlon_in != 0`` and a
+    bad ``kernel_shape``, ``OverflowError`` where an index does not fit int32, ``TypeError`` for another dtype."""
+    nlat_in, nlon_in = (int(v) for v in in_shape)
+    nlat_out, nlon_out = (int(v) for v in out_shape)
+    for g in (grid_in, grid_out):
+        if g not in GRIDS:
+            raise ValueError(f"grid must be one of {GRIDS}, got {g!r}")
+    if nlat_in < 1 or nlon_in < 1 or nlat_out < 1 or nlon_out < 1 or nlon_out % nlon_in != 0:
+        raise ValueError(f"nlon_out ({nlon_out}) must be a positive multiple of nlon_in ({nlon_in})")
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("disco_transpose_tables: dtype must be np.float32 or np.float64")
+    K = kernel_size(kernel_shape)
+    if K * nlat_in * nlon_in >= 2 ** 31:
+        raise OverflowError(f"the input {K} x {nlat_in} x {nlon_in} does not fit int32 indices")
+    cutoff = float(theta_cutoff) if theta_cutoff is not None else default_cutoff(kernel_shape, nlat_in)
+    # psi_p of every fine point about every coarse point: the forward table from the fine grid to the coarse one
+    # without its quadrature weight, rows p * nlat_in + k'
+    rp, idx, psi = _filter_csr(out_shape, in_shape, kernel_shape, grid_out, grid_in, cutoff, False, np.float64, False)
+    _, w_in = colatitudes(nlat_in, grid_in)
+    kc = np.repeat(np.arange(K * nlat_in, dtype=np.int64) % nlat_in, np.diff(rp.astype(np.int64)))
+    val = psi * (w_in * (2.0 * np.pi / nlon_in))[kc]
+    rp_t, idx_t, val_t = disco_csr_transpose(rp, idx, val, K, out_shape, in_shape)
+    if normalize and len(val_t):
+        rows = np.repeat(np.arange(len(rp_t) - 1, dtype=np.int64), np.diff(rp_t.astype(np.int64)))
+        total = np.bincount(rows, weights=val_t, minlength=len(rp_t) - 1)
+        val_t = val_t / np.where(total > 0.0, total, 1.0)[rows]
+    return rp_t, idx_t, val_t.astype(dtype)
+
+
+class _DiscoTransposeTables:
+    """One transposed filter tensor on one device: ``row_ptr``, ``idx``, ``val`` (fp32) as ``disco_t`` takes them, the
+    host copy of ``row_ptr`` (checked here, on the host: non-decreasing from 0 to nnz, and every idx inside
+    K * nlat_in * nlon_in), and K, s, nnz, ``nnz_max`` (the longest row)."""
+
+    def __init__(self, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
+        rp, idx, val = disco_transpose_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff,
+                                              normalize)
+        self.K = kernel_size(kernel_shape)
+        self.nlat_out, self.nlon_out = int(out_shape[0]), int(out_shape[1])
+        self.s = self.nlon_out // int(in_shape[1])
+        self.nnz = int(idx.shape[0])
+        if rp[0] != 0 or rp[-1] != self.nnz or np.any(np.diff(rp.astype(np.int64)) < 0):
+            raise ValueError("disco_t tables: row_ptr must run from 0 to nnz without decreasing")
+        if self.nnz and (idx.min() < 0 or idx.max() >= self.K * int(in_shape[0]) * int(in_shape[1])):
+            raise ValueError("disco_t tables: idx outside the input grid")
+        self.row_ptr_host = rp
+        self.nnz_max = int(np.diff(rp.astype(np.int64)).max()) if len(rp) > 1 else 0
+        self.row_ptr = torch.from_numpy(rp).to(device)
+        self.idx = torch.from_numpy(idx).to(device)
+        self.val = torch.from_numpy(val).to(device)
+
+
+def disco_transpose_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equiangular",
+                                 grid_out: str = "equiangular", theta_cutoff: Optional[float] = None,
+                                 normalize: bool = True, device="cpu") -> _DiscoTransposeTables:
+    """The transposed tables cached per (grids, basis, cutoff, normalize, device), like ``disco_table_holder``."""
+    nr, nphi = _kernel_shape(kernel_shape)
+    key = ("t", tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape), nr, nphi, grid_in, grid_out,
+           None if theta_cutoff is None else float(theta_cutoff), bool(normalize), str(torch.device(device)))
+    t = _CACHE.get(key)
+    if t is None:
+        t = _CACHE[key] = _DiscoTransposeTables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff,
+                                                normalize, device)
+    return t
+
+
+def disco_transpose(z: torch.Tensor, tables: _DiscoTransposeTables, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``z`` [..., C, K, nlat_in, nlon_in] (fp32 or bf16) -> y [..., C, nlat_out, nlon_out] of the same dtype, plus
+    ``bias`` [C] (fp32): the ``disco_t`` op on a holder's tables (the hand kernel on a GPU, its ATen counterpart on
+    CPU tensors)."""
+    if z.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"disco_transpose: z must be float32 or bfloat16, got {z.dtype}")
+    return _ops().disco_t(z, tables.row_ptr, tables.idx, tables.val, tables.nlat_out, tables.nlon_out, bias)
 
 
 def disco(x: torch.Tensor, tables: _DiscoTables) -> torch.Tensor:
