@@ -312,7 +312,9 @@ __device__ __forceinline__ float row_sum16(float x) {
 // It removes the per-tile workgroup turnaround (launch, prologue DMA latency, epilogue drain) of a
 // grid of one tile per workgroup -- and measured 4-12 % SLOWER (profiles/gemm_persistent_r4.txt: the
 // GEMMs run power-limited, the turnaround gaps were the cheap part), so it stays opt-in
-// (MI_DFT_GEMM_PERSIST=1, bit-exact: tests/test_gemm_variants.py).
+// (MI_DFT_GEMM_PERSIST=1).  Neither it nor the direct epilogue (MI_DFT_GEMM_EPI=direct) has a test: both are read
+// once per process and by tuning builds only, so a test would need a tuning library and a child process per
+// variant; tests/test_gemm_edges_gpu.py pins the default instances only.
 // NT: N % 256 != 0 -- the last feature panel is ragged (N % 64 == 0): its W rows past N are clamped in
 // the DMA, its bias / c1 loads clamped, and the epilogue halves past N store nothing (wave-uniform).
 template <int ACT, bool BIAS, int RES, bool LN, int MODE, bool SPLIT, int OUT, bool STATS = false, bool PERSIST = false,
