@@ -7,9 +7,9 @@
 //   _ipc_alloc      hipMalloc'd buffer (an IPC handle names a whole allocation, so the gather
 //                   buffers cannot come from the caching allocator's sub-blocks)
 //   _ipc_mem_handle / _ipc_open_mem / _ipc_close_mem      hipIpc{Get,Open,Close}MemHandle
-//   _ipc_event_*    inter-process events (hipEventInterprocess): record on the producer's
-//                   stream, hipStreamWaitEvent on the consumer's
-//   _ipc_write_value / _ipc_wait_value   stream-ordered flag words (hipStreamWrite/WaitValue32)
+//   _ipc_write_value / _ipc_wait_value   stream-ordered flag and event words
+//                   (hipStreamWrite/WaitValue32; the runtime's own inter-process events are not
+//                   used: exporting one needs hipHostRegister, which not every machine supports)
 //   _ipc_can_access_peer                 hipDeviceCanAccessPeer (checked for every rank pair first)
 //   _ipc_push       one kernel copying a source to N destination pointers concurrently on
 //                   the current stream (peer stores over xGMI, one link per destination)
@@ -44,7 +44,7 @@ at::Tensor ipc_alloc(int64_t bytes, int64_t device) {
   auto opts = at::TensorOptions().dtype(at::kByte).device(at::Device(at::kCUDA, static_cast<c10::DeviceIndex>(device)));
   // freed only when the last tensor reference goes: IpcAllGather.close() drops it in its second
   // teardown phase, after a barrier that every peer reaches only once it has unmapped this
-  // buffer (hipIpcCloseMemHandle) and released the events it opened -- never while mapped
+  // buffer (hipIpcCloseMemHandle) -- never while mapped
   return at::from_blob(p, {bytes}, [](void* q) { (void)hipFree(q); }, opts);
 }
 
@@ -72,44 +72,6 @@ int64_t ipc_open_mem(const at::Tensor& handle, int64_t device) {
 }
 
 void ipc_close_mem(int64_t ptr) { hip_ok(hipIpcCloseMemHandle(reinterpret_cast<void*>(ptr)), "_ipc_close_mem"); }
-
-int64_t ipc_event_create(int64_t device) {
-  c10::hip::HIPGuard guard(static_cast<c10::DeviceIndex>(device));
-  hipEvent_t ev;
-  hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventInterprocess), "_ipc_event_create");
-  return reinterpret_cast<int64_t>(ev);
-}
-
-at::Tensor ipc_event_handle(int64_t ev) {
-  hipIpcEventHandle_t h;
-  hip_ok(hipIpcGetEventHandle(&h, reinterpret_cast<hipEvent_t>(ev)), "_ipc_event_handle");
-  at::Tensor out = at::empty({HIP_IPC_HANDLE_SIZE}, at::TensorOptions().dtype(at::kByte));
-  std::memcpy(out.data_ptr(), &h, HIP_IPC_HANDLE_SIZE);
-  return out;
-}
-
-int64_t ipc_event_open(const at::Tensor& handle, int64_t device) {
-  TORCH_CHECK(handle.numel() == HIP_IPC_HANDLE_SIZE && handle.scalar_type() == at::kByte,
-              "amd_dft._ipc_event_open: IPC handles are uint8[64]");
-  c10::hip::HIPGuard guard(static_cast<c10::DeviceIndex>(device));
-  hipIpcEventHandle_t h;
-  std::memcpy(&h, handle.contiguous().cpu().data_ptr(), HIP_IPC_HANDLE_SIZE);
-  hipEvent_t ev;
-  hip_ok(hipIpcOpenEventHandle(&ev, h), "_ipc_event_open");
-  return reinterpret_cast<int64_t>(ev);
-}
-
-void ipc_event_record(int64_t ev, int64_t device) {
-  auto st = c10::hip::getCurrentHIPStream(static_cast<c10::DeviceIndex>(device)).stream();
-  hip_ok(hipEventRecord(reinterpret_cast<hipEvent_t>(ev), st), "_ipc_event_record");
-}
-
-void ipc_stream_wait(int64_t ev, int64_t device) {
-  auto st = c10::hip::getCurrentHIPStream(static_cast<c10::DeviceIndex>(device)).stream();
-  hip_ok(hipStreamWaitEvent(st, reinterpret_cast<hipEvent_t>(ev), 0), "_ipc_stream_wait");
-}
-
-void ipc_event_destroy(int64_t ev) { (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(ev)); }
 
 // Whether `device` can map and store into `peer`'s memory (the direct mesh's precondition: every
 // push is a peer store over the xGMI link between the two GPUs).
@@ -171,12 +133,6 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("_ipc_mem_handle(Tensor buf) -> Tensor", &amd_dft::ipc_mem_handle);
   m.def("_ipc_open_mem(Tensor handle, int device) -> int", &amd_dft::ipc_open_mem);
   m.def("_ipc_close_mem(int ptr) -> ()", &amd_dft::ipc_close_mem);
-  m.def("_ipc_event_create(int device) -> int", &amd_dft::ipc_event_create);
-  m.def("_ipc_event_handle(int ev) -> Tensor", &amd_dft::ipc_event_handle);
-  m.def("_ipc_event_open(Tensor handle, int device) -> int", &amd_dft::ipc_event_open);
-  m.def("_ipc_event_record(int ev, int device) -> ()", &amd_dft::ipc_event_record);
-  m.def("_ipc_stream_wait(int ev, int device) -> ()", &amd_dft::ipc_stream_wait);
-  m.def("_ipc_event_destroy(int ev) -> ()", &amd_dft::ipc_event_destroy);
   m.def("_ipc_can_access_peer(int device, int peer) -> bool", &amd_dft::ipc_can_access_peer);
   m.def("_ipc_write_value(int ptr, int value, int device) -> ()", &amd_dft::ipc_write_value);
   m.def("_ipc_wait_value(int ptr, int value, int device) -> ()", &amd_dft::ipc_wait_value);

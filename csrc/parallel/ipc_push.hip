@@ -6,7 +6,7 @@
 // first pass).
 //
 // Visibility: the peer stores go over the fabric into another GPU's memory, and the consumer
-// learns of them from a stream packet (flag write / interprocess event) that the command processor
+// learns of them from a stream packet (the write of a flag or event word) that the command processor
 // runs after this kernel.  Each workgroup therefore ends with a SYSTEM-scope release once all of
 // its waves' stores have completed: every storing wave waits for its stores (vmcnt(0)), the
 // workgroup synchronises, and one lane issues the release fence, which writes back anything the

@@ -27,9 +27,9 @@ host never blocks on a peer (no barriers on the enqueue path).
 ``protocol="events"`` (default) is the round-2 form: inter-process events, whose stream wait
 targets the latest record enqueued so far, so two Gloo host barriers per step ensure the peers'
 records are enqueued first.  It stays the default until the flag protocol has been validated
-across xGMI (gathered contents checked over slot reuse on a multi-GPU node): the event record /
-wait pair is a system-scope release / acquire that the runtime provides, whereas the flag words
-rely on the push kernel's own system-scope release (csrc/parallel/ipc_push.hip).
+across xGMI (gathered contents checked over slot reuse on a multi-GPU node).  On the GPU an event
+is itself a counted word (``HipIpcTransport``), so both protocols rely on the push kernel's own
+system-scope release (csrc/parallel/ipc_push.hip).
 Failure behaviour: with "events" a dead peer surfaces as a Gloo barrier timeout (the process
 group's timeout, ``init_distributed(timeout_s=...)``); with "flags" the host never blocks, so a
 dead peer leaves this rank's STREAM waiting on a flag word that never advances -- the next host
@@ -39,7 +39,7 @@ Contract (both): the gathered buffer of step ``k`` stays valid until the gather 
 ``k + nbuf`` is called, and every read of it must be enqueued (in stream order on the calling
 stream, or joined into it) before that call.
 
-Transports: ``HipIpcTransport`` (GPU: hipMalloc'd buffers, IPC memory/event handles) and
+Transports: ``HipIpcTransport`` (GPU: hipMalloc'd buffers and event words, IPC memory handles) and
 ``ShmTransport`` (CPU: ``/dev/shm``-backed storages).  The CPU transport emulates a GPU stream
 with one worker thread per rank, inter-process events with shared ``(enqueued, completed)``
 counters and flag words as shared int32s written / polled by the workers, so the multi-process
@@ -61,8 +61,21 @@ import torch.distributed as dist
 from .._loader import load_plugins
 
 
+class _HipIpcEvent:
+    """Inter-process event of the GPU transport: ``ptr`` is a device word (in an ``_ipc_alloc``
+    buffer of the recording rank, mapped by the peers) holding the number of records that have
+    completed; ``host`` counts, in host shared memory, the records enqueued so far."""
+
+    def __init__(self, ptr: int, host: "_ShmEvent"):
+        self.ptr = ptr
+        self.host = host
+
+
 class HipIpcTransport:
-    """hipMalloc'd gather buffers shared through IPC memory / event handles."""
+    """hipMalloc'd gather buffers shared through IPC memory handles.  Events are counted device
+    words written and waited for in stream order (``hipStreamWriteValue32`` / ``WaitValue32``),
+    not the runtime's inter-process events: exporting one of those pins host memory the process
+    already owns (``hipHostRegister``), which not every machine supports."""
 
     def __init__(self, device: torch.device):
         load_plugins()
@@ -70,9 +83,8 @@ class HipIpcTransport:
         self.dev = device.index if device.index is not None else torch.cuda.current_device()
         self.ops = torch.ops.amd_dft
         self._opened: List[int] = []         # peers' buffers mapped into this process
-        self._opened_events: List[int] = []  # peers' events opened in this process
-        self._events: List[int] = []         # this rank's own (exported) events
         self._bufs: List[torch.Tensor] = []  # this rank's own (exported) buffers
+        self._files: List[str] = []          # host counters of this rank's own events
 
     def alloc(self, nbytes: int):
         buf = self.ops._ipc_alloc(nbytes, self.dev)
@@ -87,25 +99,28 @@ class HipIpcTransport:
         return p
 
     def new_event(self):
-        ev = self.ops._ipc_event_create(self.dev)
-        self._events.append(ev)
-        return ev, self.ops._ipc_event_handle(ev)
+        word, handle = self.alloc(4)
+        word.zero_()
+        torch.cuda.synchronize(self.device)
+        path = f"/dev/shm/amd_dft_ipc_{os.getpid()}_{uuid.uuid4().hex[:12]}"
+        self._files.append(path)
+        return _HipIpcEvent(word.data_ptr(), _ShmEvent(path, create=True)), (handle, path)
 
     def open_event(self, handle, local_ev, is_self: bool):
         if is_self:
             return local_ev
-        ev = self.ops._ipc_event_open(handle, self.dev)
-        self._opened_events.append(ev)
-        return ev
+        return _HipIpcEvent(self.open(handle[0], None, False), _ShmEvent(handle[1], create=False))
+
+    def record(self, ev: _HipIpcEvent) -> None:
+        ev.host.c[0] += 1
+        self.write_value(ev.ptr, 0, int(ev.host.c[0]))
+
+    def wait(self, ev: _HipIpcEvent) -> None:
+        # the peer's latest record enqueued so far (after the handshake)
+        self.wait_value(ev.ptr, 0, int(ev.host.c[0]))
 
     def push(self, src: torch.Tensor, dst_ptrs: Sequence[int], offset: int) -> None:
         self.ops._ipc_push(src.contiguous(), list(dst_ptrs), offset)
-
-    def record(self, ev) -> None:
-        self.ops._ipc_event_record(ev, self.dev)
-
-    def wait(self, ev) -> None:
-        self.ops._ipc_stream_wait(ev, self.dev)
 
     def write_value(self, flags, idx: int, value: int) -> None:
         self.ops._ipc_write_value(int(flags) + 4 * idx, value, self.dev)
@@ -120,22 +135,23 @@ class HipIpcTransport:
         torch.cuda.current_stream(self.device).synchronize()
 
     def close_imports(self) -> None:
-        """Teardown step 1: unmap every peer buffer and release every peer event this process
-        opened.  Caller guarantees (barrier) that no rank still pushes or waits."""
+        """Teardown step 1: unmap every peer buffer and peer event word this process opened.
+        Caller guarantees (barrier) that no rank still pushes or waits."""
         torch.cuda.synchronize(self.device)
         for p in self._opened:
             self.ops._ipc_close_mem(p)
-        for ev in self._opened_events:
-            self.ops._ipc_event_destroy(ev)
-        self._opened, self._opened_events = [], []
+        self._opened = []
 
     def close_own(self) -> None:
         """Teardown step 2, after a second barrier (every peer has run close_imports, so nobody
-        maps these any more): destroy this rank's exported events and free its buffers."""
-        for ev in self._events:
-            self.ops._ipc_event_destroy(ev)
-        self._events = []
+        maps these any more): free this rank's buffers and event words, drop its host counters."""
         self._bufs = []  # the last references: hipFree through the from_blob deleter
+        for f in self._files:
+            try:
+                os.unlink(f)
+            except OSError:
+                pass
+        self._files = []
 
     def close(self) -> None:
         self.close_imports()

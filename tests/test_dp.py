@@ -207,7 +207,7 @@ def test_ipc_gather_slow_consumer_detects_race_without_release(protocol):
 def test_dp_allgather_gloo_world2_on_one_gpu(backend):
     """Two ranks share the one GPU (Gloo; RCCL refuses duplicate devices): hipGraph replays on
     two output buffers, the gather on the communication stream, event/stream ordering.  ``ipc``:
-    real hipIpc memory + event handles across the two processes, direct pushes."""
+    real hipIpc memory handles (buffers and event words) across the two processes, direct pushes."""
     _run_dp("cuda", backend)
 
 
