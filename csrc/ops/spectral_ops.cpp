@@ -740,15 +740,28 @@ AMD_DFT_OP_FAMILY(legendre_vec, LegendreVec)
 // with float64 val, the unrounded definition (what the fp64 oracle tests compare).  The table is trusted to be what
 // ops.disco.disco_tables builds (the holder checks it on the host); the kernel reads nothing outside x whatever it
 // holds, and the CPU kernel checks every entry.
-void check_disco(const char* op, const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx,
-                 const at::Tensor& val, int64_t K, int64_t nlat_out, int64_t nlon_out) {
+
+// What disco and disco_t ask of the input's dtype and of the table alike; `xn` names the input ("x" or "z").  The
+// checks of the shapes, which differ, follow in check_disco / check_disco_t.
+void check_disco_table(const char* op, const char* xn, const at::Tensor& x, const at::Tensor& row_ptr,
+                       const at::Tensor& idx, const at::Tensor& val) {
   const auto xt = x.scalar_type();
-  TORCH_CHECK(xt == at::kFloat || xt == at::kBFloat16 || (xt == at::kDouble && x.device().is_cpu()), op,
-              ": x must be float32 or bfloat16 (float64 on CPU tensors), got ", xt);
+  TORCH_CHECK(xt == at::kFloat || xt == at::kBFloat16 || (xt == at::kDouble && x.device().is_cpu()), op, ": ", xn,
+              " must be float32 or bfloat16 (float64 on CPU tensors), got ", xt);
   TORCH_CHECK(val.scalar_type() == (xt == at::kDouble ? at::kDouble : at::kFloat), op, ": val must be ",
-              xt == at::kDouble ? "float64 for a float64 x" : "float32", ", got ", val.scalar_type());
+              xt == at::kDouble ? "float64 for a float64 " : "float32", xt == at::kDouble ? xn : "", ", got ",
+              val.scalar_type());
   TORCH_CHECK(row_ptr.scalar_type() == at::kInt && idx.scalar_type() == at::kInt, op,
               ": row_ptr and idx must be int32, got ", row_ptr.scalar_type(), " and ", idx.scalar_type());
+  TORCH_CHECK(idx.dim() == 1 && val.dim() == 1 && idx.size(0) == val.size(0) && idx.size(0) < (int64_t(1) << 31), op,
+              ": idx and val must be [nnz] with nnz < 2^31, got ", idx.sizes(), " and ", val.sizes());
+  TORCH_CHECK(row_ptr.device() == x.device() && idx.device() == x.device() && val.device() == x.device(), op,
+              ": row_ptr, idx and val must be on the device of ", xn);
+}
+
+void check_disco(const char* op, const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx,
+                 const at::Tensor& val, int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  check_disco_table(op, "x", x, row_ptr, idx, val);
   TORCH_CHECK(x.dim() >= 2, op, ": x must be [..., nlat_in, nlon_in], got ", x.sizes());
   TORCH_CHECK(K >= 1 && nlat_out >= 1 && nlon_out >= 1 && K * nlat_out < (int64_t(1) << 31) - 1, op,
               ": K, nlat_out and nlon_out must be >= 1");
@@ -758,10 +771,6 @@ void check_disco(const char* op, const at::Tensor& x, const at::Tensor& row_ptr,
   TORCH_CHECK(nlon_in % nlon_out == 0, op, ": nlon_in (", nlon_in, ") must be a multiple of nlon_out (", nlon_out, ")");
   TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.size(0) == K * nlat_out + 1, op, ": row_ptr must be [K * nlat_out + 1] = [",
               K * nlat_out + 1, "], got ", row_ptr.sizes());
-  TORCH_CHECK(idx.dim() == 1 && val.dim() == 1 && idx.size(0) == val.size(0) && idx.size(0) < (int64_t(1) << 31), op,
-              ": idx and val must be [nnz] with nnz < 2^31, got ", idx.sizes(), " and ", val.sizes());
-  TORCH_CHECK(row_ptr.device() == x.device() && idx.device() == x.device() && val.device() == x.device(), op,
-              ": row_ptr, idx and val must be on the device of x");
 }
 
 std::vector<int64_t> disco_out_shape(const at::Tensor& x, int64_t K, int64_t nlat_out, int64_t nlon_out) {
@@ -809,27 +818,48 @@ at::Tensor disco_ref(const at::Tensor& x, const at::Tensor& row_ptr, const at::T
   return y.to(x.scalar_type());
 }
 
-// the launch path of disco and disco_out (y contiguous, x's dtype)
-void disco_run(const at::Tensor& x_, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val, int64_t K,
-               int64_t nlat_out, int64_t nlon_out, const at::Tensor& y) {
+// the launch path of disco, disco_t and their _out ops (y contiguous, x's dtype).  Transposed: x is z
+// [..., C, K, nlat_in, nlon_in], a plane is its K basis planes, and bias [C] or none is added.
+void disco_launch(bool transposed, const at::Tensor& x_, const at::Tensor& row_ptr, const at::Tensor& idx,
+                  const at::Tensor& val, int64_t K, int64_t nlat_out, int64_t nlon_out,
+                  const c10::optional<at::Tensor>& bias, const at::Tensor& y) {
   if (y.numel() == 0) return;
   at::Tensor x = x_.contiguous();  // element loads: a view at any element offset is read where it is
   at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vl = val.contiguous();
+  at::Tensor bf = f32_or_undef(bias);
   DiscoLaunch p;
+  p.transposed = transposed ? 1 : 0;
   p.x = x.data_ptr();
   p.row_ptr = rp.data_ptr<int32_t>();
   p.idx = ix.data_ptr<int32_t>();
   p.val = vl.data_ptr<float>();
+  p.bias = bf.defined() ? bf.data_ptr<float>() : nullptr;
   p.y = y.data_ptr();
+  p.C = transposed ? x.size(-4) : 1;
+  p.K = static_cast<int>(K);
   p.nlat_in = static_cast<int>(x.size(-2));
   p.nlon_in = static_cast<int>(x.size(-1));
-  p.planes = x.numel() / (x.size(-2) * x.size(-1));
-  p.K = static_cast<int>(K);
+  p.planes = x.numel() / ((transposed ? K : 1) * x.size(-2) * x.size(-1));
   p.nlat_out = static_cast<int>(nlat_out);
   p.nlon_out = static_cast<int>(nlon_out);
   p.nnz = idx.size(0);
   p.bf16 = x.scalar_type() == at::kBFloat16 ? 1 : 0;
   launch_disco(p, current_stream(x));
+}
+
+// the route as disco_info and disco_t_info print it; `phases` appears in the transposed direction only
+std::string disco_route_info(bool transposed, int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K,
+                             int64_t nlat_out, int64_t nlon_out, int64_t nnz_max, bool bf16) {
+  const DiscoRoute r = disco_route(transposed, planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
+  return "PT=" + std::to_string(r.pt) + " rows=" + std::to_string(r.rows) + " lds=" + std::to_string(r.lds) +
+         " ptiles=" + std::to_string(r.ptiles) + " wgs=" + std::to_string(r.wgs) +
+         " passes=" + std::to_string(r.passes) + (transposed ? " phases=" + std::to_string(r.phases) : "") +
+         " items=" + std::to_string(kDiscoItems) + " threads=" + std::to_string(kDiscoThreads) + (bf16 ? " bf16=1" : "");
+}
+
+void disco_run(const at::Tensor& x, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val, int64_t K,
+               int64_t nlat_out, int64_t nlon_out, const at::Tensor& y) {
+  disco_launch(false, x, row_ptr, idx, val, K, nlat_out, nlon_out, c10::nullopt, y);
 }
 
 void check_disco_device(const char* op, const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -869,11 +899,7 @@ std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t
               "amd_dft.disco_info: sizes must be >= 1 and the input grid and nnz_max below 2^31");
   TORCH_CHECK(nlon_in % nlon_out == 0, "amd_dft.disco_info: nlon_in must be a multiple of nlon_out");
   TORCH_CHECK(nlon_in * 4 <= kDiscoLdsBytes, "amd_dft.disco_info: nlon_in must be at most ", kDiscoLdsBytes / 4);
-  const DiscoRoute r = disco_route(planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
-  return "PT=" + std::to_string(r.pt) + " rows=" + std::to_string(r.rows) + " lds=" + std::to_string(r.lds) +
-         " ptiles=" + std::to_string(r.ptiles) + " wgs=" + std::to_string(r.wgs) +
-         " passes=" + std::to_string(r.passes) + " items=" + std::to_string(kDiscoItems) +
-         " threads=" + std::to_string(kDiscoThreads) + (bf16 ? " bf16=1" : "");
+  return disco_route_info(false, planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
 }
 
 // ------------------------------------------------------------------ DISCO convolution on the sphere (transposed half)
@@ -888,12 +914,7 @@ std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t
 void check_disco_t(const char* op, const at::Tensor& z, const at::Tensor& row_ptr, const at::Tensor& idx,
                    const at::Tensor& val, int64_t nlat_out, int64_t nlon_out, const c10::optional<at::Tensor>& bias) {
   const auto zt = z.scalar_type();
-  TORCH_CHECK(zt == at::kFloat || zt == at::kBFloat16 || (zt == at::kDouble && z.device().is_cpu()), op,
-              ": z must be float32 or bfloat16 (float64 on CPU tensors), got ", zt);
-  TORCH_CHECK(val.scalar_type() == (zt == at::kDouble ? at::kDouble : at::kFloat), op, ": val must be ",
-              zt == at::kDouble ? "float64 for a float64 z" : "float32", ", got ", val.scalar_type());
-  TORCH_CHECK(row_ptr.scalar_type() == at::kInt && idx.scalar_type() == at::kInt, op,
-              ": row_ptr and idx must be int32, got ", row_ptr.scalar_type(), " and ", idx.scalar_type());
+  check_disco_table(op, "z", z, row_ptr, idx, val);
   TORCH_CHECK(z.dim() >= 4, op, ": z must be [..., C, K, nlat_in, nlon_in], got ", z.sizes());
   const int64_t C = z.size(-4), K = z.size(-3), nlat_in = z.size(-2), nlon_in = z.size(-1);
   TORCH_CHECK(K >= 1 && nlat_in >= 1 && nlon_in >= 1 && K * nlat_in * nlon_in < (int64_t(1) << 31), op,
@@ -905,10 +926,6 @@ void check_disco_t(const char* op, const at::Tensor& z, const at::Tensor& row_pt
   TORCH_CHECK(nlat_out * s < (int64_t(1) << 31) - 1, op, ": too many table rows");
   TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.size(0) == nlat_out * s + 1, op, ": row_ptr must be [nlat_out * s + 1] = [",
               nlat_out * s + 1, "], got ", row_ptr.sizes());
-  TORCH_CHECK(idx.dim() == 1 && val.dim() == 1 && idx.size(0) == val.size(0) && idx.size(0) < (int64_t(1) << 31), op,
-              ": idx and val must be [nnz] with nnz < 2^31, got ", idx.sizes(), " and ", val.sizes());
-  TORCH_CHECK(row_ptr.device() == z.device() && idx.device() == z.device() && val.device() == z.device(), op,
-              ": row_ptr, idx and val must be on the device of z");
   if (present(bias)) {
     TORCH_CHECK(bias->scalar_type() == (zt == at::kDouble ? at::kDouble : at::kFloat), op, ": bias must be ",
                 zt == at::kDouble ? "float64 for a float64 z" : "float32", ", got ", bias->scalar_type());
@@ -971,30 +988,9 @@ at::Tensor disco_t_ref(const at::Tensor& z, const at::Tensor& row_ptr, const at:
   return y.to(z.scalar_type());
 }
 
-// the launch path of disco_t and disco_t_out (y contiguous, z's dtype)
-void disco_t_run(const at::Tensor& z_, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
+void disco_t_run(const at::Tensor& z, const at::Tensor& row_ptr, const at::Tensor& idx, const at::Tensor& val,
                  int64_t nlat_out, int64_t nlon_out, const c10::optional<at::Tensor>& bias, const at::Tensor& y) {
-  if (y.numel() == 0) return;
-  at::Tensor z = z_.contiguous();  // element loads: a view at any element offset is read where it is
-  at::Tensor rp = row_ptr.contiguous(), ix = idx.contiguous(), vl = val.contiguous();
-  at::Tensor bf = f32_or_undef(bias);
-  DiscoTLaunch p;
-  p.z = z.data_ptr();
-  p.row_ptr = rp.data_ptr<int32_t>();
-  p.idx = ix.data_ptr<int32_t>();
-  p.val = vl.data_ptr<float>();
-  p.bias = bf.defined() ? bf.data_ptr<float>() : nullptr;
-  p.y = y.data_ptr();
-  p.C = z.size(-4);
-  p.K = static_cast<int>(z.size(-3));
-  p.nlat_in = static_cast<int>(z.size(-2));
-  p.nlon_in = static_cast<int>(z.size(-1));
-  p.planes = z.numel() / (z.size(-3) * z.size(-2) * z.size(-1));
-  p.nlat_out = static_cast<int>(nlat_out);
-  p.nlon_out = static_cast<int>(nlon_out);
-  p.nnz = idx.size(0);
-  p.bf16 = z.scalar_type() == at::kBFloat16 ? 1 : 0;
-  launch_disco_t(p, current_stream(z));
+  disco_launch(true, z, row_ptr, idx, val, z.size(-3), nlat_out, nlon_out, bias, y);
 }
 
 void check_disco_t_device(const char* op, const at::Tensor& z, const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -1024,7 +1020,7 @@ struct DiscoT : OpFamily {
 };
 AMD_DFT_OP_FAMILY(disco_t, DiscoT)
 
-// Which instance and grid disco_t runs -- host only, no device; from disco_t_route, which launch_disco_t dispatches
+// Which instance and grid disco_t runs -- host only, no device; from disco_route, which launch_disco dispatches
 // on: "PT=1 rows=7 lds=60480 ptiles=20 wgs=14400 passes=1 phases=2 items=3 threads=256".  As with disco_info the band
 // of an output latitude is in the table, so whether it is walked in chunks is not part of the answer.
 std::string disco_t_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out,
@@ -1036,11 +1032,7 @@ std::string disco_t_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64
   TORCH_CHECK(nlon_out % nlon_in == 0, "amd_dft.disco_t_info: nlon_out must be a multiple of nlon_in");
   TORCH_CHECK(K * nlon_in * 4 <= kDiscoLdsBytes, "amd_dft.disco_t_info: K * nlon_in must be at most ",
               kDiscoLdsBytes / 4);
-  const DiscoTRoute r = disco_t_route(planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
-  return "PT=" + std::to_string(r.pt) + " rows=" + std::to_string(r.rows) + " lds=" + std::to_string(r.lds) +
-         " ptiles=" + std::to_string(r.ptiles) + " wgs=" + std::to_string(r.wgs) +
-         " passes=" + std::to_string(r.passes) + " phases=" + std::to_string(r.phases) +
-         " items=" + std::to_string(kDiscoItems) + " threads=" + std::to_string(kDiscoThreads) + (bf16 ? " bf16=1" : "");
+  return disco_route_info(true, planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
 }
 
 // ------------------------------------------------------------------ SFNO per-degree channel mixing

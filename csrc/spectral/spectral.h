@@ -426,40 +426,52 @@ inline InstanceNormRoute instance_norm_route(int64_t planes, int64_t P, bool bf1
 }
 void launch_instance_norm(const InstanceNormLaunch& p, void* stream);
 
-// ---- Discrete-continuous (DISCO) convolution on the sphere, the gather half (disco.hip):
+// ---- Discrete-continuous (DISCO) convolutions on the sphere, both directions (disco.hip).  Forward, the gather half:
 //   y[n, p, k', j'] = sum_e val[e] * x[n, k_e, (d_e + s j') mod nlon_in],  e over CSR row p * nlat_out + k',
 //   idx[e] = k_e * nlon_in + d_e sorted within a row, s = nlon_in / nlon_out
+// Transposed, the upsampling half: a gather CSR over rows r = k * s + rho (output latitude k, longitude phase rho,
+// s = nlon_out / nlon_in),
+//   y[n, k, s t + rho] = sum_e val[e] * z[n, p_e, k'_e, (d_e + t) mod nlon_in] (+ bias[n mod C]),  0 <= t < nlon_in,
+//   idx[e] = (k'_e * K + p_e) * nlon_in + d_e sorted within a row
 struct DiscoLaunch {
-  const void* x = nullptr;         // [planes, nlat_in, nlon_in] fp32 (bf16 if bf16), element-aligned
-  const int32_t* row_ptr = nullptr;  // [K * nlat_out + 1]
-  const int32_t* idx = nullptr;    // [nnz]
-  const float* val = nullptr;      // [nnz]
-  void* y = nullptr;               // [planes, K, nlat_out, nlon_out], x's dtype
-  int64_t planes = 0;
+  const void* x = nullptr;           // [planes, nlat_in, nlon_in] fp32 (bf16 if bf16), element-aligned;
+                                     // transposed: z [planes, K, nlat_in, nlon_in]
+  const int32_t* row_ptr = nullptr;  // [K * nlat_out + 1]; transposed: [nlat_out * s + 1]
+  const int32_t* idx = nullptr;      // [nnz]
+  const float* val = nullptr;        // [nnz]
+  const float* bias = nullptr;       // transposed only: [C] or nullptr; plane n takes bias[n mod C]
+  void* y = nullptr;                 // [planes, K, nlat_out, nlon_out], x's dtype; transposed: [planes, nlat_out, nlon_out]
+  int64_t planes = 0, C = 1;
   int nlat_in = 0, nlon_in = 0, K = 0, nlat_out = 0, nlon_out = 0;
   int64_t nnz = 0;
   int bf16 = 0;
+  int transposed = 0;
 };
-// The route of a call (host only; launch_disco and the disco_info op both answer from here).  A workgroup of
-// kDiscoThreads owns one output latitude and PT planes and holds `rows` input rows of each as fp32 in LDS.  PT = 4
-// where four planes of at least kDiscoMinRows rows fit kDiscoLdsBytes and there are four planes, else 1.  The band of
-// an output latitude is read from the table by the kernel; where it is taller than `rows` it is walked in chunks.
+// The route of a call (host only; launch_disco and the disco_info / disco_t_info ops answer from here).  A workgroup
+// of kDiscoThreads owns one output latitude and PT planes and holds `rows` LDS rows of each as fp32: an LDS row is one
+// input row, nlon_in * 4 bytes, or in the transposed direction all K basis planes of one input latitude,
+// K * nlon_in * 4 bytes.  PT = 4 where four planes of at least kDiscoMinRows rows fit kDiscoLdsBytes and there are
+// four planes, else 1.  The band of an output latitude is read from the table by the kernel; where it is taller than
+// `rows` it is walked in chunks.  Lanes are (plane, item) with nlon_out items per plane, or nlon_in per phase in the
+// transposed direction, where a workgroup walks all s phases.
 constexpr int kDiscoThreads = 256;
 constexpr int kDiscoItems = 3;                  // outputs per lane and pass
 constexpr int64_t kDiscoLdsBytes = 64 * 1024;   // two workgroups per CU
 constexpr int kDiscoMinRows = 8;
 struct DiscoRoute {
   int pt;          // planes per workgroup: 1 or 4
-  int rows;        // input rows per plane in LDS (the chunk)
+  int rows;        // LDS rows per plane (the chunk, in input latitudes)
   int64_t lds;     // dynamic LDS bytes per workgroup
   int64_t ptiles;  // plane tiles
   int64_t wgs;     // nlat_out * ptiles
-  int passes;      // ceil(pt * nlon_out / (kDiscoThreads * kDiscoItems))
+  int passes;      // ceil(pt * items per plane / (kDiscoThreads * kDiscoItems)), per phase
+  int phases;      // s in the transposed direction, else 1
 };
-inline DiscoRoute disco_route(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t /*K*/, int64_t nlat_out,
-                              int64_t nlon_out, int64_t /*nnz_max*/, bool /*bf16*/) {
+inline DiscoRoute disco_route(bool transposed, int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K,
+                              int64_t nlat_out, int64_t nlon_out, int64_t /*nnz_max*/, bool /*bf16*/) {
   DiscoRoute r{};
-  const int64_t row = nlon_in * 4;
+  const int64_t row = (transposed ? K * nlon_in : nlon_in) * 4;
+  const int64_t items = transposed ? nlon_in : nlon_out;
   r.pt = (planes >= 4 && 4 * kDiscoMinRows * row <= kDiscoLdsBytes) ? 4 : 1;
   int64_t rows = kDiscoLdsBytes / (r.pt * row);
   if (rows < 1) rows = 1;
@@ -468,56 +480,11 @@ inline DiscoRoute disco_route(int64_t planes, int64_t nlat_in, int64_t nlon_in, 
   r.lds = r.pt * rows * row;
   r.ptiles = (planes + r.pt - 1) / r.pt;
   r.wgs = nlat_out * r.ptiles;
-  r.passes = static_cast<int>((r.pt * nlon_out + kDiscoThreads * kDiscoItems - 1) / (kDiscoThreads * kDiscoItems));
+  r.passes = static_cast<int>((r.pt * items + kDiscoThreads * kDiscoItems - 1) / (kDiscoThreads * kDiscoItems));
+  r.phases = static_cast<int>(transposed ? nlon_out / nlon_in : 1);
   return r;
 }
 void launch_disco(const DiscoLaunch& p, void* stream);
-
-// ---- DISCO convolution on the sphere, the transposed (upsampling) half (disco_t.hip): a gather CSR over rows
-// r = k * s + rho (output latitude k, longitude phase rho, s = nlon_out / nlon_in),
-//   y[n, k, s t + rho] = sum_e val[e] * z[n, p_e, k'_e, (d_e + t) mod nlon_in] (+ bias[n mod C]),  0 <= t < nlon_in,
-//   idx[e] = (k'_e * K + p_e) * nlon_in + d_e sorted within a row
-struct DiscoTLaunch {
-  const void* z = nullptr;           // [planes, K, nlat_in, nlon_in] fp32 (bf16 if bf16), element-aligned
-  const int32_t* row_ptr = nullptr;  // [nlat_out * s + 1]
-  const int32_t* idx = nullptr;      // [nnz]
-  const float* val = nullptr;        // [nnz]
-  const float* bias = nullptr;       // [C] or nullptr; plane n takes bias[n mod C]
-  void* y = nullptr;                 // [planes, nlat_out, nlon_out], z's dtype
-  int64_t planes = 0, C = 1;
-  int nlat_in = 0, nlon_in = 0, K = 0, nlat_out = 0, nlon_out = 0;
-  int64_t nnz = 0;
-  int bf16 = 0;
-};
-// The route (host only; launch_disco_t and the disco_t_info op both answer from here): disco_route's rule with an
-// LDS row of all K basis planes of one input latitude, K * nlon_in * 4 bytes.  A workgroup owns one output latitude,
-// all s phases and PT planes; lanes are (plane, t), so a pass covers kDiscoThreads * kDiscoItems of PT * nlon_in.
-struct DiscoTRoute {
-  int pt;          // planes per workgroup: 1 or 4
-  int rows;        // input latitudes per plane in LDS (the chunk), K basis planes each
-  int64_t lds;     // dynamic LDS bytes per workgroup
-  int64_t ptiles;  // plane tiles
-  int64_t wgs;     // nlat_out * ptiles
-  int passes;      // ceil(pt * nlon_in / (kDiscoThreads * kDiscoItems)), per phase
-  int phases;      // s
-};
-inline DiscoTRoute disco_t_route(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out,
-                                 int64_t nlon_out, int64_t /*nnz_max*/, bool /*bf16*/) {
-  DiscoTRoute r{};
-  const int64_t row = K * nlon_in * 4;
-  r.pt = (planes >= 4 && 4 * kDiscoMinRows * row <= kDiscoLdsBytes) ? 4 : 1;
-  int64_t rows = kDiscoLdsBytes / (r.pt * row);
-  if (rows < 1) rows = 1;
-  if (rows > nlat_in) rows = nlat_in;
-  r.rows = static_cast<int>(rows);
-  r.lds = r.pt * rows * row;
-  r.ptiles = (planes + r.pt - 1) / r.pt;
-  r.wgs = nlat_out * r.ptiles;
-  r.passes = static_cast<int>((r.pt * nlon_in + kDiscoThreads * kDiscoItems - 1) / (kDiscoThreads * kDiscoItems));
-  r.phases = static_cast<int>(nlon_out / nlon_in);
-  return r;
-}
-void launch_disco_t(const DiscoTLaunch& p, void* stream);
 
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {

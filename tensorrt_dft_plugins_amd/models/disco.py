@@ -10,7 +10,7 @@ once).
 
 The weight is ``[Cout, Cin, K]``, torch-harmonics' layout but not its normalisation: published weights do not
 carry over.  ``DiscreteContinuousConvTransposeS2`` is the transposed (upsampling) layer, coarse grid -> fine grid:
-one ``fno_pointwise`` at the coarse resolution, then the ``disco_t`` op (``csrc/spectral/disco_t.hip``), which adds
+one ``fno_pointwise`` at the coarse resolution, then the ``disco_t`` op (``csrc/spectral/disco.hip`` too), which adds
 the bias.  Out of scope: ``groups``, other filter bases, autograd.
 """
 from __future__ import annotations
@@ -138,7 +138,7 @@ class DiscreteContinuousConvTransposeS2(nn.Module):
     nlon_out] with ``nlon_out % nlon_in == 0``, fp32 or bf16 on the amd backend.
 
     Backends: ``"amd"``: one ``fno_pointwise`` at the coarse resolution (``Cin -> Cout * K``, no bias), then the
-    ``disco_t`` op, which adds the bias (``csrc/spectral/disco_t.hip`` on a GPU).  ``"torch"``: the definition, a
+    ``disco_t`` op, which adds the bias (``csrc/spectral/disco.hip`` on a GPU).  ``"torch"``: the definition, a
     sparse matrix applied once per input longitude shift in eager torch, in the input's precision (fp64 in, fp64
     out; bf16 computed in fp32 and rounded once).  The weight is ``[Cout, Cin, K]``, torch-harmonics' layout
     (``DiscreteContinuousConvTransposeS2``) but not its normalisation: published weights do not carry over."""

@@ -41,7 +41,7 @@ normalisation), same grids of :mod:`.sht`, local coordinates, basis and K:
   and the phase rho = j mod s only: z = 1 gives y = 1 (upsampling preserves constants); a point with A = 0 stays 0.
 * layer: z[b, o, p, k', j'] = sum_c W[o, c, p] x[b, c, k', j'], out[b, o] = disco_t(z)[b, o] + bias[o], W
   ``[Cout, Cin, K]``.
-* table (``disco_transpose_tables``, the ``disco_t`` op, ``csrc/spectral/disco_t.hip``): a gather CSR over rows
+* table (``disco_transpose_tables``, the ``disco_t`` op, ``csrc/spectral/disco.hip`` too): a gather CSR over rows
   r = k s + rho, idx[e] = (k'_e K + p_e) nlon_in + d_e sorted within a row,
   y[n, k, s t + rho] = sum_{e in row r} val[e] z[n, p_e, k'_e, (d_e + t) mod nlon_in], 0 <= t < nlon_in; the entry of
   PsiT with D = s m + rho lands in row k s + rho with d = (nlon_in - m) mod nlon_in.
@@ -189,20 +189,22 @@ def _filter_csr(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cuto
     return row_ptr, idx, val
 
 
-class _DiscoTables:
+class _Tables:
     """One filter tensor on one device: ``row_ptr``, ``idx``, ``val`` (fp32) as the op takes them, the host copy of
-    ``row_ptr`` (checked here, on the host: non-decreasing from 0 to nnz, and every idx inside the input grid), and
-    K, nnz, ``nnz_max`` (the longest row)."""
+    ``row_ptr`` (checked here, on the host: non-decreasing from 0 to nnz, and every idx inside the input), and
+    K, nnz, ``nnz_max`` (the longest row).  A direction names its ``_build``-er, its ``_op`` for the error texts and
+    whether an idx runs over the ``_basis_planes`` too."""
 
     def __init__(self, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
-        rp, idx, val = disco_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize)
+        rp, idx, val = self._build(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize)
         self.K = kernel_size(kernel_shape)
         self.nlat_out, self.nlon_out = int(out_shape[0]), int(out_shape[1])
         self.nnz = int(idx.shape[0])
         if rp[0] != 0 or rp[-1] != self.nnz or np.any(np.diff(rp.astype(np.int64)) < 0):
-            raise ValueError("disco tables: row_ptr must run from 0 to nnz without decreasing")
-        if self.nnz and (idx.min() < 0 or idx.max() >= int(in_shape[0]) * int(in_shape[1])):
-            raise ValueError("disco tables: idx outside the input grid")
+            raise ValueError(f"{self._op} tables: row_ptr must run from 0 to nnz without decreasing")
+        bound = (self.K if self._basis_planes else 1) * int(in_shape[0]) * int(in_shape[1])
+        if self.nnz and (idx.min() < 0 or idx.max() >= bound):
+            raise ValueError(f"{self._op} tables: idx outside the input grid")
         self.row_ptr_host = rp
         self.nnz_max = int(np.diff(rp.astype(np.int64)).max()) if len(rp) > 1 else 0
         self.row_ptr = torch.from_numpy(rp).to(device)
@@ -210,7 +212,22 @@ class _DiscoTables:
         self.val = torch.from_numpy(val).to(device)
 
 
+class _DiscoTables(_Tables):
+    """The forward filter tensor as ``disco`` takes it: every idx inside the input grid."""
+    _build, _op, _basis_planes = staticmethod(disco_tables), "disco", False
+
+
 _CACHE: dict = {}
+
+
+def _cached(cls, tag, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
+    nr, nphi = _kernel_shape(kernel_shape)
+    key = tag + (tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape), nr, nphi, grid_in, grid_out,
+                 None if theta_cutoff is None else float(theta_cutoff), bool(normalize), str(torch.device(device)))
+    t = _CACHE.get(key)
+    if t is None:
+        t = _CACHE[key] = cls(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device)
+    return t
 
 
 def disco_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equiangular",
@@ -218,14 +235,8 @@ def disco_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equian
                        device="cpu") -> _DiscoTables:
     """The tables cached per (grids, basis, cutoff, normalize, device), in the style of ``sht_tables``: they live as
     long as the process, so a captured hipGraph that reads them stays valid."""
-    nr, nphi = _kernel_shape(kernel_shape)
-    key = (tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape), nr, nphi, grid_in, grid_out,
-           None if theta_cutoff is None else float(theta_cutoff), bool(normalize), str(torch.device(device)))
-    t = _CACHE.get(key)
-    if t is None:
-        t = _CACHE[key] = _DiscoTables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize,
-                                       device)
-    return t
+    return _cached(_DiscoTables, (), in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize,
+                   device)
 
 
 def disco_csr_transpose(row_ptr, idx, val, K: int, fine_shape: Tuple[int, int], coarse_shape: Tuple[int, int]):
@@ -320,41 +331,21 @@ def disco_transpose_tables(in_shape: Tuple[int, int], out_shape: Tuple[int, int]
     return rp_t, idx_t, val_t.astype(dtype)
 
 
-class _DiscoTransposeTables:
-    """One transposed filter tensor on one device: ``row_ptr``, ``idx``, ``val`` (fp32) as ``disco_t`` takes them, the
-    host copy of ``row_ptr`` (checked here, on the host: non-decreasing from 0 to nnz, and every idx inside
-    K * nlat_in * nlon_in), and K, s, nnz, ``nnz_max`` (the longest row)."""
+class _DiscoTransposeTables(_Tables):
+    """The transposed filter tensor as ``disco_t`` takes it: every idx inside K * nlat_in * nlon_in; also s."""
+    _build, _op, _basis_planes = staticmethod(disco_transpose_tables), "disco_t", True
 
-    def __init__(self, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
-        rp, idx, val = disco_transpose_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff,
-                                              normalize)
-        self.K = kernel_size(kernel_shape)
-        self.nlat_out, self.nlon_out = int(out_shape[0]), int(out_shape[1])
+    def __init__(self, in_shape, out_shape, *args):
+        super().__init__(in_shape, out_shape, *args)
         self.s = self.nlon_out // int(in_shape[1])
-        self.nnz = int(idx.shape[0])
-        if rp[0] != 0 or rp[-1] != self.nnz or np.any(np.diff(rp.astype(np.int64)) < 0):
-            raise ValueError("disco_t tables: row_ptr must run from 0 to nnz without decreasing")
-        if self.nnz and (idx.min() < 0 or idx.max() >= self.K * int(in_shape[0]) * int(in_shape[1])):
-            raise ValueError("disco_t tables: idx outside the input grid")
-        self.row_ptr_host = rp
-        self.nnz_max = int(np.diff(rp.astype(np.int64)).max()) if len(rp) > 1 else 0
-        self.row_ptr = torch.from_numpy(rp).to(device)
-        self.idx = torch.from_numpy(idx).to(device)
-        self.val = torch.from_numpy(val).to(device)
 
 
 def disco_transpose_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equiangular",
                                  grid_out: str = "equiangular", theta_cutoff: Optional[float] = None,
                                  normalize: bool = True, device="cpu") -> _DiscoTransposeTables:
     """The transposed tables cached per (grids, basis, cutoff, normalize, device), like ``disco_table_holder``."""
-    nr, nphi = _kernel_shape(kernel_shape)
-    key = ("t", tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape), nr, nphi, grid_in, grid_out,
-           None if theta_cutoff is None else float(theta_cutoff), bool(normalize), str(torch.device(device)))
-    t = _CACHE.get(key)
-    if t is None:
-        t = _CACHE[key] = _DiscoTransposeTables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff,
-                                                normalize, device)
-    return t
+    return _cached(_DiscoTransposeTables, ("t",), in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff,
+                   normalize, device)
 
 
 def disco_transpose(z: torch.Tensor, tables: _DiscoTransposeTables, bias: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -273,6 +273,33 @@ def test_disco_info_on_the_host():
             ops.disco_info(*bad, False)
 
 
+# (planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16) -> the whole string, recorded from the two-kernel
+# tree before disco and disco_t were put on one route: PT = 4 and PT = 1 from each cause (fewer than four planes, a
+# row above 512 words), rows clamped to nlat_in, rows = 1 at the 16384-word limit, passes 1 / 2 / 3, bf16
+ROUTES = [
+    ((20, 720, 1440, 3, 360, 720, 1000, False), "PT=1 rows=11 lds=63360 ptiles=20 wgs=7200 passes=1 items=3 threads=256"),
+    ((64, 180, 360, 9, 180, 360, 1000, True),
+     "PT=4 rows=11 lds=63360 ptiles=16 wgs=2880 passes=2 items=3 threads=256 bf16=1"),
+    ((3, 17, 32, 9, 9, 16, 1000, False), "PT=1 rows=17 lds=2176 ptiles=3 wgs=27 passes=1 items=3 threads=256"),
+    ((5, 17, 32, 9, 9, 16, 1000, False), "PT=4 rows=17 lds=8704 ptiles=2 wgs=18 passes=1 items=3 threads=256"),
+    ((8, 40, 516, 3, 40, 258, 1000, False), "PT=1 rows=31 lds=63984 ptiles=8 wgs=320 passes=1 items=3 threads=256"),
+    ((8, 40, 512, 3, 40, 256, 1000, False), "PT=4 rows=8 lds=65536 ptiles=2 wgs=80 passes=2 items=3 threads=256"),
+    ((8, 40, 512, 3, 40, 256, 1000, True), "PT=4 rows=8 lds=65536 ptiles=2 wgs=80 passes=2 items=3 threads=256 bf16=1"),
+    ((1, 3, 16384, 2, 3, 16384, 1000, False), "PT=1 rows=1 lds=65536 ptiles=1 wgs=3 passes=22 items=3 threads=256"),
+    ((4, 10, 512, 2, 10, 512, 1000, False), "PT=4 rows=8 lds=65536 ptiles=1 wgs=10 passes=3 items=3 threads=256"),
+    ((7, 5, 24, 2, 5, 8, 0, True), "PT=4 rows=5 lds=1920 ptiles=2 wgs=10 passes=1 items=3 threads=256 bf16=1"),
+    ((2, 12, 2048, 2, 12, 1024, 2 ** 31 - 1, False),
+     "PT=1 rows=8 lds=65536 ptiles=2 wgs=24 passes=2 items=3 threads=256"),
+    ((1000, 90, 180, 5, 45, 90, 1000, False),
+     "PT=4 rows=22 lds=63360 ptiles=250 wgs=11250 passes=1 items=3 threads=256"),
+]
+
+
+@pytest.mark.parametrize("args,info", ROUTES, ids=[str(i) for i in range(len(ROUTES))])
+def test_disco_info_pinned(args, info):
+    assert ops.disco_info(*args) == info
+
+
 def test_export_runner_engine(tmp_path):
     ins, outs, ks, gi, go = GRID_CASES[1]
     torch.manual_seed(4)

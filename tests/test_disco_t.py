@@ -332,6 +332,44 @@ def test_disco_t_info_on_the_host():
             ops.disco_t_info(*bad, False)
 
 
+# (planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16) -> the whole string, recorded from the two-kernel
+# tree before disco and disco_t were put on one route: the two benchmarked shapes, PT = 4 and PT = 1 from each cause
+# (fewer than four planes, K * nlon_in above 512 words), rows clamped to nlat_in, rows = 1 at the 16384-word limit,
+# passes 1 / 2 / 3, phases 1 / 2 / 3 / 32, bf16
+ROUTES = [
+    ((20, 360, 720, 3, 720, 1440, 1000, False),
+     "PT=1 rows=7 lds=60480 ptiles=20 wgs=14400 passes=1 phases=2 items=3 threads=256"),
+    ((64, 180, 360, 9, 180, 360, 1000, False),
+     "PT=1 rows=5 lds=64800 ptiles=64 wgs=11520 passes=1 phases=1 items=3 threads=256"),
+    ((64, 180, 360, 9, 180, 360, 1000, True),
+     "PT=1 rows=5 lds=64800 ptiles=64 wgs=11520 passes=1 phases=1 items=3 threads=256 bf16=1"),
+    ((2, 5, 64, 2, 9, 2048, 1000, False),
+     "PT=1 rows=5 lds=2560 ptiles=2 wgs=18 passes=1 phases=32 items=3 threads=256"),
+    ((5, 9, 16, 9, 17, 32, 1000, True),
+     "PT=4 rows=9 lds=20736 ptiles=2 wgs=34 passes=1 phases=2 items=3 threads=256 bf16=1"),
+    ((5, 9, 200, 2, 9, 200, 1000, False),
+     "PT=4 rows=9 lds=57600 ptiles=2 wgs=18 passes=2 phases=1 items=3 threads=256"),
+    ((2, 12, 2048, 2, 12, 2048, 1000, True),
+     "PT=1 rows=4 lds=65536 ptiles=2 wgs=24 passes=3 phases=1 items=3 threads=256 bf16=1"),
+    ((1, 4, 8192, 2, 4, 8192, 1000, False),
+     "PT=1 rows=1 lds=65536 ptiles=1 wgs=4 passes=11 phases=1 items=3 threads=256"),
+    ((8, 6, 12, 2, 12, 36, 1000, False), "PT=4 rows=6 lds=2304 ptiles=2 wgs=24 passes=1 phases=3 items=3 threads=256"),
+    ((4, 20, 256, 2, 20, 512, 1000, False),
+     "PT=4 rows=8 lds=65536 ptiles=1 wgs=20 passes=2 phases=2 items=3 threads=256"),
+    ((4, 20, 258, 2, 20, 516, 1000, False),
+     "PT=1 rows=20 lds=41280 ptiles=4 wgs=80 passes=1 phases=2 items=3 threads=256"),
+    ((3, 20, 256, 2, 20, 512, 0, True),
+     "PT=1 rows=20 lds=40960 ptiles=3 wgs=60 passes=1 phases=2 items=3 threads=256 bf16=1"),
+    ((1000, 45, 90, 5, 90, 180, 2 ** 31 - 1, False),
+     "PT=4 rows=9 lds=64800 ptiles=250 wgs=22500 passes=1 phases=2 items=3 threads=256"),
+]
+
+
+@pytest.mark.parametrize("args,info", ROUTES, ids=[str(i) for i in range(len(ROUTES))])
+def test_disco_t_info_pinned(args, info):
+    assert ops.disco_t_info(*args) == info
+
+
 def test_export_runner_engine_encoder_decoder(tmp_path):
     coarse, fine, ks, gc, gf = GRID_CASES[0]
     torch.manual_seed(4)

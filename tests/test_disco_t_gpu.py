@@ -1,4 +1,4 @@
-"""The ``disco_t`` kernel (csrc/spectral/disco_t.hip) and ``DiscreteContinuousConvTransposeS2`` on the GPU, under
+"""The ``disco_t`` kernel (csrc/spectral/disco.hip) and ``DiscreteContinuousConvTransposeS2`` on the GPU, under
 ``strict_mode`` with no fallback counted.
 
 Kernel cases (planes, in grid -> out grid, basis), each ragged against the instance's tiles:
