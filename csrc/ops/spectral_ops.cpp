@@ -8,6 +8,11 @@
 #include <ATen/core/dispatch/Dispatcher.h>
 #include <torch/library.h>
 
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
 #include "trace.h"
 #include "../spectral/dft_gemm.h"
 #include "../spectral/spectral.h"
@@ -19,8 +24,8 @@ namespace amd_dft {
 namespace {
 
 // The families with an `_out` op (afno_mlp, fno_mix, fno_pointwise, fno_c2r_pw, legendre, legendre_vec, disco,
-// sfno_mix, instance_norm) are described once each, in a struct after their check, reference and launch path;
-// op_family.h makes the six backend forms of the description.
+// attention_s2, sfno_mix, instance_norm) are described once each, in a struct after their check, reference and launch
+// path; op_family.h makes the six backend forms of the description.
 
 // ------------------------------------------------------------------ AFNO spectral filter
 // xw [B, H, KM, C, 2] fp32 (W-direction half spectrum), w1t/w2t [NB, 2BS, 2BS] bf16 ([n][k]),
@@ -1035,6 +1040,162 @@ std::string disco_t_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64
   return disco_route_info(true, planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
 }
 
+// ------------------------------------------------------------------ neighbourhood attention on the sphere
+// q [B, heads * d, nlat_out, nlon_out], k and v [B, heads * d, nlat_in, nlon_in], hw int32 [nlat_out, nlat_in],
+// logw [nlat_in] -> y as q.  The neighbours of output point (k', j') in input row k are the longitudes j with circular
+// |j - s j'| <= hw[k', k], s = nlon_in / nlon_out (hw < 0: none; hw is clamped to nlon_in / 2, the whole row, each
+// longitude once), and
+//   y[b, h, :, k', j'] = sum_{(k, j)} softmax(scale sum_c q[b, h, c, k', j'] k[b, h, c, k, j] + logw[k]) v[b, h, :, k, j];
+// an empty neighbourhood gives 0.  q, k, v all float32 or all bfloat16 with float32 logw; CPU tensors only: all
+// float64 with float32 or float64 logw.  The CPU kernel is the plain definition in fp64, rounded once.
+void check_attention_s2(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                        const at::Tensor& hw, const at::Tensor& logw, int64_t heads, double) {
+  const auto qt = q.scalar_type();
+  TORCH_CHECK(qt == at::kFloat || qt == at::kBFloat16 || (qt == at::kDouble && q.device().is_cpu()), op,
+              ": q must be float32 or bfloat16 (float64 on CPU tensors), got ", qt);
+  TORCH_CHECK(k.scalar_type() == qt && v.scalar_type() == qt, op, ": q, k and v must share one dtype, got ", qt, ", ",
+              k.scalar_type(), " and ", v.scalar_type());
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && k.sizes() == v.sizes() && q.size(0) == k.size(0) &&
+                  q.size(1) == k.size(1),
+              op, ": q must be [B, C, nlat_out, nlon_out] and k, v [B, C, nlat_in, nlon_in], got ", q.sizes(), ", ",
+              k.sizes(), " and ", v.sizes());
+  TORCH_CHECK(heads >= 1 && q.size(1) >= 1 && q.size(1) % heads == 0, op, ": the ", q.size(1),
+              " channels must be a positive multiple of heads = ", heads);
+  const int64_t nlat_in = k.size(2), nlon_in = k.size(3), nlat_out = q.size(2), nlon_out = q.size(3);
+  TORCH_CHECK(nlat_in >= 1 && nlon_in >= 1 && nlat_out >= 1 && nlon_out >= 1 && nlon_in < (1 << 24) &&
+                  nlat_in * nlon_in < (int64_t(1) << 31) && nlat_out * nlat_in < (int64_t(1) << 31),
+              op, ": the grids must be non-empty and hold fewer than 2^31 points");
+  TORCH_CHECK(nlon_in % nlon_out == 0, op, ": nlon_in (", nlon_in, ") must be a multiple of nlon_out (", nlon_out, ")");
+  TORCH_CHECK(hw.scalar_type() == at::kInt && hw.dim() == 2 && hw.size(0) == nlat_out && hw.size(1) == nlat_in, op,
+              ": hw must be int32 [nlat_out, nlat_in] = [", nlat_out, ", ", nlat_in, "], got ", hw.scalar_type(), " ",
+              hw.sizes());
+  TORCH_CHECK((logw.scalar_type() == at::kFloat || (logw.scalar_type() == at::kDouble && qt == at::kDouble)) &&
+                  logw.dim() == 1 && logw.size(0) == nlat_in,
+              op, ": logw must be float32 [nlat_in] (float64 allowed next to float64 q), got ", logw.scalar_type(), " ",
+              logw.sizes());
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device() && hw.device() == q.device() &&
+                  logw.device() == q.device(),
+              op, ": k, v, hw and logw must be on the device of q");
+}
+
+at::Tensor attention_s2_ref(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& hw,
+                            const at::Tensor& logw, int64_t heads, double scale) {
+  const int64_t B = q.size(0), C = q.size(1), d = C / heads, Hi = k.size(2), Wi = k.size(3), Ho = q.size(2),
+                Wo = q.size(3), s = Wi / Wo;
+  const at::Tensor qd = q.to(at::kDouble).contiguous(), kd = k.to(at::kDouble).contiguous(),
+                   vd = v.to(at::kDouble).contiguous(), hc = hw.contiguous(), ld = logw.to(at::kDouble).contiguous();
+  at::Tensor y = at::zeros(q.sizes(), qd.options());
+  const double *qp = qd.data_ptr<double>(), *kp = kd.data_ptr<double>(), *vp = vd.data_ptr<double>(),
+               *lp = ld.data_ptr<double>();
+  const int32_t* hp = hc.data_ptr<int32_t>();
+  double* yp = y.data_ptr<double>();
+  const int64_t pin = Hi * Wi, pout = Ho * Wo;
+  at::parallel_for(0, B * heads * Ho, 1, [&](int64_t b0, int64_t b1) {
+    std::vector<double> sc;
+    std::vector<int64_t> at_;
+    for (int64_t t = b0; t < b1; ++t) {
+      const int64_t bh = t / Ho, ko = t % Ho;
+      const double* qb = qp + bh * d * pout + ko * Wo;
+      const double* kb = kp + bh * d * pin;
+      const double* vb = vp + bh * d * pin;
+      double* yb = yp + bh * d * pout + ko * Wo;
+      for (int64_t jo = 0; jo < Wo; ++jo) {
+        sc.clear();
+        at_.clear();
+        double mx = -std::numeric_limits<double>::infinity();
+        for (int64_t ki = 0; ki < Hi; ++ki) {
+          const int64_t h = std::min<int64_t>(hp[ko * Hi + ki], Wi / 2);
+          if (h < 0) continue;
+          for (int64_t j = 0; j < Wi; ++j) {  // every longitude once
+            int64_t dist = j - s * jo;
+            dist = dist < 0 ? -dist : dist;
+            dist = std::min(dist, Wi - dist);
+            if (dist > h) continue;
+            double sum = 0.0;
+            for (int64_t c = 0; c < d; ++c) sum += qb[c * pout + jo] * kb[c * pin + ki * Wi + j];
+            sc.push_back(scale * sum + lp[ki]);
+            at_.push_back(ki * Wi + j);
+            mx = std::max(mx, sc.back());
+          }
+        }
+        if (sc.empty()) continue;  // an empty neighbourhood: 0
+        double den = 0.0;
+        for (double& e : sc) den += (e = std::exp(e - mx));
+        for (int64_t c = 0; c < d; ++c) {
+          double sum = 0.0;
+          for (size_t e = 0; e < sc.size(); ++e) sum += sc[e] * vb[c * pin + at_[e]];
+          yb[c * pout + jo] = sum / den;
+        }
+      }
+    }
+  });
+  return y.to(q.scalar_type());
+}
+
+void attention_s2_run(const at::Tensor& q_, const at::Tensor& k_, const at::Tensor& v_, const at::Tensor& hw_,
+                      const at::Tensor& logw_, int64_t heads, double scale, const at::Tensor& y) {
+  if (y.numel() == 0) return;
+  const at::Tensor q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous();  // element loads
+  const at::Tensor hw = hw_.contiguous(), logw = logw_.contiguous();
+  AttnS2Launch p;
+  p.q = q.data_ptr();
+  p.k = k.data_ptr();
+  p.v = v.data_ptr();
+  p.hw = hw.data_ptr<int32_t>();
+  p.logw = logw.data_ptr<float>();
+  p.y = y.data_ptr();
+  p.B = q.size(0);
+  p.heads = heads;
+  p.d = q.size(1) / heads;
+  p.nlat_in = static_cast<int>(k.size(2));
+  p.nlon_in = static_cast<int>(k.size(3));
+  p.nlat_out = static_cast<int>(q.size(2));
+  p.nlon_out = static_cast<int>(q.size(3));
+  p.scale = static_cast<float>(scale);
+  p.bf16 = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+  launch_attention_s2(p, current_stream(q));
+}
+
+void check_attention_s2_device(const char* op, const at::Tensor& q, const at::Tensor&, const at::Tensor&,
+                               const at::Tensor&, const at::Tensor&, int64_t heads, double) {
+  TORCH_CHECK(q.size(1) / heads <= kAttnS2MaxD, op, ": the head dimension d = C / heads must be at most ",
+              kAttnS2MaxD, " on the device (the kernel's four output row tiles), got ", q.size(1) / heads);
+}
+
+struct AttentionS2 : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                         const at::Tensor&, int64_t, double);
+  static constexpr const char *name = "attention_s2", *out_name = "attention_s2_out";
+  static constexpr auto& check = check_attention_s2;
+  static constexpr auto& check_device = check_attention_s2_device;
+  static OpResult result(const at::Tensor& q, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                         const at::Tensor&, int64_t, double) {
+    return {q.sizes(), q.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& q, const A&...) {  // element stores
+    return q.element_size();
+  }
+  static constexpr auto& reference = attention_s2_ref;
+  static constexpr auto& run = attention_s2_run;
+};
+AMD_DFT_OP_FAMILY(attention_s2, AttentionS2)
+
+// Which instance and grid attention_s2 runs -- host only, no device; from attention_s2_route, which
+// launch_attention_s2 dispatches on: "DP=64 lds=36864 qtiles=6 wgs=4320 qtile=64 chunk=64 threads=256".
+std::string attention_s2_info(int64_t B, int64_t heads, int64_t d, int64_t nlat_in, int64_t nlon_in,
+                              int64_t nlat_out, int64_t nlon_out, bool bf16) {
+  TORCH_CHECK(B >= 1 && heads >= 1 && nlat_in >= 1 && nlon_in >= 1 && nlat_out >= 1 && nlon_out >= 1,
+              "amd_dft.attention_s2_info: sizes must be >= 1");
+  TORCH_CHECK(d >= 1 && d <= kAttnS2MaxD, "amd_dft.attention_s2_info: the head dimension must be 1 .. ", kAttnS2MaxD);
+  TORCH_CHECK(nlon_in % nlon_out == 0, "amd_dft.attention_s2_info: nlon_in must be a multiple of nlon_out");
+  const AttnS2Route r = attention_s2_route(B, heads, d, nlat_in, nlon_in, nlat_out, nlon_out, bf16);
+  return "DP=" + std::to_string(r.dp) + " lds=" + std::to_string(r.lds) + " qtiles=" + std::to_string(r.qtiles) +
+         " wgs=" + std::to_string(r.wgs) + " qtile=" + std::to_string(kAttnS2QTile) +
+         " chunk=" + std::to_string(kAttnS2Chunk) + " threads=" + std::to_string(kAttnS2Threads) +
+         (bf16 ? " bf16=1" : "");
+}
+
 // ------------------------------------------------------------------ SFNO per-degree channel mixing
 // c [B, Cin, L, M, 2] fp32 (spherical harmonic coefficients, complex as trailing re/im), w [Cin, Cout, L, 2] fp32
 // -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
@@ -1558,6 +1719,9 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
              "-> Tensor")                                                                                             \
   X(disco_t_out, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias, "      \
                  "Tensor(a!) out) -> Tensor(a!)")                                                                     \
+  X(attention_s2, "(Tensor q, Tensor k, Tensor v, Tensor hw, Tensor logw, int heads, float scale) -> Tensor")         \
+  X(attention_s2_out, "(Tensor q, Tensor k, Tensor v, Tensor hw, Tensor logw, int heads, float scale, Tensor(a!) out) " \
+                      "-> Tensor(a!)")                                                                                \
   X(sfno_mix, "(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor")                                      \
   X(sfno_mix_out, "(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)")
 
@@ -1581,6 +1745,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("disco_t_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int nnz_max, "
         "bool bf16=False) -> str",
         &amd_dft::disco_t_info);
+  m.def("attention_s2_info(int B, int heads, int d, int nlat_in, int nlon_in, int nlat_out, int nlon_out, "
+        "bool bf16=False) -> str",
+        &amd_dft::attention_s2_info);
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
   m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri, bool bf16=False) -> str",
         &amd_dft::sfno_mix_info);

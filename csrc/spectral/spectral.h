@@ -486,6 +486,48 @@ inline DiscoRoute disco_route(bool transposed, int64_t planes, int64_t nlat_in, 
 }
 void launch_disco(const DiscoLaunch& p, void* stream);
 
+// ---- Neighbourhood attention on the sphere (attention_s2.hip): quadrature-weighted softmax attention of every
+// output point over the input points within a geodesic cutoff.  The neighbours of output latitude k' in input row k
+// are the longitudes j with circular |j - s j'| <= hw[k', k] (s = nlon_in / nlon_out; hw < 0: none):
+//   y[b, h, :, k', j'] = sum_{(k, j)} softmax(scale q.k + logw[k]) v[b, h, :, k, j]
+struct AttnS2Launch {
+  const void* q = nullptr;        // [B, heads * d, nlat_out, nlon_out] fp32 (bf16 if bf16)
+  const void* k = nullptr;        // [B, heads * d, nlat_in, nlon_in]
+  const void* v = nullptr;        // [B, heads * d, nlat_in, nlon_in]
+  const int32_t* hw = nullptr;    // [nlat_out, nlat_in]; any value: clamped to [-1, nlon_in / 2] by the kernel
+  const float* logw = nullptr;    // [nlat_in]
+  void* y = nullptr;              // [B, heads * d, nlat_out, nlon_out], q's dtype
+  int64_t B = 0, heads = 0, d = 0;
+  int nlat_in = 0, nlon_in = 0, nlat_out = 0, nlon_out = 0;
+  float scale = 1.f;
+  int bf16 = 0;
+};
+// The route of a call (host only; launch_attention_s2 and the attention_s2_info op answer from here).  A workgroup of
+// kAttnS2Threads owns one (b, head, k') and kAttnS2QTile output longitudes, 16 per wave, and walks the keys of an
+// input row in chunks of kAttnS2Chunk longitudes through LDS.  dp: the head dimension padded to the contraction
+// depth of the MFMA (32 or 64); bf16 operands take one LDS plane each, fp32 two (the bf16x3 split).
+constexpr int kAttnS2Threads = 256;
+constexpr int kAttnS2QTile = 64;
+constexpr int kAttnS2Chunk = 64;
+constexpr int kAttnS2MaxD = 64;
+struct AttnS2Route {
+  int dp;          // 32 or 64
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t qtiles;  // query tiles per output row
+  int64_t wgs;     // nlat_out * B * heads * qtiles
+};
+inline AttnS2Route attention_s2_route(int64_t B, int64_t heads, int64_t d, int64_t /*nlat_in*/, int64_t /*nlon_in*/,
+                                      int64_t nlat_out, int64_t nlon_out, bool bf16) {
+  AttnS2Route r{};
+  r.dp = d <= 32 ? 32 : 64;
+  // K [chunk][dp + 8] and V [dp][chunk + 8] bf16, per plane
+  r.lds = (bf16 ? 1 : 2) * 2 * (int64_t(kAttnS2Chunk) * (r.dp + 8) + int64_t(r.dp) * (kAttnS2Chunk + 8));
+  r.qtiles = (nlon_out + kAttnS2QTile - 1) / kAttnS2QTile;
+  r.wgs = nlat_out * B * heads * r.qtiles;
+  return r;
+}
+void launch_attention_s2(const AttnS2Launch& p, void* stream);
+
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {
   const void* x = nullptr;        // [O, L, C] bf16 (fp32 if f32) stored residual stream
