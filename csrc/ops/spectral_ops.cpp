@@ -24,8 +24,8 @@ namespace amd_dft {
 namespace {
 
 // The families with an `_out` op (afno_mlp, fno_mix, fno_pointwise, fno_c2r_pw, legendre, legendre_vec, disco,
-// attention_s2, sfno_mix, instance_norm) are described once each, in a struct after their check, reference and launch
-// path; op_family.h makes the six backend forms of the description.
+// disco_spectral, attention_s2, sfno_mix, instance_norm) are described once each, in a struct after their check,
+// reference and launch path; op_family.h makes the six backend forms of the description.
 
 // ------------------------------------------------------------------ AFNO spectral filter
 // xw [B, H, KM, C, 2] fp32 (W-direction half spectrum), w1t/w2t [NB, 2BS, 2BS] bf16 ([n][k]),
@@ -907,6 +907,172 @@ std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t
   return disco_route_info(false, planes, nlat_in, nlon_in, K, nlat_out, nlon_out, nnz_max, bf16);
 }
 
+// ------------------------------------------------------------------ DISCO convolution, longitude-Fourier route
+// xhat [..., nlat_in, Mi, 2] (the unnormalised R2C of x along longitude, all Mi = nlon_in / 2 + 1 modes), the packed
+// table of ops.disco.disco_spectral_tables [P, G, Mo, 16, KD] and lo int32 [G] -> Yh [..., K, nlat_out, Mo, 2], whose
+// C2R to nlon_out (times 1 / nlon_out) is disco(x):
+//   Yh[n, p, k', m'] = sum_{r < s} sum_{dk < U} (T[g, m', row, 2 j] + i T[g, m', row, 2 j + 1]) Xh[n, lo[g] + dk, mu]
+// with g = k' / R, row = (k' - g R) K + p, j = r U + dk, mu = m' + r nlon_out, Xh[k, mu] = conj(Xh[k, nlon_in - mu])
+// above the stored half spectrum, and band rows at or beyond nlat_in contributing nothing; lo is clamped to
+// [0, nlat_in - 1].  U, the band height the table was packed with, is an argument: KD = ceil32(2 s U) does not
+// determine it.  Precisions: float32 xhat with the two bf16 planes (hi, lo) of the table (P = 2, bf16x3), or
+// bfloat16 xhat with the one plane (P = 1); a mixed call raises.  CPU tensors only: float64 xhat with either bf16
+// form (the planes summed: the reference of the GPU tests) or with a float64 table [1, G, Mo, 16, KD] (the
+// unrounded definition).  Every sum of the CPU kernel is fp64, one rounding to xhat's dtype.
+void check_disco_spectral(const char* op, const at::Tensor& xh, const at::Tensor& table, const at::Tensor& lo, int64_t K,
+                          int64_t U, int64_t nlat_out, int64_t nlon_in, int64_t nlon_out) {
+  const auto xt = xh.scalar_type(), tt = table.scalar_type();
+  TORCH_CHECK(xt == at::kFloat || xt == at::kBFloat16 || (xt == at::kDouble && xh.device().is_cpu()), op,
+              ": xhat must be float32 or bfloat16 (float64 on CPU tensors), got ", xt);
+  TORCH_CHECK(K >= 1 && K <= 16 && U >= 1 && nlat_out >= 1 && nlon_out >= 1 && nlon_in >= 1 && nlon_in % nlon_out == 0 &&
+                  nlon_in < (1 << 28) && nlat_out < (1 << 28),
+              op, ": needs 1 <= K <= 16, U >= 1 and nlon_in a positive multiple of nlon_out, got K = ", K, ", U = ", U,
+              ", nlon_in = ", nlon_in, ", nlon_out = ", nlon_out);
+  TORCH_CHECK(xh.dim() >= 3 && xh.size(-1) == 2 && xh.size(-2) == nlon_in / 2 + 1 && xh.size(-3) >= 1, op,
+              ": xhat must be [..., nlat_in, nlon_in / 2 + 1 = ", nlon_in / 2 + 1, ", 2], got ", xh.sizes());
+  TORCH_CHECK(U <= xh.size(-3) && (nlon_in / nlon_out) * U < (1 << 24), op, ": U must be at most nlat_in");
+  const DiscoSpectralRoute r = disco_spectral_route(1, xh.size(-3), nlon_in, K, nlat_out, nlon_out, U, false);
+  TORCH_CHECK(table.dim() == 5 && table.size(1) == r.G && table.size(2) == r.Mo && table.size(3) == 16 &&
+                  table.size(4) == r.KD,
+              op, ": table must be [planes, ", r.G, ", ", r.Mo, ", 16, ", r.KD, "], got ", table.sizes());
+  const int64_t P = table.size(0);
+  if (xt == at::kDouble) {
+    TORCH_CHECK((tt == at::kDouble && P == 1) || (tt == at::kBFloat16 && (P == 1 || P == 2)), op,
+                ": a float64 xhat takes a float64 table [1, ...] or bfloat16 planes [1 | 2, ...], got ", tt, " ",
+                table.sizes());
+  } else {
+    TORCH_CHECK(tt == at::kBFloat16 && P == (xt == at::kFloat ? 2 : 1), op,
+                ": xhat and table must both be float32 (the table's two bfloat16 planes, hi and lo) or both bfloat16 "
+                "(one plane), got ", xt, " and ", tt, " ", table.sizes());
+  }
+  TORCH_CHECK(lo.scalar_type() == at::kInt && lo.dim() == 1 && lo.size(0) == r.G, op, ": lo must be int32 [", r.G,
+              "], got ", lo.scalar_type(), " ", lo.sizes());
+  TORCH_CHECK(table.device() == xh.device() && lo.device() == xh.device(), op,
+              ": table and lo must be on the device of xhat");
+}
+
+std::vector<int64_t> disco_spectral_out_shape(const at::Tensor& xh, int64_t K, int64_t nlat_out, int64_t nlon_out) {
+  TORCH_CHECK(xh.dim() >= 3, "disco_spectral: xhat must be [..., nlat_in, Mi, 2]");
+  std::vector<int64_t> s(xh.sizes().begin(), xh.sizes().end() - 3);
+  s.insert(s.end(), {K, nlat_out, nlon_out / 2 + 1, 2});
+  return s;
+}
+
+at::Tensor disco_spectral_ref(const at::Tensor& xh, const at::Tensor& table, const at::Tensor& lo, int64_t K, int64_t U,
+                              int64_t nlat_out, int64_t nlon_in, int64_t nlon_out) {
+  const int64_t nlat_in = xh.size(-3), Mi = xh.size(-2);
+  const DiscoSpectralRoute rt = disco_spectral_route(1, nlat_in, nlon_in, K, nlat_out, nlon_out, U, false);
+  const int64_t R = rt.R, G = rt.G, Mo = rt.Mo, KD = rt.KD, s = rt.s;
+  const at::Tensor td = table.to(at::kDouble).sum(0).contiguous();  // hi + lo
+  const at::Tensor xd = xh.to(at::kDouble).contiguous(), lc = lo.contiguous();
+  const int64_t N = xd.numel() / (nlat_in * Mi * 2);
+  at::Tensor y = at::zeros(disco_spectral_out_shape(xh, K, nlat_out, nlon_out), xd.options());
+  const double* tp = td.data_ptr<double>();
+  const double* xp = xd.data_ptr<double>();
+  const int32_t* lp = lc.data_ptr<int32_t>();
+  double* yp = y.data_ptr<double>();
+  at::parallel_for(0, N * G, 1, [&](int64_t b, int64_t e) {
+    for (int64_t t = b; t < e; ++t) {
+      const int64_t n = t / G, g = t % G;
+      const int64_t l0 = std::min<int64_t>(std::max<int64_t>(lp[g], 0), nlat_in - 1);
+      for (int64_t row = 0; row < R * K; ++row) {
+        const int64_t kp = g * R + row / K, p = row % K;
+        if (kp >= nlat_out) break;
+        for (int64_t m = 0; m < Mo; ++m) {
+          const double* tr = tp + ((g * Mo + m) * 16 + row) * KD;
+          double re = 0.0, im = 0.0;
+          for (int64_t r = 0; r < s; ++r) {
+            int64_t mu = m + r * nlon_out;
+            const bool conj = mu >= Mi;
+            if (conj) mu = nlon_in - mu;
+            for (int64_t dk = 0; dk < U && l0 + dk < nlat_in; ++dk) {
+              const double* xv = xp + ((n * nlat_in + l0 + dk) * Mi + mu) * 2;
+              const double xr = xv[0], xi = conj ? -xv[1] : xv[1];
+              const double gr = tr[2 * (r * U + dk)], gi = tr[2 * (r * U + dk) + 1];
+              re += gr * xr - gi * xi;
+              im += gr * xi + gi * xr;
+            }
+          }
+          double* yv = yp + ((((n * K + p) * nlat_out + kp) * Mo) + m) * 2;
+          yv[0] = re;
+          yv[1] = im;
+        }
+      }
+    }
+  });
+  return y.to(xh.scalar_type());
+}
+
+// the launch path of disco_spectral and disco_spectral_out: y is the contiguous result, aligned to one (re, im) pair
+void disco_spectral_run(const at::Tensor& xh_, const at::Tensor& table_, const at::Tensor& lo_, int64_t K, int64_t U,
+                        int64_t nlat_out, int64_t nlon_in, int64_t nlon_out, const at::Tensor& y) {
+  if (y.numel() == 0) return;
+  const bool bf16 = xh_.scalar_type() == at::kBFloat16;
+  // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy; the table's
+  // fragments are 16-byte loads
+  at::Tensor xh = aligned_to(xh_.contiguous(), bf16 ? 4 : 8);
+  at::Tensor table = aligned_to(table_.contiguous(), 16), lo = lo_.contiguous();
+  DiscoSpectralLaunch p;
+  p.x = xh.data_ptr();
+  p.th = reinterpret_cast<const uint16_t*>(table.data_ptr());
+  p.tl = bf16 ? nullptr : p.th + table.numel() / 2;
+  p.lo = lo.data_ptr<int32_t>();
+  p.y = y.data_ptr();
+  p.nlat_in = static_cast<int>(xh.size(-3));
+  p.N = xh.numel() / (xh.size(-3) * xh.size(-2) * 2);
+  p.nlon_in = static_cast<int>(nlon_in);
+  p.K = static_cast<int>(K);
+  p.U = static_cast<int>(U);
+  p.nlat_out = static_cast<int>(nlat_out);
+  p.nlon_out = static_cast<int>(nlon_out);
+  p.bf16 = bf16 ? 1 : 0;
+  launch_disco_spectral(p, current_stream(xh));
+}
+
+void check_disco_spectral_device(const char* op, const at::Tensor& xh, const at::Tensor&, const at::Tensor&, int64_t K,
+                                 int64_t U, int64_t nlat_out, int64_t nlon_in, int64_t nlon_out) {
+  const DiscoSpectralRoute r = disco_spectral_route(1, xh.size(-3), nlon_in, K, nlat_out, nlon_out, U,
+                                                    xh.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(r.ok, op, ": the band of ", r.s, " x ", U, " input rows (KD = ", r.KD, ") needs ", r.lds,
+              " bytes of LDS per workgroup, above ", kDiscoSpecLdsBytes);
+  TORCH_CHECK(xh.size(-3) < (1 << 28), op, ": nlat_in too large");
+}
+
+struct DiscoSpectral : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                         int64_t);
+  static constexpr const char *name = "disco_spectral", *out_name = "disco_spectral_out";
+  static constexpr auto& check = check_disco_spectral;
+  static constexpr auto& check_device = check_disco_spectral_device;
+  static OpResult result(const at::Tensor& xh, const at::Tensor&, const at::Tensor&, int64_t K, int64_t, int64_t nlat_out,
+                         int64_t, int64_t nlon_out) {
+    return {disco_spectral_out_shape(xh, K, nlat_out, nlon_out), xh.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& xh, const A&...) {  // one (re, im) pair
+    return 2 * xh.element_size();
+  }
+  static constexpr auto& reference = disco_spectral_ref;
+  static constexpr auto& run = disco_spectral_run;
+};
+AMD_DFT_OP_FAMILY(disco_spectral, DiscoSpectral)
+
+// The tiling disco_spectral runs -- host only, no device; from disco_spectral_route, which launch_disco_spectral
+// dispatches on: "R=4 KD=96 MT=8 PTL=16 lds=53760 wgs=8280 table_bytes=199618560"
+std::string disco_spectral_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out,
+                                int64_t nlon_out, int64_t U, bool bf16) {
+  TORCH_CHECK(planes >= 1 && nlat_in >= 1 && nlon_in >= 1 && K >= 1 && K <= 16 && nlat_out >= 1 && nlon_out >= 1 &&
+                  U >= 1 && U <= nlat_in && nlon_in < (1 << 28) && nlat_out < (1 << 28) && nlon_in % nlon_out == 0,
+              "amd_dft.disco_spectral_info: sizes must be >= 1, K <= 16, U <= nlat_in and nlon_in a multiple of "
+              "nlon_out");
+  const DiscoSpectralRoute r = disco_spectral_route(planes, nlat_in, nlon_in, K, nlat_out, nlon_out, U, bf16);
+  TORCH_CHECK(r.ok, "amd_dft.disco_spectral_info: the band (KD = ", r.KD, ") needs ", r.lds,
+              " bytes of LDS per workgroup, above ", kDiscoSpecLdsBytes);
+  return "R=" + std::to_string(r.R) + " KD=" + std::to_string(r.KD) + " MT=" + std::to_string(r.mt) +
+         " PTL=" + std::to_string(r.ptl) + " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) +
+         " table_bytes=" + std::to_string(r.table_bytes) + (bf16 ? " bf16=1" : "");
+}
+
 // ------------------------------------------------------------------ DISCO convolution on the sphere (transposed half)
 // z [..., C, K, nlat_in, nlon_in], a gather CSR over rows k * s + rho, s = nlon_out / nlon_in (row_ptr int32
 // [nlat_out * s + 1], idx int32 [nnz] = (k' * K + p) * nlon_in + d sorted within a row, val [nnz]), bias [C] fp32 or
@@ -1715,6 +1881,10 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
   X(disco, "(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out) -> Tensor")         \
   X(disco_out, "(Tensor x, Tensor row_ptr, Tensor idx, Tensor val, int K, int nlat_out, int nlon_out, Tensor(a!) out) " \
                "-> Tensor(a!)")                                                                                       \
+  X(disco_spectral, "(Tensor xhat, Tensor table, Tensor lo, int K, int U, int nlat_out, int nlon_in, int nlon_out) "   \
+                    "-> Tensor")                                                                                      \
+  X(disco_spectral_out, "(Tensor xhat, Tensor table, Tensor lo, int K, int U, int nlat_out, int nlon_in, "            \
+                        "int nlon_out, Tensor(a!) out) -> Tensor(a!)")                                                \
   X(disco_t, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias=None) "     \
              "-> Tensor")                                                                                             \
   X(disco_t_out, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias, "      \
@@ -1745,6 +1915,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("disco_t_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int nnz_max, "
         "bool bf16=False) -> str",
         &amd_dft::disco_t_info);
+  m.def("disco_spectral_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int U, "
+        "bool bf16=False) -> str",
+        &amd_dft::disco_spectral_info);
   m.def("attention_s2_info(int B, int heads, int d, int nlat_in, int nlon_in, int nlat_out, int nlon_out, "
         "bool bf16=False) -> str",
         &amd_dft::attention_s2_info);

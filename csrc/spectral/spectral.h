@@ -486,6 +486,67 @@ inline DiscoRoute disco_route(bool transposed, int64_t planes, int64_t nlat_in, 
 }
 void launch_disco(const DiscoLaunch& p, void* stream);
 
+// ---- DISCO convolution in the longitude-Fourier domain (disco_spectral.hip): after an R2C along longitude every
+// output mode m' is one small banded complex matrix applied along latitude, with the s = nlon_in / nlon_out input
+// modes mu = m' + r nlon_out (r < s) folded onto it:
+//   Yh[n, p, k', m'] = sum_{r < s} sum_{dk < U} (T[.., 2 j] + i T[.., 2 j + 1]) Xh[n, lo[g] + dk, mu],  j = r U + dk,
+// g = k' / R the group of R consecutive output latitudes whose (k' - g R) K + p are the <= 16 rows of one MFMA tile,
+// Xh[k, mu] = conj(Xh[k, nlon_in - mu]) above the stored half spectrum.
+struct DiscoSpectralLaunch {
+  const void* x = nullptr;         // [N, nlat_in, Mi, 2] fp32 (bf16 if bf16), Mi = nlon_in / 2 + 1, pair-aligned
+  const uint16_t* th = nullptr;    // [G, Mo, 16, KD] bf16: the hi plane of the packed table (bf16: the table)
+  const uint16_t* tl = nullptr;    // the lo plane, bf16(T - hi); not read if bf16
+  const int32_t* lo = nullptr;     // [G] first input latitude of a group's band; any value: clamped by the kernel
+  void* y = nullptr;               // [N, K, nlat_out, Mo, 2], x's dtype, pair-aligned
+  int64_t N = 0;
+  int nlat_in = 0, nlon_in = 0, K = 0, U = 0, nlat_out = 0, nlon_out = 0;
+  int bf16 = 0;
+};
+// The route of a call (host only; launch_disco_spectral and the disco_spectral_info op both answer from here).  A
+// workgroup of 256 threads owns one group g, MT consecutive output modes (wave w: modes w, w + 4, ...) and PTL planes
+// (2 PTL real columns), and holds the whole band of its modes in LDS: per precision plane (fp32: hi and lo),
+// mode and plane one row of KD / 2 (re, im) words plus 16 bytes, and kDiscoSpecModePad words after every mode.  The tile starts at 8 modes x 16 planes and
+// shrinks -- first to 8 planes, then to 4 modes -- until the image fits kDiscoSpecLdsBytes; the result tile
+// [16][PTL][2 MT + 2] floats reuses the space.  ok = false: K > 16 (no group fits an MFMA tile) or not even the
+// smallest tile fits.
+constexpr int64_t kDiscoSpecLdsBytes = 64 * 1024;
+constexpr int kDiscoSpecModePad = 8;  // words: the staging stores of 8 modes x 8 words land in 64 different banks
+struct DiscoSpectralRoute {
+  bool ok;
+  int R;           // output latitudes per group: the largest of 8, 4, 2, 1 with R K <= 16
+  int G;           // groups: ceil(nlat_out / R)
+  int s, Mo;       // nlon_in / nlon_out, nlon_out / 2 + 1
+  int KD;          // padded contraction: ceil32(2 s U)
+  int mt, ptl;     // modes and planes per workgroup
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t wgs;     // G * ceil(Mo / mt) * ceil(planes / ptl)
+  int64_t table_bytes;  // all planes of the table
+};
+inline int64_t disco_spectral_lds_bytes(int mt, int ptl, int kd, bool bf16) {
+  const int64_t xs = (bf16 ? 1LL : 2LL) * mt * (ptl * (2 * kd + 16) + 4 * kDiscoSpecModePad);
+  const int64_t ys = 16LL * ptl * (2 * mt + 2) * 4;
+  return xs > ys ? xs : ys;
+}
+inline DiscoSpectralRoute disco_spectral_route(int64_t planes, int64_t /*nlat_in*/, int64_t nlon_in, int64_t K,
+                                               int64_t nlat_out, int64_t nlon_out, int64_t U, bool bf16) {
+  DiscoSpectralRoute r{};
+  r.R = K <= 2 ? 8 : K <= 4 ? 4 : K <= 8 ? 2 : 1;
+  r.G = static_cast<int>((nlat_out + r.R - 1) / r.R);
+  r.s = static_cast<int>(nlon_in / nlon_out);
+  r.Mo = static_cast<int>(nlon_out / 2 + 1);
+  r.KD = static_cast<int>((2 * r.s * U + 31) / 32 * 32);
+  r.mt = 8;
+  r.ptl = 16;
+  if (disco_spectral_lds_bytes(r.mt, r.ptl, r.KD, bf16) > kDiscoSpecLdsBytes) r.ptl = 8;
+  if (disco_spectral_lds_bytes(r.mt, r.ptl, r.KD, bf16) > kDiscoSpecLdsBytes) r.mt = 4;
+  r.lds = disco_spectral_lds_bytes(r.mt, r.ptl, r.KD, bf16);
+  r.ok = K <= 16 && r.lds <= kDiscoSpecLdsBytes;
+  r.wgs = static_cast<int64_t>(r.G) * ((r.Mo + r.mt - 1) / r.mt) * ((planes + r.ptl - 1) / r.ptl);
+  r.table_bytes = (bf16 ? 1LL : 2LL) * r.G * r.Mo * 16 * r.KD * 2;
+  return r;
+}
+void launch_disco_spectral(const DiscoSpectralLaunch& p, void* stream);
+
 // ---- Neighbourhood attention on the sphere (attention_s2.hip): quadrature-weighted softmax attention of every
 // output point over the input points within a geodesic cutoff.  The neighbours of output latitude k' in input row k
 // are the longitudes j with circular |j - s j'| <= hw[k', k] (s = nlon_in / nlon_out; hw < 0: none):

@@ -6,7 +6,9 @@ Backends: ``"amd"`` (the default): the ``disco`` op (``csrc/spectral/disco.hip``
 CPU tensors) followed by one ``fno_pointwise`` over the ``Cin * K`` gathered channels.  ``"torch"``: the definition
 and the numerics oracle, a sparse matrix applied at every output longitude in eager torch -- what a user writes
 without the op; it follows the input's precision (fp64 in, fp64 out; a bf16 input is computed in fp32 and rounded
-once).
+once).  ``algorithm="spectral"`` (opt in; ``"gather"`` is the default) runs the amd backend by the longitude-Fourier
+route instead: ``r2c``, the ``disco_spectral`` op (``csrc/spectral/disco_spectral.hip``), ``c2r``, then the same
+``fno_pointwise``; the torch backend is the same definition either way.
 
 The weight is ``[Cout, Cin, K]``, torch-harmonics' layout but not its normalisation: published weights do not
 carry over.  ``DiscreteContinuousConvTransposeS2`` is the transposed (upsampling) layer, coarse grid -> fine grid:
@@ -33,10 +35,14 @@ class DiscreteContinuousConvS2(nn.Module):
 
     def __init__(self, in_chans: int, out_chans: int, in_shape: Tuple[int, int], out_shape: Tuple[int, int],
                  kernel_shape, bias: bool = True, grid_in: str = "equiangular", grid_out: str = "equiangular",
-                 theta_cutoff: Optional[float] = None, normalize: bool = True, backend: str = "amd"):
+                 theta_cutoff: Optional[float] = None, normalize: bool = True, backend: str = "amd",
+                 algorithm: str = "gather"):
         super().__init__()
         if backend not in ("torch", "amd"):
             raise ValueError(f"backend must be 'torch' or 'amd', got {backend!r}")
+        if algorithm not in ("gather", "spectral"):
+            raise ValueError(f"algorithm must be 'gather' or 'spectral', got {algorithm!r}")
+        self.algorithm = algorithm
         self.in_chans, self.out_chans = int(in_chans), int(out_chans)
         self.in_shape = tuple(int(v) for v in in_shape)
         self.out_shape = tuple(int(v) for v in out_shape)
@@ -71,6 +77,10 @@ class DiscreteContinuousConvS2(nn.Module):
     def tables(self, device) -> "D._DiscoTables":
         return D.disco_table_holder(self.in_shape, self.out_shape, self.kernel_shape, self.grid_in, self.grid_out,
                                     self.theta_cutoff, self.normalize, device)
+
+    def spectral_tables(self, device) -> "D._DiscoSpectralTables":
+        return D.disco_spectral_table_holder(self.in_shape, self.out_shape, self.kernel_shape, self.grid_in,
+                                             self.grid_out, self.theta_cutoff, self.normalize, device)
 
     # ---- torch backend: the definition
     def _psi(self, ref: torch.Tensor) -> torch.Tensor:
@@ -121,7 +131,10 @@ class DiscreteContinuousConvS2(nn.Module):
             raise TypeError(f"DiscreteContinuousConvS2: the amd backend takes float32 or bfloat16, got {x.dtype}")
         B = x.shape[0]
         Ho, Wo = self.out_shape
-        y = D.disco(x, self.tables(x.device))  # [B, Cin, K, Ho, Wo]
+        if self.algorithm == "spectral":
+            y = D.disco_spectral(x, self.spectral_tables(x.device))
+        else:
+            y = D.disco(x, self.tables(x.device))  # [B, Cin, K, Ho, Wo]
         w, b = self._flat_weight()
         return torch.ops.amd_dft.fno_pointwise(None, y.view(B, self.in_chans * self.K, Ho, Wo), w, b, False)
 

@@ -45,6 +45,23 @@ normalisation), same grids of :mod:`.sht`, local coordinates, basis and K:
   r = k s + rho, idx[e] = (k'_e K + p_e) nlon_in + d_e sorted within a row,
   y[n, k, s t + rho] = sum_{e in row r} val[e] z[n, p_e, k'_e, (d_e + t) mod nlon_in], 0 <= t < nlon_in; the entry of
   PsiT with D = s m + rho lands in row k s + rho with d = (nlon_in - m) mod nlon_in.
+
+The longitude-Fourier route of the forward convolution (``disco_spectral``, ``csrc/spectral/disco_spectral.hip``; opt
+in, the gather route above is the default).  Every row is a circular correlation along longitude, so with
+Mi = nlon_in // 2 + 1, Mo = nlon_out // 2 + 1:
+
+* X[k, mu] = sum_j x[k, j] e^{-2 pi i mu j / nlon_in}, the unnormalised ``r2c``, stored for mu < Mi and completed as
+  X[k, mu] = conj(X[k, nlon_in - mu]) above;
+* G[p, k', k, mu] = conj(sum_d Psi[p, k', k, d] e^{-2 pi i mu d / nlon_in}), 0 <= mu < nlon_in (real for an
+  isotropic basis, complex in general);
+* Yh[p, k', m'] = (1 / s) sum_{r < s} sum_k G[p, k', k, m' + r nlon_out] X[k, m' + r nlon_out], 0 <= m' < Mo: the
+  fold of s input modes onto one output mode is the subsampling to the coarse grid;
+* y[p, k', :] = irfft(Yh[p, k', :], n = nlon_out), backward norm.
+
+Packed table (``disco_spectral_tables``): output latitudes in groups of R consecutive k' (R the largest of 8, 4, 2, 1
+with R K <= 16, the last group ragged with zero rows); group g touches the input latitudes lo[g] .. hi[g], U the
+tallest such band; ``T[g, m', row, kappa]`` with row = (k' - g R) K + p < 16 and kappa = 2 (r U + k - lo[g]) + c holding
+Re G / s (c = 0) and Im G / s (c = 1) at mu = m' + r nlon_out, zero-padded to KD = ceil32(2 s U).
 """
 from __future__ import annotations
 
@@ -58,7 +75,8 @@ from .._loader import load_plugins
 from .sht import GRIDS, colatitudes
 
 __all__ = ["disco_tables", "disco_table_holder", "disco", "kernel_size", "default_cutoff", "disco_transpose_tables",
-           "disco_csr_transpose", "disco_transpose_table_holder", "disco_transpose"]
+           "disco_csr_transpose", "disco_transpose_table_holder", "disco_transpose", "disco_spectral_tables",
+           "disco_spectral_table_holder", "disco_spectral", "disco_spectral_group"]
 
 KernelShape = Union[int, Sequence[int]]
 
@@ -237,6 +255,108 @@ def disco_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equian
     long as the process, so a captured hipGraph that reads them stays valid."""
     return _cached(_DiscoTables, (), in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize,
                    device)
+
+
+def disco_spectral_group(K: int) -> int:
+    """R: output latitudes per group of the spectral table, the largest of 8, 4, 2, 1 with R K <= 16."""
+    if not 1 <= int(K) <= 16:
+        raise ValueError(f"the longitude-Fourier route takes 1 <= K <= 16 basis functions, got {K}")
+    return next(r for r in (8, 4, 2, 1) if r * int(K) <= 16)
+
+
+def disco_spectral_tables(in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel_shape: KernelShape,
+                          grid_in: str = "equiangular", grid_out: str = "equiangular",
+                          theta_cutoff: Optional[float] = None, normalize: bool = True, dtype=np.float32):
+    """The packed table of the longitude-Fourier route, built in float64 numpy from the CSR of ``disco_tables``, one
+    group of output latitudes at a time (the dense Psi of the whole grid is never held).
+
+    Returns ``(T [G, Mo, 16, KD] of dtype, lo int32 [G], U)``: the layout of the module docstring.  T carries the
+    1 / s of the fold and nothing else: the remaining factor of the inverse transform, 1 / nlon_out, is the ``scale``
+    argument of the one ``c2r`` call that finishes the job (``disco_spectral``).  A group without entries has
+    lo = 0 and an all-zero table.  Raises like ``disco_tables``, and ``ValueError`` for K > 16."""
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("disco_spectral_tables: dtype must be np.float32 or np.float64")
+    rp, idx, val = disco_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize,
+                                dtype=np.float64)
+    nlat_in, nlon_in = (int(v) for v in in_shape)
+    nlat_out, nlon_out = (int(v) for v in out_shape)
+    K = kernel_size(kernel_shape)
+    R = disco_spectral_group(K)
+    G, s, Mo = -(-nlat_out // R), nlon_in // nlon_out, nlon_out // 2 + 1
+    rp = rp.astype(np.int64)
+    krow, d = idx.astype(np.int64) // nlon_in, idx.astype(np.int64) % nlon_in
+
+    def entries(g):  # (row of the tile, k, d, value) of every entry of group g
+        out = []
+        for kl in range(min(R, nlat_out - g * R)):
+            for p in range(K):
+                a, b = rp[p * nlat_out + g * R + kl], rp[p * nlat_out + g * R + kl + 1]
+                out.append((np.full(b - a, kl * K + p), krow[a:b], d[a:b], val[a:b]))
+        return tuple(np.concatenate(c) for c in zip(*out))
+
+    lo = np.zeros(G, dtype=np.int32)
+    U = 1
+    for g in range(G):
+        _, k, _, _ = entries(g)
+        if len(k):
+            lo[g] = k.min()
+            U = max(U, int(k.max()) - int(k.min()) + 1)
+    KD = -(-2 * s * U // 32) * 32
+    T = np.zeros((G, Mo, 16, KD), dtype=dtype)
+    mu = np.arange(Mo)[None, :] + nlon_out * np.arange(s)[:, None]  # [s, Mo]
+    for g in range(G):
+        row, k, dd, v = entries(g)
+        psi = np.zeros((16, U, nlon_in))
+        psi[row, k - lo[g], dd] = v
+        Gs = np.conj(np.fft.fft(psi, axis=-1))[:, :, mu] / s     # [16, U, s, Mo]
+        Gs = Gs.transpose(3, 0, 2, 1).reshape(Mo, 16, s * U)     # j = r U + dk
+        T[g, :, :, 0:2 * s * U:2] = Gs.real
+        T[g, :, :, 1:2 * s * U:2] = Gs.imag
+    return T, lo, U
+
+
+class _DiscoSpectralTables:
+    """The packed table on one device as ``disco_spectral`` takes it: ``table`` bf16 [2, G, Mo, 16, KD], the fp32
+    values split once, on the host, into the planes hi = bf16(T) and lo = bf16(T - hi) (``table_bf16``: the hi plane
+    alone, [1, G, Mo, 16, KD], what a bf16 call takes), ``lo`` int32 [G], and K, R, U, KD, s, Mo, ``table_bytes``."""
+
+    def __init__(self, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
+        T, lo, U = disco_spectral_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize)
+        self.K = kernel_size(kernel_shape)
+        self.R, self.U, self.KD = disco_spectral_group(self.K), int(U), int(T.shape[-1])
+        self.nlat_out, self.nlon_out = int(out_shape[0]), int(out_shape[1])
+        self.nlon_in = int(in_shape[1])
+        self.s, self.Mo = self.nlon_in // self.nlon_out, self.nlon_out // 2 + 1
+        t32 = torch.from_numpy(T)
+        hi = t32.to(torch.bfloat16)
+        self.table = torch.stack([hi, (t32 - hi.float()).to(torch.bfloat16)]).to(device)
+        self.table_bf16 = self.table[:1]
+        self.table_bytes = self.table.numel() * 2
+        self.lo = torch.from_numpy(lo).to(device)
+
+
+def disco_spectral_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equiangular",
+                                grid_out: str = "equiangular", theta_cutoff: Optional[float] = None,
+                                normalize: bool = True, device="cpu") -> _DiscoSpectralTables:
+    """The spectral tables cached per (grids, basis, cutoff, normalize, device), like ``disco_table_holder``; one
+    table serves every layer on the same grids."""
+    return _cached(_DiscoSpectralTables, ("spectral",), in_shape, out_shape, kernel_shape, grid_in, grid_out,
+                   theta_cutoff, normalize, device)
+
+
+def disco_spectral(x: torch.Tensor, tables: _DiscoSpectralTables) -> torch.Tensor:
+    """``x`` [..., nlat_in, nlon_in] (fp32 or bf16) -> y [..., K, nlat_out, nlon_out] of the same dtype, the shape and
+    meaning of ``disco(x, tables)`` by the longitude-Fourier route: ``r2c`` along longitude (all modes), the
+    ``disco_spectral`` op, ``c2r`` to nlon_out with scale 1 / nlon_out."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"disco_spectral: x must be float32 or bfloat16, got {x.dtype}")
+    if x.dim() < 2 or int(x.shape[-1]) != tables.nlon_in:
+        raise ValueError(f"disco_spectral: x must be [..., nlat_in, {tables.nlon_in}], got {tuple(x.shape)}")
+    ops = _ops()
+    xh = ops.r2c(x, [x.dim() - 1], 1.0, [], x.dtype)  # [..., nlat_in, Mi, 2]
+    table = tables.table_bf16 if x.dtype == torch.bfloat16 else tables.table
+    yh = ops.disco_spectral(xh, table, tables.lo, tables.K, tables.U, tables.nlat_out, tables.nlon_in, tables.nlon_out)
+    return ops.c2r(yh, [yh.dim() - 2], [tables.nlon_out], 1.0 / tables.nlon_out, [], x.dtype)
 
 
 def disco_csr_transpose(row_ptr, idx, val, K: int, fine_shape: Tuple[int, int], coarse_shape: Tuple[int, int]):
