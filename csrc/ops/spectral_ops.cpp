@@ -24,7 +24,7 @@ namespace amd_dft {
 namespace {
 
 // The families with an `_out` op (afno_mlp, fno_mix, fno_pointwise, fno_c2r_pw, legendre, legendre_vec, disco,
-// disco_spectral, attention_s2, sfno_mix, instance_norm) are described once each, in a struct after their check,
+// disco_spectral, disco_spectral_t, attention_s2, sfno_mix, instance_norm) are described once each, in a struct after their check,
 // reference and launch path; op_family.h makes the six backend forms of the description.
 
 // ------------------------------------------------------------------ AFNO spectral filter
@@ -919,11 +919,33 @@ std::string disco_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t
 // bfloat16 xhat with the one plane (P = 1); a mixed call raises.  CPU tensors only: float64 xhat with either bf16
 // form (the planes summed: the reference of the GPU tests) or with a float64 table [1, G, Mo, 16, KD] (the
 // unrounded definition).  Every sum of the CPU kernel is fp64, one rounding to xhat's dtype.
+// What disco_spectral and disco_spectral_t ask of the spectrum's dtype, the packed table and lo alike; `xn` names
+// the spectrum ("xhat" or "zhat"), `r` is the call's route.
+void check_disco_spectral_table(const char* op, const char* xn, const at::Tensor& xh, const at::Tensor& table,
+                                const at::Tensor& lo, const DiscoSpectralRoute& r) {
+  const auto xt = xh.scalar_type(), tt = table.scalar_type();
+  TORCH_CHECK(xt == at::kFloat || xt == at::kBFloat16 || (xt == at::kDouble && xh.device().is_cpu()), op, ": ", xn,
+              " must be float32 or bfloat16 (float64 on CPU tensors), got ", xt);
+  TORCH_CHECK(table.dim() == 5 && table.size(1) == r.G && table.size(2) == r.Mo && table.size(3) == 16 &&
+                  table.size(4) == r.KD,
+              op, ": table must be [planes, ", r.G, ", ", r.Mo, ", 16, ", r.KD, "], got ", table.sizes());
+  const int64_t P = table.size(0);
+  if (xt == at::kDouble) {
+    TORCH_CHECK((tt == at::kDouble && P == 1) || (tt == at::kBFloat16 && (P == 1 || P == 2)), op, ": a float64 ", xn,
+                " takes a float64 table [1, ...] or bfloat16 planes [1 | 2, ...], got ", tt, " ", table.sizes());
+  } else {
+    TORCH_CHECK(tt == at::kBFloat16 && P == (xt == at::kFloat ? 2 : 1), op, ": ", xn,
+                " and table must both be float32 (the table's two bfloat16 planes, hi and lo) or both bfloat16 "
+                "(one plane), got ", xt, " and ", tt, " ", table.sizes());
+  }
+  TORCH_CHECK(lo.scalar_type() == at::kInt && lo.dim() == 1 && lo.size(0) == r.G, op, ": lo must be int32 [", r.G,
+              "], got ", lo.scalar_type(), " ", lo.sizes());
+  TORCH_CHECK(table.device() == xh.device() && lo.device() == xh.device(), op, ": table and lo must be on the device of ",
+              xn);
+}
+
 void check_disco_spectral(const char* op, const at::Tensor& xh, const at::Tensor& table, const at::Tensor& lo, int64_t K,
                           int64_t U, int64_t nlat_out, int64_t nlon_in, int64_t nlon_out) {
-  const auto xt = xh.scalar_type(), tt = table.scalar_type();
-  TORCH_CHECK(xt == at::kFloat || xt == at::kBFloat16 || (xt == at::kDouble && xh.device().is_cpu()), op,
-              ": xhat must be float32 or bfloat16 (float64 on CPU tensors), got ", xt);
   TORCH_CHECK(K >= 1 && K <= 16 && U >= 1 && nlat_out >= 1 && nlon_out >= 1 && nlon_in >= 1 && nlon_in % nlon_out == 0 &&
                   nlon_in < (1 << 28) && nlat_out < (1 << 28),
               op, ": needs 1 <= K <= 16, U >= 1 and nlon_in a positive multiple of nlon_out, got K = ", K, ", U = ", U,
@@ -931,24 +953,8 @@ void check_disco_spectral(const char* op, const at::Tensor& xh, const at::Tensor
   TORCH_CHECK(xh.dim() >= 3 && xh.size(-1) == 2 && xh.size(-2) == nlon_in / 2 + 1 && xh.size(-3) >= 1, op,
               ": xhat must be [..., nlat_in, nlon_in / 2 + 1 = ", nlon_in / 2 + 1, ", 2], got ", xh.sizes());
   TORCH_CHECK(U <= xh.size(-3) && (nlon_in / nlon_out) * U < (1 << 24), op, ": U must be at most nlat_in");
-  const DiscoSpectralRoute r = disco_spectral_route(1, xh.size(-3), nlon_in, K, nlat_out, nlon_out, U, false);
-  TORCH_CHECK(table.dim() == 5 && table.size(1) == r.G && table.size(2) == r.Mo && table.size(3) == 16 &&
-                  table.size(4) == r.KD,
-              op, ": table must be [planes, ", r.G, ", ", r.Mo, ", 16, ", r.KD, "], got ", table.sizes());
-  const int64_t P = table.size(0);
-  if (xt == at::kDouble) {
-    TORCH_CHECK((tt == at::kDouble && P == 1) || (tt == at::kBFloat16 && (P == 1 || P == 2)), op,
-                ": a float64 xhat takes a float64 table [1, ...] or bfloat16 planes [1 | 2, ...], got ", tt, " ",
-                table.sizes());
-  } else {
-    TORCH_CHECK(tt == at::kBFloat16 && P == (xt == at::kFloat ? 2 : 1), op,
-                ": xhat and table must both be float32 (the table's two bfloat16 planes, hi and lo) or both bfloat16 "
-                "(one plane), got ", xt, " and ", tt, " ", table.sizes());
-  }
-  TORCH_CHECK(lo.scalar_type() == at::kInt && lo.dim() == 1 && lo.size(0) == r.G, op, ": lo must be int32 [", r.G,
-              "], got ", lo.scalar_type(), " ", lo.sizes());
-  TORCH_CHECK(table.device() == xh.device() && lo.device() == xh.device(), op,
-              ": table and lo must be on the device of xhat");
+  check_disco_spectral_table(op, "xhat", xh, table, lo,
+                             disco_spectral_route(1, xh.size(-3), nlon_in, K, nlat_out, nlon_out, U, false));
 }
 
 std::vector<int64_t> disco_spectral_out_shape(const at::Tensor& xh, int64_t K, int64_t nlat_out, int64_t nlon_out) {
@@ -1003,23 +1009,30 @@ at::Tensor disco_spectral_ref(const at::Tensor& xh, const at::Tensor& table, con
   return y.to(xh.scalar_type());
 }
 
-// the launch path of disco_spectral and disco_spectral_out: y is the contiguous result, aligned to one (re, im) pair
-void disco_spectral_run(const at::Tensor& xh_, const at::Tensor& table_, const at::Tensor& lo_, int64_t K, int64_t U,
-                        int64_t nlat_out, int64_t nlon_in, int64_t nlon_out, const at::Tensor& y) {
+// the launch path of disco_spectral, disco_spectral_t and their _out ops: y is the contiguous result, aligned to one
+// (re, im) pair.  Transposed: xh is zhat [..., C, K, nlat_in, Mi, 2], a plane is its K basis planes, and bias [C] or
+// none is added.
+void disco_spectral_launch(bool transposed, const at::Tensor& xh_, const at::Tensor& table_, const at::Tensor& lo_,
+                           int64_t K, int64_t U, int64_t nlat_out, int64_t nlon_in, int64_t nlon_out,
+                           const c10::optional<at::Tensor>& bias, const at::Tensor& y) {
   if (y.numel() == 0) return;
   const bool bf16 = xh_.scalar_type() == at::kBFloat16;
   // one load per mode's (re, im), 8 bytes (bf16: 4): a view at an odd element offset gets its own copy; the table's
   // fragments are 16-byte loads
   at::Tensor xh = aligned_to(xh_.contiguous(), bf16 ? 4 : 8);
   at::Tensor table = aligned_to(table_.contiguous(), 16), lo = lo_.contiguous();
+  at::Tensor bf = f32_or_undef(bias);
   DiscoSpectralLaunch p;
+  p.transposed = transposed ? 1 : 0;
+  p.bias = bf.defined() ? bf.data_ptr<float>() : nullptr;
+  p.C = transposed ? xh.size(-5) : 1;
   p.x = xh.data_ptr();
   p.th = reinterpret_cast<const uint16_t*>(table.data_ptr());
   p.tl = bf16 ? nullptr : p.th + table.numel() / 2;
   p.lo = lo.data_ptr<int32_t>();
   p.y = y.data_ptr();
   p.nlat_in = static_cast<int>(xh.size(-3));
-  p.N = xh.numel() / (xh.size(-3) * xh.size(-2) * 2);
+  p.N = xh.numel() / ((transposed ? K : 1) * xh.size(-3) * xh.size(-2) * 2);
   p.nlon_in = static_cast<int>(nlon_in);
   p.K = static_cast<int>(K);
   p.U = static_cast<int>(U);
@@ -1027,6 +1040,11 @@ void disco_spectral_run(const at::Tensor& xh_, const at::Tensor& table_, const a
   p.nlon_out = static_cast<int>(nlon_out);
   p.bf16 = bf16 ? 1 : 0;
   launch_disco_spectral(p, current_stream(xh));
+}
+
+void disco_spectral_run(const at::Tensor& xh, const at::Tensor& table, const at::Tensor& lo, int64_t K, int64_t U,
+                        int64_t nlat_out, int64_t nlon_in, int64_t nlon_out, const at::Tensor& y) {
+  disco_spectral_launch(false, xh, table, lo, K, U, nlat_out, nlon_in, nlon_out, c10::nullopt, y);
 }
 
 void check_disco_spectral_device(const char* op, const at::Tensor& xh, const at::Tensor&, const at::Tensor&, int64_t K,
@@ -1071,6 +1089,141 @@ std::string disco_spectral_info(int64_t planes, int64_t nlat_in, int64_t nlon_in
   return "R=" + std::to_string(r.R) + " KD=" + std::to_string(r.KD) + " MT=" + std::to_string(r.mt) +
          " PTL=" + std::to_string(r.ptl) + " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs) +
          " table_bytes=" + std::to_string(r.table_bytes) + (bf16 ? " bf16=1" : "");
+}
+
+// ------------------------------------------------------------------ transposed DISCO, longitude-Fourier route
+// zhat [..., C, K, nlat_in, Mi, 2] (the unnormalised R2C of z along longitude on the coarse grid, all
+// Mi = nlon_in / 2 + 1 modes), the packed table of ops.disco.disco_spectral_transpose_tables [P, G, Mo, 16, KD], lo
+// int32 [G] and bias [C] fp32 or none -> Yh [..., C, nlat_out, Mo, 2], whose C2R to nlon_out (times 1 / nlon_out) is
+// disco_t(z, bias):
+//   Yh[n, k, mu] = sum_{p < K} sum_{dk < U} (T[g, mu, k - 16 g, 2 j] + i T[.., 2 j + 1]) Zh[n, p, lo[g] + dk, nu]
+//                  (+ nlon_out bias[n mod C] at mu = 0, real part: the spectrum of the constant field)
+// with g = k / 16, j = p U + dk, nu = mu mod nlon_in, Zh[k', nu] = conj(Zh[k', nlon_in - nu]) above the stored half
+// spectrum, band rows at or beyond nlat_in contributing nothing and lo clamped to [0, nlat_in - 1].  Any K >= 1 and
+// any KD = ceil32(2 K U): the kernel walks the contraction in chunks.  Precisions as disco_spectral; a float64 zhat
+// (CPU tensors) takes a float32 or float64 bias.
+void check_disco_spectral_t(const char* op, const at::Tensor& zh, const at::Tensor& table, const at::Tensor& lo, int64_t K,
+                            int64_t U, int64_t nlat_out, int64_t nlon_in, int64_t nlon_out,
+                            const c10::optional<at::Tensor>& bias) {
+  TORCH_CHECK(K >= 1 && U >= 1 && nlat_out >= 1 && nlon_out >= 1 && nlon_in >= 1 && nlon_out % nlon_in == 0 &&
+                  nlon_out < (1 << 28) && nlat_out < (1 << 28) && K * U < (1 << 24),
+              op, ": needs K >= 1, U >= 1 and nlon_out a positive multiple of nlon_in, got K = ", K, ", U = ", U,
+              ", nlon_in = ", nlon_in, ", nlon_out = ", nlon_out);
+  TORCH_CHECK(zh.dim() >= 5 && zh.size(-1) == 2 && zh.size(-2) == nlon_in / 2 + 1 && zh.size(-3) >= 1 &&
+                  zh.size(-4) == K && zh.size(-5) >= 1,
+              op, ": zhat must be [..., C, K = ", K, ", nlat_in, nlon_in / 2 + 1 = ", nlon_in / 2 + 1, ", 2], got ",
+              zh.sizes());
+  TORCH_CHECK(U <= zh.size(-3), op, ": U must be at most nlat_in");
+  check_disco_spectral_table(op, "zhat", zh, table, lo,
+                             disco_spectral_t_route(1, zh.size(-3), nlon_in, K, nlat_out, nlon_out, U, false));
+  if (present(bias)) {
+    const auto bt = bias->scalar_type();
+    TORCH_CHECK(bt == at::kFloat || (bt == at::kDouble && zh.scalar_type() == at::kDouble), op,
+                ": bias must be float32 (or float64 for a float64 zhat), got ", bt);
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == zh.size(-5), op, ": bias must be [C] = [", zh.size(-5), "], got ",
+                bias->sizes());
+    TORCH_CHECK(bias->device() == zh.device(), op, ": bias must be on the device of zhat");
+  }
+}
+
+std::vector<int64_t> disco_spectral_t_out_shape(const at::Tensor& zh, int64_t nlat_out, int64_t nlon_out) {
+  TORCH_CHECK(zh.dim() >= 5, "disco_spectral_t: zhat must be [..., C, K, nlat_in, Mi, 2]");
+  std::vector<int64_t> s(zh.sizes().begin(), zh.sizes().end() - 4);
+  s.insert(s.end(), {nlat_out, nlon_out / 2 + 1, 2});
+  return s;
+}
+
+at::Tensor disco_spectral_t_ref(const at::Tensor& zh, const at::Tensor& table, const at::Tensor& lo, int64_t K, int64_t U,
+                                int64_t nlat_out, int64_t nlon_in, int64_t nlon_out,
+                                const c10::optional<at::Tensor>& bias) {
+  const int64_t C = zh.size(-5), nlat_in = zh.size(-3), Mi = zh.size(-2);
+  const DiscoSpectralRoute rt = disco_spectral_t_route(1, nlat_in, nlon_in, K, nlat_out, nlon_out, U, false);
+  const int64_t G = rt.G, Mo = rt.Mo, KD = rt.KD;
+  const at::Tensor td = table.to(at::kDouble).sum(0).contiguous();  // hi + lo
+  const at::Tensor zd = zh.to(at::kDouble).contiguous(), lc = lo.contiguous();
+  const int64_t N = zd.numel() / (K * nlat_in * Mi * 2);
+  at::Tensor bd;
+  if (present(bias)) bd = bias->to(at::kDouble).contiguous();
+  const double* bp = bd.defined() ? bd.data_ptr<double>() : nullptr;
+  at::Tensor y = at::zeros(disco_spectral_t_out_shape(zh, nlat_out, nlon_out), zd.options());
+  const double* tp = td.data_ptr<double>();
+  const double* zp = zd.data_ptr<double>();
+  const int32_t* lp = lc.data_ptr<int32_t>();
+  double* yp = y.data_ptr<double>();
+  at::parallel_for(0, N * nlat_out, 1, [&](int64_t b, int64_t e) {
+    for (int64_t t = b; t < e; ++t) {
+      const int64_t n = t / nlat_out, k = t % nlat_out, g = k / 16;
+      const int64_t l0 = std::min<int64_t>(std::max<int64_t>(lp[g], 0), nlat_in - 1);
+      for (int64_t m = 0; m < Mo; ++m) {
+        const double* tr = tp + ((g * Mo + m) * 16 + (k - 16 * g)) * KD;
+        int64_t nu = m % nlon_in;
+        const bool conj = nu >= Mi;
+        if (conj) nu = nlon_in - nu;
+        double re = 0.0, im = 0.0;
+        for (int64_t p = 0; p < K; ++p)
+          for (int64_t dk = 0; dk < U && l0 + dk < nlat_in; ++dk) {
+            const double* zv = zp + (((n * K + p) * nlat_in + l0 + dk) * Mi + nu) * 2;
+            const double zr = zv[0], zi = conj ? -zv[1] : zv[1];
+            const double hr = tr[2 * (p * U + dk)], hi = tr[2 * (p * U + dk) + 1];
+            re += hr * zr - hi * zi;
+            im += hr * zi + hi * zr;
+          }
+        if (bp && m == 0) re += static_cast<double>(nlon_out) * bp[n % C];
+        double* yv = yp + (t * Mo + m) * 2;
+        yv[0] = re;
+        yv[1] = im;
+      }
+    }
+  });
+  return y.to(zh.scalar_type());
+}
+
+void disco_spectral_t_run(const at::Tensor& zh, const at::Tensor& table, const at::Tensor& lo, int64_t K, int64_t U,
+                          int64_t nlat_out, int64_t nlon_in, int64_t nlon_out, const c10::optional<at::Tensor>& bias,
+                          const at::Tensor& y) {
+  disco_spectral_launch(true, zh, table, lo, K, U, nlat_out, nlon_in, nlon_out, bias, y);
+}
+
+// no KD or K limit in this direction: only the grid dimensions can overflow
+void check_disco_spectral_t_device(const char* op, const at::Tensor& zh, const at::Tensor&, const at::Tensor&, int64_t K,
+                                   int64_t, int64_t nlat_out, int64_t, int64_t,
+                                   const c10::optional<at::Tensor>&) {
+  const int64_t planes = zh.numel() / (K * zh.size(-3) * zh.size(-2) * 2);
+  TORCH_CHECK((nlat_out + 15) / 16 <= 65535 && (planes + 15) / 16 <= 65535 && zh.size(-3) < (1 << 28), op,
+              ": tensor too large (at most 65535 groups of 16 output latitudes and of 16 planes)");
+}
+
+struct DiscoSpectralT : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                         int64_t, const c10::optional<at::Tensor>&);
+  static constexpr const char *name = "disco_spectral_t", *out_name = "disco_spectral_t_out";
+  static constexpr auto& check = check_disco_spectral_t;
+  static constexpr auto& check_device = check_disco_spectral_t_device;
+  static OpResult result(const at::Tensor& zh, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t nlat_out,
+                         int64_t, int64_t nlon_out, const c10::optional<at::Tensor>&) {
+    return {disco_spectral_t_out_shape(zh, nlat_out, nlon_out), zh.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& zh, const A&...) {  // one (re, im) pair
+    return 2 * zh.element_size();
+  }
+  static constexpr auto& reference = disco_spectral_t_ref;
+  static constexpr auto& run = disco_spectral_t_run;
+};
+AMD_DFT_OP_FAMILY(disco_spectral_t, DiscoSpectralT)
+
+// The tiling disco_spectral_t runs -- host only, no device; from disco_spectral_t_route, which launch_disco_spectral
+// dispatches on: "KD=96 KC=96 chunks=1 MT=8 PTL=16 lds=53760 wgs=8190 table_bytes=199342080"
+std::string disco_spectral_t_info(int64_t planes, int64_t nlat_in, int64_t nlon_in, int64_t K, int64_t nlat_out,
+                                  int64_t nlon_out, int64_t U, bool bf16) {
+  TORCH_CHECK(planes >= 1 && nlat_in >= 1 && nlon_in >= 1 && K >= 1 && nlat_out >= 1 && nlon_out >= 1 && U >= 1 &&
+                  U <= nlat_in && K * U < (1 << 24) && nlon_out < (1 << 28) && nlat_out < (1 << 28) &&
+                  nlon_out % nlon_in == 0,
+              "amd_dft.disco_spectral_t_info: sizes must be >= 1, U <= nlat_in and nlon_out a multiple of nlon_in");
+  const DiscoSpectralRoute r = disco_spectral_t_route(planes, nlat_in, nlon_in, K, nlat_out, nlon_out, U, bf16);
+  return "KD=" + std::to_string(r.KD) + " KC=" + std::to_string(r.KC) + " chunks=" + std::to_string(r.chunks) +
+         " MT=" + std::to_string(r.mt) + " PTL=" + std::to_string(r.ptl) + " lds=" + std::to_string(r.lds) +
+         " wgs=" + std::to_string(r.wgs) + " table_bytes=" + std::to_string(r.table_bytes) + (bf16 ? " bf16=1" : "");
 }
 
 // ------------------------------------------------------------------ DISCO convolution on the sphere (transposed half)
@@ -1885,6 +2038,10 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
                     "-> Tensor")                                                                                      \
   X(disco_spectral_out, "(Tensor xhat, Tensor table, Tensor lo, int K, int U, int nlat_out, int nlon_in, "            \
                         "int nlon_out, Tensor(a!) out) -> Tensor(a!)")                                                \
+  X(disco_spectral_t, "(Tensor zhat, Tensor table, Tensor lo, int K, int U, int nlat_out, int nlon_in, int nlon_out, " \
+                      "Tensor? bias=None) -> Tensor")                                                                 \
+  X(disco_spectral_t_out, "(Tensor zhat, Tensor table, Tensor lo, int K, int U, int nlat_out, int nlon_in, "          \
+                          "int nlon_out, Tensor? bias, Tensor(a!) out) -> Tensor(a!)")                                \
   X(disco_t, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias=None) "     \
              "-> Tensor")                                                                                             \
   X(disco_t_out, "(Tensor z, Tensor row_ptr, Tensor idx, Tensor val, int nlat_out, int nlon_out, Tensor? bias, "      \
@@ -1918,6 +2075,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("disco_spectral_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int U, "
         "bool bf16=False) -> str",
         &amd_dft::disco_spectral_info);
+  m.def("disco_spectral_t_info(int planes, int nlat_in, int nlon_in, int K, int nlat_out, int nlon_out, int U, "
+        "bool bf16=False) -> str",
+        &amd_dft::disco_spectral_t_info);
   m.def("attention_s2_info(int B, int heads, int d, int nlat_in, int nlon_in, int nlat_out, int nlon_out, "
         "bool bf16=False) -> str",
         &amd_dft::attention_s2_info);

@@ -501,6 +501,13 @@ struct DiscoSpectralLaunch {
   int64_t N = 0;
   int nlat_in = 0, nlon_in = 0, K = 0, U = 0, nlat_out = 0, nlon_out = 0;
   int bf16 = 0;
+  // the transposed (upsampling) direction, disco_spectral_t: x is Zh [N, K, nlat_in, Mi, 2] on the coarse grid, y is
+  // Yh [N, nlat_out, Mo, 2] on the fine one, nlon_out a multiple of nlon_in, and
+  //   Yh[n, k, mu] = sum_{p < K} sum_{dk < U} (T[.., 2 j] + i T[.., 2 j + 1]) Zh[n, p, lo[g] + dk, mu mod nlon_in],
+  // j = p U + dk, g = k / 16, the table row k - 16 g; nlon_out * bias[n mod C] is added to Re Yh[n, k, 0].
+  int transposed = 0;
+  const float* bias = nullptr;     // [C] fp32 or null (transposed only)
+  int64_t C = 1;
 };
 // The route of a call (host only; launch_disco_spectral and the disco_spectral_info op both answer from here).  A
 // workgroup of 256 threads owns one group g, MT consecutive output modes (wave w: modes w, w + 4, ...) and PTL planes
@@ -517,6 +524,7 @@ struct DiscoSpectralRoute {
   int G;           // groups: ceil(nlat_out / R)
   int s, Mo;       // nlon_in / nlon_out, nlon_out / 2 + 1
   int KD;          // padded contraction: ceil32(2 s U)
+  int KC, chunks;  // the contraction goes through LDS in `chunks` pieces of KC (the last may be shorter); forward: one
   int mt, ptl;     // modes and planes per workgroup
   int64_t lds;     // dynamic LDS bytes per workgroup
   int64_t wgs;     // G * ceil(Mo / mt) * ceil(planes / ptl)
@@ -539,8 +547,36 @@ inline DiscoSpectralRoute disco_spectral_route(int64_t planes, int64_t /*nlat_in
   r.ptl = 16;
   if (disco_spectral_lds_bytes(r.mt, r.ptl, r.KD, bf16) > kDiscoSpecLdsBytes) r.ptl = 8;
   if (disco_spectral_lds_bytes(r.mt, r.ptl, r.KD, bf16) > kDiscoSpecLdsBytes) r.mt = 4;
+  r.KC = r.KD;
+  r.chunks = 1;
   r.lds = disco_spectral_lds_bytes(r.mt, r.ptl, r.KD, bf16);
   r.ok = K <= 16 && r.lds <= kDiscoSpecLdsBytes;
+  r.wgs = static_cast<int64_t>(r.G) * ((r.Mo + r.mt - 1) / r.mt) * ((planes + r.ptl - 1) / r.ptl);
+  r.table_bytes = (bf16 ? 1LL : 2LL) * r.G * r.Mo * 16 * r.KD * 2;
+  return r;
+}
+// The transposed direction (disco_spectral_t; nlon_out = s nlon_in).  The output has no basis index, so a group is
+// always R = 16 consecutive OUTPUT latitudes, the rows of one MFMA tile, and the K basis planes sit in the
+// contraction: j = p U + dk, KD = ceil32(2 K U), any K >= 1.  KD grows with K U (448 at 180 x 360, (3, 4)), so the
+// tile stays 8 modes x 16 planes and the contraction is walked through LDS in chunks of KC, the largest multiple of
+// 32 whose image fits kDiscoSpecLdsBytes (96 for fp32, 224 for bf16 with the present layout), the accumulators kept
+// in registers: there is no KD limit, ok is always true.
+inline DiscoSpectralRoute disco_spectral_t_route(int64_t planes, int64_t /*nlat_in*/, int64_t nlon_in, int64_t K,
+                                                 int64_t nlat_out, int64_t nlon_out, int64_t U, bool bf16) {
+  DiscoSpectralRoute r{};
+  r.R = 16;
+  r.G = static_cast<int>((nlat_out + 15) / 16);
+  r.s = static_cast<int>(nlon_out / nlon_in);
+  r.Mo = static_cast<int>(nlon_out / 2 + 1);
+  r.KD = static_cast<int>((2 * K * U + 31) / 32 * 32);
+  r.mt = 8;
+  r.ptl = 16;
+  int kc = 32;
+  while (disco_spectral_lds_bytes(r.mt, r.ptl, kc + 32, bf16) <= kDiscoSpecLdsBytes) kc += 32;
+  r.KC = r.KD < kc ? r.KD : kc;
+  r.chunks = (r.KD + r.KC - 1) / r.KC;
+  r.lds = disco_spectral_lds_bytes(r.mt, r.ptl, r.KC, bf16);
+  r.ok = true;
   r.wgs = static_cast<int64_t>(r.G) * ((r.Mo + r.mt - 1) / r.mt) * ((planes + r.ptl - 1) / r.ptl);
   r.table_bytes = (bf16 ? 1LL : 2LL) * r.G * r.Mo * 16 * r.KD * 2;
   return r;

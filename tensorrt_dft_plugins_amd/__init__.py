@@ -15,7 +15,8 @@ from .ops.dft import (  # noqa: F401
 )
 from .ops.attention_s2 import attention_s2, attention_s2_tables  # noqa: F401
 from .ops.disco import (  # noqa: F401
-    disco, disco_spectral, disco_spectral_tables, disco_tables, disco_transpose, disco_transpose_tables,
+    disco, disco_spectral, disco_spectral_tables, disco_spectral_transpose, disco_spectral_transpose_tables,
+    disco_tables, disco_transpose, disco_transpose_tables,
 )
 from .ops.sht import isht, ivsht, sht, vsht  # noqa: F401
 

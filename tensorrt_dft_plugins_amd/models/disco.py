@@ -151,17 +151,23 @@ class DiscreteContinuousConvTransposeS2(nn.Module):
     nlon_out] with ``nlon_out % nlon_in == 0``, fp32 or bf16 on the amd backend.
 
     Backends: ``"amd"``: one ``fno_pointwise`` at the coarse resolution (``Cin -> Cout * K``, no bias), then the
-    ``disco_t`` op, which adds the bias (``csrc/spectral/disco.hip`` on a GPU).  ``"torch"``: the definition, a
+    ``disco_t`` op, which adds the bias (``csrc/spectral/disco.hip`` on a GPU); with ``algorithm="spectral"`` (opt
+    in; ``"gather"`` is the default) the longitude-Fourier route instead: ``r2c``, the ``disco_spectral_t`` op
+    (``csrc/spectral/disco_spectral.hip``), which adds the bias at mode 0, and ``c2r``.  ``"torch"``: the definition, a
     sparse matrix applied once per input longitude shift in eager torch, in the input's precision (fp64 in, fp64
     out; bf16 computed in fp32 and rounded once).  The weight is ``[Cout, Cin, K]``, torch-harmonics' layout
     (``DiscreteContinuousConvTransposeS2``) but not its normalisation: published weights do not carry over."""
 
     def __init__(self, in_chans: int, out_chans: int, in_shape: Tuple[int, int], out_shape: Tuple[int, int],
                  kernel_shape, bias: bool = True, grid_in: str = "equiangular", grid_out: str = "equiangular",
-                 theta_cutoff: Optional[float] = None, normalize: bool = True, backend: str = "amd"):
+                 theta_cutoff: Optional[float] = None, normalize: bool = True, backend: str = "amd",
+                 algorithm: str = "gather"):
         super().__init__()
         if backend not in ("torch", "amd"):
             raise ValueError(f"backend must be 'torch' or 'amd', got {backend!r}")
+        if algorithm not in ("gather", "spectral"):
+            raise ValueError(f"algorithm must be 'gather' or 'spectral', got {algorithm!r}")
+        self.algorithm = algorithm
         self.in_chans, self.out_chans = int(in_chans), int(out_chans)
         self.in_shape = tuple(int(v) for v in in_shape)
         self.out_shape = tuple(int(v) for v in out_shape)
@@ -196,6 +202,10 @@ class DiscreteContinuousConvTransposeS2(nn.Module):
     def tables(self, device) -> "D._DiscoTransposeTables":
         return D.disco_transpose_table_holder(self.in_shape, self.out_shape, self.kernel_shape, self.grid_in,
                                               self.grid_out, self.theta_cutoff, self.normalize, device)
+
+    def spectral_tables(self, device) -> "D._DiscoSpectralTransposeTables":
+        return D.disco_spectral_transpose_table_holder(self.in_shape, self.out_shape, self.kernel_shape, self.grid_in,
+                                                       self.grid_out, self.theta_cutoff, self.normalize, device)
 
     # ---- torch backend: the definition
     def _psi(self, ref: torch.Tensor) -> torch.Tensor:
@@ -252,7 +262,10 @@ class DiscreteContinuousConvTransposeS2(nn.Module):
         Hi, Wi = self.in_shape
         w, b = self._flat_weight()
         z = torch.ops.amd_dft.fno_pointwise(None, x, w, None, False)  # [B, Cout K, Hi, Wi]
-        return D.disco_transpose(z.view(B, self.out_chans, self.K, Hi, Wi), self.tables(x.device), b)
+        z = z.view(B, self.out_chans, self.K, Hi, Wi)
+        if self.algorithm == "spectral":
+            return D.disco_spectral_transpose(z, self.spectral_tables(x.device), b)
+        return D.disco_transpose(z, self.tables(x.device), b)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 4 or x.shape[1] != self.in_chans or tuple(x.shape[2:]) != self.in_shape:

@@ -62,6 +62,22 @@ Packed table (``disco_spectral_tables``): output latitudes in groups of R consec
 with R K <= 16, the last group ragged with zero rows); group g touches the input latitudes lo[g] .. hi[g], U the
 tallest such band; ``T[g, m', row, kappa]`` with row = (k' - g R) K + p < 16 and kappa = 2 (r U + k - lo[g]) + c holding
 Re G / s (c = 0) and Im G / s (c = 1) at mu = m' + r nlon_out, zero-padded to KD = ceil32(2 s U).
+
+The longitude-Fourier route of the transposed convolution (``disco_spectral_transpose``, the ``disco_spectral_t`` op,
+the same kernel template; opt in).  y is the circular convolution of PsiT[p, k', k, .] with z upsampled by zeros, and
+the DFT of a zero-upsampled signal is the periodic extension of the coarse spectrum, so with s = nlon_out / nlon_in:
+
+* Z[p, k', nu] the unnormalised ``r2c`` of z, stored for nu < Mi, Z[nu] = conj(Z[nlon_in - nu]) above;
+* H[p, k', k, mu] = sum_D PsiT[p, k', k, D] e^{-2 pi i mu D / nlon_out} (a convolution: no conjugate); the CSR entry
+  of row k s + rho with idx = (k' K + p) nlon_in + d sits at D = s ((nlon_in - d) mod nlon_in) + rho;
+* Yh[k, mu] = sum_{p, k'} H[p, k', k, mu] Z[p, k', mu mod nlon_in], 0 <= mu < Mo: no fold and no 1 / s, each coarse
+  mode feeds up to s fine modes; the bias adds nlon_out bias[c] to Re Yh[k, 0];
+* y[k, :] = irfft(Yh[k, :], n = nlon_out), backward norm.
+
+Packed table (``disco_spectral_transpose_tables``): groups of 16 consecutive OUTPUT latitudes (the output has no
+basis index; the K basis planes sit in the contraction, so any K works), group g reads the coarse latitudes
+lo[g] .. lo[g] + U - 1; ``T[g, mu, k - 16 g, kappa]`` with kappa = 2 (p U + k' - lo[g]) + c holding Re H (c = 0) and
+Im H (c = 1), zero-padded to KD = ceil32(2 K U).
 """
 from __future__ import annotations
 
@@ -76,7 +92,8 @@ from .sht import GRIDS, colatitudes
 
 __all__ = ["disco_tables", "disco_table_holder", "disco", "kernel_size", "default_cutoff", "disco_transpose_tables",
            "disco_csr_transpose", "disco_transpose_table_holder", "disco_transpose", "disco_spectral_tables",
-           "disco_spectral_table_holder", "disco_spectral", "disco_spectral_group"]
+           "disco_spectral_table_holder", "disco_spectral", "disco_spectral_group", "disco_spectral_transpose_tables",
+           "disco_spectral_transpose_table_holder", "disco_spectral_transpose"]
 
 KernelShape = Union[int, Sequence[int]]
 
@@ -475,6 +492,97 @@ def disco_transpose(z: torch.Tensor, tables: _DiscoTransposeTables, bias: Option
     if z.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"disco_transpose: z must be float32 or bfloat16, got {z.dtype}")
     return _ops().disco_t(z, tables.row_ptr, tables.idx, tables.val, tables.nlat_out, tables.nlon_out, bias)
+
+
+def disco_spectral_transpose_tables(in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel_shape: KernelShape,
+                                    grid_in: str = "equiangular", grid_out: str = "equiangular",
+                                    theta_cutoff: Optional[float] = None, normalize: bool = True, dtype=np.float32):
+    """The packed table of the transposed longitude-Fourier route, built in float64 numpy from the CSR of
+    ``disco_transpose_tables``, one group of 16 output latitudes at a time (the dense PsiT of the whole grid is never
+    held).
+
+    Returns ``(T [G, Mo, 16, KD] of dtype, lo int32 [G], U)``: the layout of the module docstring.  The per-phase
+    normalisation is in the CSR's values already and T carries nothing else: 1 / nlon_out is the ``scale`` of the one
+    ``c2r`` call that finishes the job (``disco_spectral_transpose``).  A group without entries has lo = 0 and an
+    all-zero table.  Raises like ``disco_transpose_tables``; any K >= 1."""
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("disco_spectral_transpose_tables: dtype must be np.float32 or np.float64")
+    rp, idx, val = disco_transpose_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize,
+                                          dtype=np.float64)
+    nlon_in = int(in_shape[1])
+    nlat_out, nlon_out = (int(v) for v in out_shape)
+    K = kernel_size(kernel_shape)
+    G, s, Mo = -(-nlat_out // 16), nlon_out // nlon_in, nlon_out // 2 + 1
+    rp, idx = rp.astype(np.int64), idx.astype(np.int64)
+    erow = np.repeat(np.arange(len(rp) - 1, dtype=np.int64), np.diff(rp))  # k s + rho of every entry
+    q, d = idx // nlon_in, idx % nlon_in
+    kin, p = q // K, q % K
+    big_d = s * ((nlon_in - d) % nlon_in) + erow % s  # D, the relative longitude on the fine grid
+    spans = [slice(rp[16 * g * s], rp[min(16 * g + 16, nlat_out) * s]) for g in range(G)]
+    lo = np.zeros(G, dtype=np.int32)
+    U = 1
+    for g, e in enumerate(spans):
+        if e.stop > e.start:
+            lo[g] = kin[e].min()
+            U = max(U, int(kin[e].max()) - int(lo[g]) + 1)
+    KD = -(-2 * K * U // 32) * 32
+    T = np.zeros((G, Mo, 16, KD), dtype=dtype)
+    for g, e in enumerate(spans):
+        psi = np.zeros((16, K * U, nlon_out))
+        psi[erow[e] // s - 16 * g, p[e] * U + kin[e] - lo[g], big_d[e]] = val[e]
+        H = np.fft.rfft(psi, axis=-1).transpose(2, 0, 1)  # [Mo, 16, j = p U + dk]
+        T[g, :, :, 0:2 * K * U:2] = H.real
+        T[g, :, :, 1:2 * K * U:2] = H.imag
+    return T, lo, U
+
+
+class _DiscoSpectralTransposeTables:
+    """The packed transposed table on one device as ``disco_spectral_t`` takes it: ``table`` bf16 [2, G, Mo, 16, KD],
+    the fp32 values split once, on the host, into the planes hi = bf16(T) and lo = bf16(T - hi) (``table_bf16``: the
+    hi plane alone, [1, G, Mo, 16, KD], what a bf16 call takes), ``lo`` int32 [G], and K, U, KD, s, Mo,
+    ``table_bytes``."""
+
+    def __init__(self, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
+        T, lo, U = disco_spectral_transpose_tables(in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff,
+                                                   normalize)
+        self.K, self.U, self.KD = kernel_size(kernel_shape), int(U), int(T.shape[-1])
+        self.nlat_out, self.nlon_out = int(out_shape[0]), int(out_shape[1])
+        self.nlat_in, self.nlon_in = int(in_shape[0]), int(in_shape[1])
+        self.s, self.Mo = self.nlon_out // self.nlon_in, self.nlon_out // 2 + 1
+        t32 = torch.from_numpy(T)
+        hi = t32.to(torch.bfloat16)
+        self.table = torch.stack([hi, (t32 - hi.float()).to(torch.bfloat16)]).to(device)
+        self.table_bf16 = self.table[:1]
+        self.table_bytes = self.table.numel() * 2
+        self.lo = torch.from_numpy(lo).to(device)
+
+
+def disco_spectral_transpose_table_holder(in_shape, out_shape, kernel_shape, grid_in: str = "equiangular",
+                                          grid_out: str = "equiangular", theta_cutoff: Optional[float] = None,
+                                          normalize: bool = True, device="cpu") -> _DiscoSpectralTransposeTables:
+    """The transposed spectral tables cached per (grids, basis, cutoff, normalize, device), like
+    ``disco_spectral_table_holder``."""
+    return _cached(_DiscoSpectralTransposeTables, ("spectral_t",), in_shape, out_shape, kernel_shape, grid_in, grid_out,
+                   theta_cutoff, normalize, device)
+
+
+def disco_spectral_transpose(z: torch.Tensor, tables: _DiscoSpectralTransposeTables,
+                             bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``z`` [..., C, K, nlat_in, nlon_in] (fp32 or bf16) -> y [..., C, nlat_out, nlon_out] of the same dtype, plus
+    ``bias`` [C] (fp32): the shape and meaning of ``disco_transpose(z, tables, bias)`` by the longitude-Fourier
+    route: ``r2c`` along longitude (all modes), the ``disco_spectral_t`` op (which adds the bias, at mode 0), ``c2r``
+    to nlon_out with scale 1 / nlon_out."""
+    if z.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"disco_spectral_transpose: z must be float32 or bfloat16, got {z.dtype}")
+    if z.dim() < 4 or tuple(z.shape[-3:]) != (tables.K, tables.nlat_in, tables.nlon_in):
+        raise ValueError(f"disco_spectral_transpose: z must be [..., C, {tables.K}, {tables.nlat_in}, "
+                         f"{tables.nlon_in}], got {tuple(z.shape)}")
+    ops = _ops()
+    zh = ops.r2c(z, [z.dim() - 1], 1.0, [], z.dtype)  # [..., C, K, nlat_in, Mi, 2]
+    table = tables.table_bf16 if z.dtype == torch.bfloat16 else tables.table
+    yh = ops.disco_spectral_t(zh, table, tables.lo, tables.K, tables.U, tables.nlat_out, tables.nlon_in,
+                              tables.nlon_out, bias)
+    return ops.c2r(yh, [yh.dim() - 2], [tables.nlon_out], 1.0 / tables.nlon_out, [], z.dtype)
 
 
 def disco(x: torch.Tensor, tables: _DiscoTables) -> torch.Tensor:
