@@ -24,7 +24,7 @@ namespace amd_dft {
 namespace {
 
 // The families with an `_out` op (afno_mlp, fno_mix, fno_pointwise, fno_c2r_pw, legendre, legendre_vec, disco,
-// disco_spectral, disco_spectral_t, attention_s2, sfno_mix, instance_norm) are described once each, in a struct after their check,
+// disco_spectral, disco_spectral_t, attention_s2, attention_s2_global, sfno_mix, instance_norm) are described once each, in a struct after their check,
 // reference and launch path; op_family.h makes the six backend forms of the description.
 
 // ------------------------------------------------------------------ AFNO spectral filter
@@ -1515,6 +1515,132 @@ std::string attention_s2_info(int64_t B, int64_t heads, int64_t d, int64_t nlat_
          (bf16 ? " bf16=1" : "");
 }
 
+// ------------------------------------------------------------------ global attention on the sphere
+// q [B, heads * d, nlat_out, nlon_out], k and v [B, heads * d, nlat_in, nlon_in], logw [nlat_in] -> y as q:
+//   y[b, h, :, k', j'] = sum_{all (k, j)} softmax(scale sum_c q[b, h, c, k', j'] k[b, h, c, k, j] + logw[k]) v[b, h, :, k, j]
+// over every input point; any two grids.  Dtypes as attention_s2.  The CPU kernel is the plain definition in fp64,
+// rounded once.
+void check_attention_s2_global(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                               const at::Tensor& logw, int64_t heads, double) {
+  const auto qt = q.scalar_type();
+  TORCH_CHECK(qt == at::kFloat || qt == at::kBFloat16 || (qt == at::kDouble && q.device().is_cpu()), op,
+              ": q must be float32 or bfloat16 (float64 on CPU tensors), got ", qt);
+  TORCH_CHECK(k.scalar_type() == qt && v.scalar_type() == qt, op, ": q, k and v must share one dtype, got ", qt, ", ",
+              k.scalar_type(), " and ", v.scalar_type());
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && k.sizes() == v.sizes() && q.size(0) == k.size(0) &&
+                  q.size(1) == k.size(1),
+              op, ": q must be [B, C, nlat_out, nlon_out] and k, v [B, C, nlat_in, nlon_in], got ", q.sizes(), ", ",
+              k.sizes(), " and ", v.sizes());
+  TORCH_CHECK(heads >= 1 && q.size(1) >= 1 && q.size(1) % heads == 0, op, ": the ", q.size(1),
+              " channels must be a positive multiple of heads = ", heads);
+  const int64_t nlat_in = k.size(2), nlon_in = k.size(3), nlat_out = q.size(2), nlon_out = q.size(3);
+  TORCH_CHECK(nlat_in >= 1 && nlon_in >= 1 && nlat_out >= 1 && nlon_out >= 1 &&
+                  nlat_in * nlon_in < (int64_t(1) << 31) && nlat_out * nlon_out < (int64_t(1) << 31),
+              op, ": the grids must be non-empty and hold fewer than 2^31 points");
+  TORCH_CHECK((logw.scalar_type() == at::kFloat || (logw.scalar_type() == at::kDouble && qt == at::kDouble)) &&
+                  logw.dim() == 1 && logw.size(0) == nlat_in,
+              op, ": logw must be float32 [nlat_in] (float64 allowed next to float64 q), got ", logw.scalar_type(), " ",
+              logw.sizes());
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device() && logw.device() == q.device(), op,
+              ": k, v and logw must be on the device of q");
+}
+
+at::Tensor attention_s2_global_ref(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                   const at::Tensor& logw, int64_t heads, double scale) {
+  const int64_t B = q.size(0), d = q.size(1) / heads, Wi = k.size(3), pin = k.size(2) * Wi,
+                pout = q.size(2) * q.size(3);
+  const at::Tensor qd = q.to(at::kDouble).contiguous(), kd = k.to(at::kDouble).contiguous(),
+                   vd = v.to(at::kDouble).contiguous(), ld = logw.to(at::kDouble).contiguous();
+  at::Tensor y = at::zeros(q.sizes(), qd.options());
+  const double *qp = qd.data_ptr<double>(), *kp = kd.data_ptr<double>(), *vp = vd.data_ptr<double>(),
+               *lp = ld.data_ptr<double>();
+  double* yp = y.data_ptr<double>();
+  at::parallel_for(0, B * heads * pout, 16, [&](int64_t b0, int64_t b1) {
+    std::vector<double> sc(pin);
+    for (int64_t t = b0; t < b1; ++t) {
+      const int64_t bh = t / pout, jo = t % pout;
+      const double *qb = qp + bh * d * pout + jo, *kb = kp + bh * d * pin, *vb = vp + bh * d * pin;
+      double mx = -std::numeric_limits<double>::infinity(), den = 0.0;
+      for (int64_t j = 0; j < pin; ++j) {
+        double sum = 0.0;
+        for (int64_t c = 0; c < d; ++c) sum += qb[c * pout] * kb[c * pin + j];
+        sc[j] = scale * sum + lp[j / Wi];
+        mx = std::max(mx, sc[j]);
+      }
+      for (double& e : sc) den += (e = std::exp(e - mx));
+      for (int64_t c = 0; c < d; ++c) {
+        double sum = 0.0;
+        for (int64_t j = 0; j < pin; ++j) sum += sc[j] * vb[c * pin + j];
+        yp[bh * d * pout + c * pout + jo] = sum / den;
+      }
+    }
+  });
+  return y.to(q.scalar_type());
+}
+
+void attention_s2_global_run(const at::Tensor& q_, const at::Tensor& k_, const at::Tensor& v_,
+                             const at::Tensor& logw_, int64_t heads, double scale, const at::Tensor& y) {
+  if (y.numel() == 0) return;
+  const at::Tensor q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous();  // element loads
+  const at::Tensor logw = logw_.contiguous();
+  AttnS2GlobalLaunch p;
+  p.q = q.data_ptr();
+  p.k = k.data_ptr();
+  p.v = v.data_ptr();
+  p.logw = logw.data_ptr<float>();
+  p.y = y.data_ptr();
+  p.B = q.size(0);
+  p.heads = heads;
+  p.d = q.size(1) / heads;
+  p.nlat_in = static_cast<int>(k.size(2));
+  p.nlon_in = static_cast<int>(k.size(3));
+  p.nlat_out = static_cast<int>(q.size(2));
+  p.nlon_out = static_cast<int>(q.size(3));
+  p.scale = static_cast<float>(scale);
+  p.bf16 = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+  launch_attention_s2_global(p, current_stream(q));
+}
+
+void check_attention_s2_global_device(const char* op, const at::Tensor& q, const at::Tensor&, const at::Tensor&,
+                                      const at::Tensor&, int64_t heads, double) {
+  TORCH_CHECK(q.size(1) / heads <= kAttnS2GMaxD, op, ": the head dimension d = C / heads must be at most ",
+              kAttnS2GMaxD, " on the device (the kernel's eight output row tiles), got ", q.size(1) / heads);
+}
+
+struct AttentionS2Global : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, double);
+  static constexpr const char *name = "attention_s2_global", *out_name = "attention_s2_global_out";
+  static constexpr auto& check = check_attention_s2_global;
+  static constexpr auto& check_device = check_attention_s2_global_device;
+  static OpResult result(const at::Tensor& q, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t,
+                         double) {
+    return {q.sizes(), q.options()};
+  }
+  template <class... A>
+  static uintptr_t out_align(const at::Tensor& q, const A&...) {  // element stores
+    return q.element_size();
+  }
+  static constexpr auto& reference = attention_s2_global_ref;
+  static constexpr auto& run = attention_s2_global_run;
+};
+AMD_DFT_OP_FAMILY(attention_s2_global, AttentionS2Global)
+
+// Which instance and grid attention_s2_global runs -- host only, no device; from attention_s2_global_route, which
+// launch_attention_s2_global dispatches on: "DP=64 qwave=32 qwg=128 chunk=64 lds=37376 bufs=2 qtiles=32 wgs=128
+// threads=256".
+std::string attention_s2_global_info(int64_t B, int64_t heads, int64_t d, int64_t nlat_in, int64_t nlon_in,
+                                     int64_t nlat_out, int64_t nlon_out, bool bf16) {
+  TORCH_CHECK(B >= 1 && heads >= 1 && nlat_in >= 1 && nlon_in >= 1 && nlat_out >= 1 && nlon_out >= 1,
+              "amd_dft.attention_s2_global_info: sizes must be >= 1");
+  TORCH_CHECK(d >= 1 && d <= kAttnS2GMaxD, "amd_dft.attention_s2_global_info: the head dimension must be 1 .. ",
+              kAttnS2GMaxD);
+  const AttnS2GlobalRoute r = attention_s2_global_route(B, heads, d, nlat_in, nlon_in, nlat_out, nlon_out, bf16);
+  return "DP=" + std::to_string(r.dp) + " qwave=" + std::to_string(r.qw) + " qwg=" + std::to_string(r.qwg) +
+         " chunk=" + std::to_string(kAttnS2GChunk) + " lds=" + std::to_string(r.lds) +
+         " bufs=" + std::to_string(r.nbuf) + " qtiles=" + std::to_string(r.qtiles) +
+         " wgs=" + std::to_string(r.wgs) + " threads=" + std::to_string(kAttnS2GThreads) + (bf16 ? " bf16=1" : "");
+}
+
 // ------------------------------------------------------------------ SFNO per-degree channel mixing
 // c [B, Cin, L, M, 2] fp32 (spherical harmonic coefficients, complex as trailing re/im), w [Cin, Cout, L, 2] fp32
 // -> y [B, Cout, L, M, 2] fp32:   y[b, o, l, m] = sum_i c[b, i, l, m] w[i, o, l]   (complex)
@@ -2049,6 +2175,9 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
   X(attention_s2, "(Tensor q, Tensor k, Tensor v, Tensor hw, Tensor logw, int heads, float scale) -> Tensor")         \
   X(attention_s2_out, "(Tensor q, Tensor k, Tensor v, Tensor hw, Tensor logw, int heads, float scale, Tensor(a!) out) " \
                       "-> Tensor(a!)")                                                                                \
+  X(attention_s2_global, "(Tensor q, Tensor k, Tensor v, Tensor logw, int heads, float scale) -> Tensor")            \
+  X(attention_s2_global_out, "(Tensor q, Tensor k, Tensor v, Tensor logw, int heads, float scale, Tensor(a!) out) "   \
+                             "-> Tensor(a!)")                                                                         \
   X(sfno_mix, "(Tensor c, Tensor w, Tensor? w_split=None, int tri=0) -> Tensor")                                      \
   X(sfno_mix_out, "(Tensor c, Tensor w, Tensor? w_split, int tri, Tensor(a!) out) -> Tensor(a!)")
 
@@ -2081,6 +2210,9 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("attention_s2_info(int B, int heads, int d, int nlat_in, int nlon_in, int nlat_out, int nlon_out, "
         "bool bf16=False) -> str",
         &amd_dft::attention_s2_info);
+  m.def("attention_s2_global_info(int B, int heads, int d, int nlat_in, int nlon_in, int nlat_out, int nlon_out, "
+        "bool bf16=False) -> str",
+        &amd_dft::attention_s2_global_info);
   m.def("sfno_mix_split(Tensor w) -> Tensor", &amd_dft::sfno_mix_split);
   m.def("sfno_mix_info(int B, int Cin, int Cout, int L, int M, int tri, bool bf16=False) -> str",
         &amd_dft::sfno_mix_info);

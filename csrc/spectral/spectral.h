@@ -625,6 +625,55 @@ inline AttnS2Route attention_s2_route(int64_t B, int64_t heads, int64_t d, int64
 }
 void launch_attention_s2(const AttnS2Launch& p, void* stream);
 
+// ---- Global attention on the sphere (attention_s2_global.hip): quadrature-weighted softmax attention of every output
+// point over ALL input points, any two grids (no hw table, no divisibility rule):
+//   y[b, h, :, k', j'] = sum_{all (k, j)} softmax(scale q.k + logw[k]) v[b, h, :, k, j]
+struct AttnS2GlobalLaunch {
+  const void* q = nullptr;        // [B, heads * d, nlat_out, nlon_out] fp32 (bf16 if bf16)
+  const void* k = nullptr;        // [B, heads * d, nlat_in, nlon_in]
+  const void* v = nullptr;        // [B, heads * d, nlat_in, nlon_in]
+  const float* logw = nullptr;    // [nlat_in]
+  void* y = nullptr;              // [B, heads * d, nlat_out, nlon_out], q's dtype
+  int64_t B = 0, heads = 0, d = 0;
+  int nlat_in = 0, nlon_in = 0, nlat_out = 0, nlon_out = 0;
+  float scale = 1.f;
+  int bf16 = 0;
+};
+// The route of a call (host only; launch_attention_s2_global and the attention_s2_global_info op answer from here).
+// The grids are flat: Nq = nlat_out * nlon_out queries, Nk = nlat_in * nlon_in keys.  A workgroup of kAttnS2GThreads
+// owns one (b, head) and qwg = 4 qw consecutive queries, qw per wave: 32 (two MFMA column tiles, every K and V
+// fragment read from LDS feeds both), 16 for fp32 at dp = 128 (registers).  The keys go through LDS in chunks of
+// kAttnS2GChunk, in nbuf = 2 buffers (1 for fp32 at dp = 128); a buffer holds K [chunk][dp + 8] and V [dp][chunk + 8]
+// bf16 (fp32: three planes of each: hi, lo, rest) and the chunk's bias row, kAttnS2GChunk floats.
+constexpr int kAttnS2GThreads = 256;
+constexpr int kAttnS2GChunk = 64;
+constexpr int kAttnS2GMaxD = 128;
+constexpr int64_t kAttnS2GLdsMax = 160 * 1024;
+struct AttnS2GlobalRoute {
+  int dp;          // 32, 64 or 128
+  int qw;          // queries per wave: 16 or 32
+  int qwg;         // queries per workgroup: 4 qw
+  int nbuf;        // LDS buffers of one key chunk each
+  int64_t lds;     // dynamic LDS bytes per workgroup
+  int64_t qtiles;  // query tiles per (b, head)
+  int64_t wgs;     // B * heads * qtiles
+};
+inline AttnS2GlobalRoute attention_s2_global_route(int64_t B, int64_t heads, int64_t d, int64_t /*nlat_in*/,
+                                                   int64_t /*nlon_in*/, int64_t nlat_out, int64_t nlon_out,
+                                                   bool bf16) {
+  AttnS2GlobalRoute r{};
+  r.dp = d <= 32 ? 32 : d <= 64 ? 64 : 128;
+  r.qw = !bf16 && r.dp == 128 ? 16 : 32;
+  r.qwg = 4 * r.qw;
+  r.nbuf = !bf16 && r.dp == 128 ? 1 : 2;
+  r.lds = r.nbuf * ((bf16 ? 1 : 3) * 2 * (int64_t(kAttnS2GChunk) * (r.dp + 8) + int64_t(r.dp) * (kAttnS2GChunk + 8)) +
+                    int64_t(kAttnS2GChunk) * 4);
+  r.qtiles = (nlat_out * nlon_out + r.qwg - 1) / r.qwg;
+  r.wgs = B * heads * r.qtiles;
+  return r;
+}
+void launch_attention_s2_global(const AttnS2GlobalLaunch& p, void* stream);
+
 // ---- AFNO W-direction transforms with LayerNorm fused into the IO (afno_wfft.hip)
 struct AfnoWLaunch {
   const void* x = nullptr;        // [O, L, C] bf16 (fp32 if f32) stored residual stream

@@ -13,7 +13,9 @@ from ._loader import (  # noqa: F401
 from .ops.dft import (  # noqa: F401
     contrib_irfft, contrib_rfft, fft, fftn, ifft, ifftn, irfft, irfft2, irfftn, rfft, rfft2, rfftn,
 )
-from .ops.attention_s2 import attention_s2, attention_s2_tables  # noqa: F401
+from .ops.attention_s2 import (  # noqa: F401
+    attention_s2, attention_s2_global, attention_s2_global_tables, attention_s2_tables,
+)
 from .ops.disco import (  # noqa: F401
     disco, disco_spectral, disco_spectral_tables, disco_spectral_transpose, disco_spectral_transpose_tables,
     disco_tables, disco_transpose, disco_transpose_tables,

@@ -1,4 +1,5 @@
-"""Neighbourhood attention on the sphere: the half-width table and the ``attention_s2`` op.
+"""Attention on the sphere: neighbourhood attention (the half-width table and the ``attention_s2`` op) and global
+attention (``attention_s2_global``, at the end of this module).
 
 Attention of every output point over the input points within a geodesic cutoff, weighted by the quadrature of the
 input grid: the ``NeighborhoodAttentionS2`` layer of spherical transformers and of the attention variants of
@@ -36,7 +37,8 @@ from .._loader import load_plugins
 from .disco import _cached, default_cutoff
 from .sht import GRIDS, colatitudes
 
-__all__ = ["attention_s2_tables", "attention_s2_table_holder", "attention_s2"]
+__all__ = ["attention_s2_tables", "attention_s2_table_holder", "attention_s2", "attention_s2_global_tables",
+           "attention_s2_global_table_holder", "attention_s2_global"]
 
 
 def _ops():
@@ -112,3 +114,58 @@ def attention_s2(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tables: _Att
         scale = float(q.shape[1] // heads) ** -0.5
     logw = tables.logw64 if q.dtype == torch.float64 else tables.logw
     return _ops().attention_s2(q, k, v, tables.hw, logw, heads, float(scale))
+
+
+# ---- global attention: every output point over ALL input points, any two grids
+#     score(k, j) = scale sum_c q[b, h, c, k', j'] k[b, h, c, k, j] + logw[k]
+#     y[b, h, :, k', j'] = sum_{all (k, j)} softmax(score)(k, j) v[b, h, :, k, j]
+# The only table is logw[k] = log w_k of the input grid; the output grid enters through q's shape alone.
+
+
+def attention_s2_global_tables(in_shape: Tuple[int, int], grid_in: str = "equiangular", dtype=np.float32):
+    """``logw [nlat_in]`` = log of the quadrature weights of the input grid (:func:`.sht.colatitudes`), built in
+    float64 numpy and rounded to ``dtype``.  Raises ``ValueError`` for a grid outside ``GRIDS`` or an empty shape."""
+    nlat_in, nlon_in = (int(v) for v in in_shape)
+    if grid_in not in GRIDS:
+        raise ValueError(f"grid must be one of {GRIDS}, got {grid_in!r}")
+    if nlat_in < 1 or nlon_in < 1:
+        raise ValueError(f"in_shape must be positive, got {tuple(in_shape)}")
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("attention_s2_global_tables: dtype must be np.float32 or np.float64")
+    return np.log(colatitudes(nlat_in, grid_in)[1]).astype(dtype)
+
+
+class _AttentionS2GlobalTables:
+    """``logw`` (fp32) of one input grid on one device as the op takes it, and ``logw64`` for float64 CPU tensors."""
+
+    def __init__(self, in_shape, out_shape, kernel_shape, grid_in, grid_out, theta_cutoff, normalize, device):
+        self.in_shape = tuple(int(v) for v in in_shape)
+        self.logw64 = torch.from_numpy(attention_s2_global_tables(in_shape, grid_in, dtype=np.float64)).to(device)
+        self.logw = self.logw64.float()
+
+
+def attention_s2_global_table_holder(in_shape, grid_in: str = "equiangular",
+                                     device="cpu") -> _AttentionS2GlobalTables:
+    """The table cached per (input grid, device) in the cache of ``disco_table_holder``."""
+    return _cached(_AttentionS2GlobalTables, ("attn_global",), in_shape, in_shape, 1, grid_in, grid_in, None, True,
+                   device)
+
+
+def attention_s2_global(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tables: _AttentionS2GlobalTables,
+                        scale: Optional[float] = None, heads: int = 1) -> torch.Tensor:
+    """``q`` [B, heads * d, nlat_out, nlon_out], ``k`` and ``v`` [B, heads * d, nlat_in, nlon_in], all fp32 or all
+    bf16 (fp64 on CPU tensors) -> y as q: the ``attention_s2_global`` op (the dense MFMA kernel on a GPU, d <= 128;
+    the plain C++ definition on CPU tensors).  ``scale`` defaults to d ** -0.5.  Mixed dtypes raise ``TypeError``."""
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError(f"attention_s2_global: q, k and v must share one dtype, got {q.dtype}, {k.dtype} and "
+                        f"{v.dtype}")
+    if q.dtype not in (torch.float32, torch.bfloat16) and not (q.dtype == torch.float64 and q.device.type == "cpu"):
+        raise TypeError(f"attention_s2_global: q must be float32 or bfloat16 (float64 on CPU tensors), got {q.dtype}")
+    heads = int(heads)
+    if heads < 1 or q.dim() != 4 or q.shape[1] % heads:
+        raise ValueError(f"attention_s2_global: q must be [B, heads * d, nlat_out, nlon_out], got {tuple(q.shape)} "
+                         f"with heads = {heads}")
+    if scale is None:
+        scale = float(q.shape[1] // heads) ** -0.5
+    logw = tables.logw64 if q.dtype == torch.float64 else tables.logw
+    return _ops().attention_s2_global(q, k, v, logw, heads, float(scale))
