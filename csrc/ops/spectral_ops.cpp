@@ -24,7 +24,7 @@ namespace amd_dft {
 namespace {
 
 // The families with an `_out` op (afno_mlp, fno_mix, fno_pointwise, fno_c2r_pw, legendre, legendre_vec, disco,
-// disco_spectral, disco_spectral_t, attention_s2, attention_s2_global, sfno_mix, instance_norm) are described once each, in a struct after their check,
+// disco_spectral, disco_spectral_t, attention_s2, attention_s2_global, sfno_mix, instance_norm, layer_norm_nchw) are described once each, in a struct after their check,
 // reference and launch path; op_family.h makes the six backend forms of the description.
 
 // ------------------------------------------------------------------ AFNO spectral filter
@@ -299,9 +299,17 @@ at::Tensor fno_pointwise_ref(const c10::optional<at::Tensor>& spec, const at::Te
   return y.reshape(shape).to(x.scalar_type());
 }
 
-// the launch path of fno_pointwise and fno_pointwise_out: y is the contiguous [B, Cout, ...] result in x's dtype
-void fno_pointwise_run(const c10::optional<at::Tensor>& spec_, const at::Tensor& x_, const at::Tensor& w,
-                       const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
+// LayerNorm over x's channels in front of the convolution (fno_pointwise_ln)
+struct PwLayerNorm {
+  c10::optional<at::Tensor> gamma, beta;
+  double eps;
+};
+
+// the launch path of fno_pointwise, fno_pointwise_out and fno_pointwise_ln: y is the contiguous [B, Cout, ...] result
+// in x's dtype
+void fno_pointwise_launch(const c10::optional<at::Tensor>& spec_, const at::Tensor& x_, const at::Tensor& w,
+                          const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y,
+                          const PwLayerNorm* ln) {
   TORCH_CHECK(x_.dim() >= 2, "fno_pointwise: x [B, Cin, ...]");
   TORCH_CHECK(x_.scalar_type() == at::kFloat || x_.scalar_type() == at::kBFloat16,
               "fno_pointwise: x must be float32 or bfloat16");
@@ -332,7 +340,19 @@ void fno_pointwise_run(const c10::optional<at::Tensor>& spec_, const at::Tensor&
   p.P = static_cast<int>(P);
   p.bf16 = x.scalar_type() == at::kBFloat16;
   p.gelu = gelu;
+  at::Tensor lw, lb;
+  if (ln != nullptr) {
+    lw = f32_or_undef(ln->gamma), lb = f32_or_undef(ln->beta);
+    p.ln = 1;
+    p.ln_w = lw.defined() ? lw.data_ptr<float>() : nullptr;
+    p.ln_b = lb.defined() ? lb.data_ptr<float>() : nullptr;
+    p.ln_eps = static_cast<float>(ln->eps);
+  }
   launch_fno_pointwise(p, current_stream(x));
+}
+void fno_pointwise_run(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const at::Tensor& w,
+                       const c10::optional<at::Tensor>& bias, bool gelu, const at::Tensor& y) {
+  fno_pointwise_launch(spec, x, w, bias, gelu, y, nullptr);
 }
 
 // no check beyond result's (the reference and the launch path make their own) and no out_align: out starts at any
@@ -362,6 +382,143 @@ std::string fno_pointwise_info(int64_t cin, int64_t cout, bool bf16, int64_t P) 
   if (!r.mfma) return "fixed cin=" + std::to_string(cin) + " vp=" + std::to_string(r.vp);
   return "mfma slabs=" + std::to_string(r.slabs) + " otiles=" + std::to_string(r.otiles) +
          " groups=" + std::to_string(r.groups) + " x3=" + std::to_string(r.x3 ? 1 : 0) + " vp=" + std::to_string(r.vp);
+}
+
+// ------------------------------------------------------------------ LayerNorm over channels (NCHW)
+// x [B, C, *spatial] fp32 / bf16, weight / bias [C] (fp32 or x's dtype, either may be absent):
+//   y = (x - mean) * rsqrt(var + eps) * weight[c] + bias[c], mean and biased variance over the C channels of each
+// (b, pixel) -- nn.LayerNorm(C) on the channel dimension without the permutes.  The result has x's dtype.
+void check_ln_nchw(const char* op, const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                   const c10::optional<at::Tensor>& b) {
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, op,
+              ": x must be float32 or bfloat16, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 2, op, ": x must be [B, C, *spatial], got ", x.sizes());
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C >= 1 && C < (int64_t(1) << 24), op, ": bad channel count ", C);
+  auto per_channel = [&](const c10::optional<at::Tensor>& t, const char* name) {
+    if (!present(t)) return;
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == C, op, ": ", name, " must be [C] = [", C, "], got ", t->sizes());
+    TORCH_CHECK(t->scalar_type() == at::kFloat || t->scalar_type() == x.scalar_type(), op, ": ", name,
+                " must be float32 or ", x.scalar_type(), ", got ", t->scalar_type());
+    TORCH_CHECK(t->device() == x.device(), op, ": ", name, " must be on the device of x");
+  };
+  per_channel(w, "weight");
+  per_channel(b, "bias");
+}
+
+// fp64 ATen math on the fp32 / bf16 values, not yet rounded: [B, C, P]
+at::Tensor ln_nchw_f64(const at::Tensor& x, const c10::optional<at::Tensor>& w, const c10::optional<at::Tensor>& b,
+                       double eps) {
+  const int64_t C = x.size(1);
+  at::Tensor xd = x.to(at::kDouble).reshape({x.size(0), C, -1});
+  at::Tensor xc = xd - xd.mean({1}, /*keepdim=*/true);
+  at::Tensor y = xc * at::rsqrt((xc * xc).mean({1}, /*keepdim=*/true) + eps);
+  if (present(w)) y = y * w->to(at::kDouble).reshape({1, C, 1});
+  if (present(b)) y = y + b->to(at::kDouble).reshape({1, C, 1});
+  return y;
+}
+
+at::Tensor layer_norm_nchw_ref(const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                               const c10::optional<at::Tensor>& b, double eps) {
+  if (x.numel() == 0) return at::empty_like(x, at::MemoryFormat::Contiguous);
+  return ln_nchw_f64(x, w, b, eps).reshape(x.sizes()).to(x.scalar_type());
+}
+
+// the launch path: y contiguous, x's dtype, any element alignment (the route falls to per-element I/O)
+void layer_norm_nchw_run(const at::Tensor& x_, const c10::optional<at::Tensor>& w, const c10::optional<at::Tensor>& b,
+                         double eps, const at::Tensor& y) {
+  if (x_.numel() == 0) return;
+  at::Tensor x = x_.contiguous();
+  at::Tensor wf = f32_or_undef(w), bf = f32_or_undef(b);
+  LayerNormNchwLaunch p;
+  p.x = x.data_ptr();
+  p.y = y.data_ptr();
+  p.w = wf.defined() ? wf.data_ptr<float>() : nullptr;
+  p.b = bf.defined() ? bf.data_ptr<float>() : nullptr;
+  p.B = x.size(0);
+  p.C = static_cast<int>(x.size(1));
+  p.P = x.numel() / (p.B * p.C);
+  TORCH_CHECK(p.P < (int64_t(1) << 31) - 1024, "layer_norm_nchw: more than 2^31 - 1024 elements per channel row");
+  p.eps = static_cast<float>(eps);
+  p.bf16 = x.scalar_type() == at::kBFloat16 ? 1 : 0;
+  launch_layer_norm_nchw(p, current_stream(x));
+}
+
+struct LayerNormNchw : OpFamily {
+  using Sig = at::Tensor(const at::Tensor&, const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, double);
+  static constexpr const char *name = "layer_norm_nchw", *out_name = "layer_norm_nchw_out";
+  static void check(const char* op, const at::Tensor& x, const c10::optional<at::Tensor>& w,
+                    const c10::optional<at::Tensor>& b, double) {
+    check_ln_nchw(op, x, w, b);
+  }
+  template <class... A>
+  static OpResult result(const at::Tensor& x, const A&...) {
+    return {x.sizes(), x.options()};
+  }
+  static constexpr auto& reference = layer_norm_nchw_ref;
+  static constexpr auto& run = layer_norm_nchw_run;
+};
+AMD_DFT_OP_FAMILY(layer_norm_nchw, LayerNormNchw)
+
+// The route layer_norm_nchw runs for x [B, C, P] on 16-byte-aligned tensors -- host only, no device (the companion
+// of instance_norm_info): "route=resident TP=256 vec=4 lds=8192 wgs=254" or "route=reread(L2) TP=...".  TP: pixels
+// per workgroup; vec: elements per load and store; lds: bytes of the waves' partial moments.  reread(L2): the
+// normalise pass reads the workgroup's tile a second time, C rows of TP elements it has just touched.
+std::string layer_norm_nchw_info(int64_t B, int64_t C, int64_t P, bool bf16) {
+  TORCH_CHECK(B >= 1 && C >= 1 && P >= 1 && P < (int64_t(1) << 31) - 1024,
+              "amd_dft.layer_norm_nchw_info: B, C, P must be >= 1 and P < 2^31 - 1024");
+  const LayerNormNchwRoute r = layer_norm_nchw_route(B, C, P, bf16);
+  return std::string("route=") + (r.resident ? "resident" : "reread(L2)") + " TP=" + std::to_string(r.TP) +
+         " vec=" + std::to_string(r.vec ? r.V : 1) + " lds=" + std::to_string(r.lds) + " wgs=" + std::to_string(r.wgs);
+}
+
+// ------------------------------------------------------------------ 1x1 convolution of a LayerNorm, one kernel
+// y = act(spec + W LN(x) + b), LN over x's channels as layer_norm_nchw; LN(x) is never stored.
+void check_pw_ln(const c10::optional<at::Tensor>& spec, const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
+                 const c10::optional<at::Tensor>& beta, const at::Tensor& w) {
+  check_ln_nchw("fno_pointwise_ln", x, gamma, beta);
+  TORCH_CHECK(w.dim() >= 2 && w.numel() == w.size(0) * x.size(1), "fno_pointwise_ln: weight must be [Cout, Cin]");
+  TORCH_CHECK(!present(spec) || spec->scalar_type() == x.scalar_type(), "fno_pointwise_ln: spec must have x's dtype ",
+              x.scalar_type());
+}
+std::vector<int64_t> pw_ln_shape(const at::Tensor& x, const at::Tensor& w) {
+  std::vector<int64_t> shape = x.sizes().vec();
+  shape[1] = w.size(0);
+  return shape;
+}
+
+at::Tensor fno_pointwise_ln_cpu(const c10::optional<at::Tensor>& spec, const at::Tensor& x,
+                                const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta, double eps,
+                                const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool gelu) {
+  check_pw_ln(spec, x, gamma, beta, w);
+  const int64_t B = x.size(0), Cin = x.size(1), Cout = w.size(0);
+  if (x.numel() == 0) return at::empty(pw_ln_shape(x, w), x.options());
+  at::Tensor y = at::einsum("oi,bip->bop", {w.reshape({Cout, Cin}).to(at::kDouble), ln_nchw_f64(x, gamma, beta, eps)});
+  if (present(bias)) y = y + bias->to(at::kDouble).reshape({1, -1, 1});
+  if (present(spec)) {
+    TORCH_CHECK(spec->numel() == y.numel(), "fno_pointwise_ln: spec must be [B, Cout, ...] like the output");
+    y = y + spec->to(at::kDouble).reshape({B, Cout, -1});
+  }
+  if (gelu) y = at::gelu(y);
+  return y.reshape(pw_ln_shape(x, w)).to(x.scalar_type());
+}
+
+at::Tensor fno_pointwise_ln_cuda(const c10::optional<at::Tensor>& spec, const at::Tensor& x,
+                                 const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta,
+                                 double eps, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool gelu) {
+  check_pw_ln(spec, x, gamma, beta, w);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor y = at::empty(pw_ln_shape(x, w), x.options());
+  const PwLayerNorm ln{gamma, beta, eps};
+  fno_pointwise_launch(spec, x, w, bias, gelu, y, &ln);
+  return checked(y, "fno_pointwise_ln");
+}
+
+at::Tensor fno_pointwise_ln_meta(const c10::optional<at::Tensor>&, const at::Tensor& x, const c10::optional<at::Tensor>&,
+                                 const c10::optional<at::Tensor>&, double, const at::Tensor& w,
+                                 const c10::optional<at::Tensor>&, bool) {
+  TORCH_CHECK(x.dim() >= 2 && w.dim() >= 1, "fno_pointwise_ln: x [B, Cin, ...], w [Cout, Cin]");
+  return at::empty(pw_ln_shape(x, w), x.options());
 }
 
 // ------------------------------------------------------------------ FNO layer tail (C2R-W + pointwise)
@@ -2147,6 +2304,10 @@ at::Tensor afno_spectral_meta(const at::Tensor& xw, const at::Tensor&, const at:
   X(instance_norm_stats, "(Tensor x, float eps=1e-5) -> Tensor")                                                      \
   X(fno_mix, "(Tensor x, Tensor w, int path=0) -> Tensor")                                                            \
   X(fno_mix_out, "(Tensor x, Tensor w, int path, Tensor(a!) out) -> Tensor(a!)")                                      \
+  X(layer_norm_nchw, "(Tensor x, Tensor? weight=None, Tensor? bias=None, float eps=1e-5) -> Tensor")                  \
+  X(layer_norm_nchw_out, "(Tensor x, Tensor? weight, Tensor? bias, float eps, Tensor(a!) out) -> Tensor(a!)")         \
+  X(fno_pointwise_ln, "(Tensor? spec, Tensor x, Tensor? gamma, Tensor? beta, float eps, Tensor w, Tensor? b, "        \
+                      "bool gelu) -> Tensor")                                                                         \
   X(fno_pointwise, "(Tensor? spec, Tensor x, Tensor w, Tensor? bias=None, bool gelu=True) -> Tensor")                 \
   X(fno_pointwise_out, "(Tensor? spec, Tensor x, Tensor w, Tensor? bias, bool gelu, Tensor(a!) out) -> Tensor(a!)")   \
   X(fno_c2r_pw, "(Tensor yw, Tensor x, Tensor wc, Tensor? bias=None, bool gelu=True) -> Tensor")                      \
@@ -2189,6 +2350,7 @@ TORCH_LIBRARY_FRAGMENT(amd_dft, m) {
   m.def("afno_mlp_info(int block_size, bool split, int tokens) -> str", &amd_dft::afno_mlp_info);
   m.def("ln_info(str op, int C, bool bf16) -> str", &amd_dft::ln_info);
   m.def("instance_norm_info(int planes, int P, bool bf16) -> str", &amd_dft::instance_norm_info);
+  m.def("layer_norm_nchw_info(int B, int C, int P, bool bf16) -> str", &amd_dft::layer_norm_nchw_info);
   m.def("fno_mix_info(int B, int Cin, int Cout, int M, bool bf16=False, int path=0) -> str", &amd_dft::fno_mix_info);
   m.def("fno_pointwise_info(int cin, int cout, bool bf16, int P) -> str", &amd_dft::fno_pointwise_info);
   m.def("fno_c2r_pw_info(int cin, int cout, int m, int W, bool bf16) -> str", &amd_dft::fno_c2r_pw_info);

@@ -145,6 +145,8 @@ void launch_fno_pointwise(const FnoPointwiseLaunch& p, void* stream) {
   const uintptr_t al = 4 * (p.bf16 ? 2 : 4) - 1;
   const bool aligned = !((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.y) |
                           reinterpret_cast<uintptr_t>(p.spec)) & al);
+  // fno_pointwise_ln: the MFMA kernel at every Cin, the seven fixed counts included
+  if (p.ln) return launch_fno_pointwise_mfma(p, aligned && p.P % 4 == 0, stream);
   const FnoPointwiseRoute r = fno_pointwise_route(p.Cin, p.Cout, p.bf16 != 0, p.P, aligned);
   if (r.mfma) return launch_fno_pointwise_mfma(p, r.vp == 4, stream);
   const bool vec = r.vp == 4;

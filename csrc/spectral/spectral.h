@@ -173,6 +173,12 @@ struct FnoPointwiseLaunch {
   void* y;             // [B, Cout, P]
   int B, Cin, Cout, P;
   int bf16 = 0, gelu = 1;
+  // fno_pointwise_ln (the MFMA kernel only): x is replaced by its LayerNorm over the Cin channels of each pixel,
+  // (x - mean) * rsqrt(var + eps) * ln_w[i] + ln_b[i], applied as the slab is written to LDS
+  int ln = 0;
+  const float* ln_w = nullptr;  // [Cin] fp32 or nullptr (1)
+  const float* ln_b = nullptr;  // [Cin] fp32 or nullptr (0)
+  float ln_eps = 1e-5f;
 };
 // the register-resident instances of fno_pointwise.hip
 inline bool fno_pointwise_fixed(int cin) {
@@ -425,6 +431,49 @@ inline InstanceNormRoute instance_norm_route(int64_t planes, int64_t P, bool bf1
   return r;
 }
 void launch_instance_norm(const InstanceNormLaunch& p, void* stream);
+
+// ---- LayerNorm over the channels of an NCHW tensor (layer_norm_nchw.hip):
+//   y[b, c, p] = (x[b, c, p] - mean[b, p]) * rsqrt(var[b, p] + eps) * w[c] + b[c],  biased variance over the C channels
+struct LayerNormNchwLaunch {
+  const void* x = nullptr;   // [B, C, P] fp32 (bf16 if bf16), contiguous, any element alignment
+  void* y = nullptr;         // same shape
+  const float* w = nullptr;  // [C] fp32 or nullptr (1)
+  const float* b = nullptr;  // [C] fp32 or nullptr (0)
+  int64_t B = 0, P = 0;
+  int C = 1;
+  float eps = 1e-5f;
+  int bf16 = 0;
+};
+// The route of a call (host only; launch_layer_norm_nchw and the layer_norm_nchw_info op both answer from here).
+// A lane owns V consecutive pixels, a 256-thread workgroup a tile of TP = 64 V pixels of one batch entry, its four
+// waves the channels round-robin.  V starts at 4 and halves while the grid would have fewer than kLnNchwFillWgs
+// workgroups.  (128, half the CUs: with 256 a 180 x 360 field, 254 tiles, fell to V = 2 and measured 7 % slower at
+// 256 channels in both dtypes, the same at 64.)  resident: a wave's channels, at most
+// kLnNchwResident of them, stay in registers between the moment pass and the normalise pass (32 channels x 4 pixels
+// = 128 VGPRs of the 512 a one-wave-per-SIMD workgroup may hold; both dtypes, the registers hold fp32); reread: more
+// channels, the tile is read a second time.  align: the power of two (bytes, up to 16) x and y both start on.
+constexpr int kLnNchwResident = 32;  // channels per wave on the resident route: C <= 128
+constexpr int64_t kLnNchwFillWgs = 128;
+struct LayerNormNchwRoute {
+  bool resident;
+  int V;        // pixels per lane
+  int TP;       // pixels per workgroup, 64 V
+  bool vec;     // V-element vector loads and stores (else per element)
+  int64_t lds;  // static LDS bytes per workgroup: the waves' (mean, M2) partials
+  int64_t wgs;  // workgroups: B * ceil(P / TP)
+};
+inline LayerNormNchwRoute layer_norm_nchw_route(int64_t B, int64_t C, int64_t P, bool bf16, int align = 16) {
+  LayerNormNchwRoute r{};
+  r.resident = C <= 4 * kLnNchwResident;
+  r.V = 4;
+  while (r.V > 1 && B * ((P + 64 * r.V - 1) / (64 * r.V)) < kLnNchwFillWgs) r.V /= 2;
+  r.TP = 64 * r.V;
+  r.vec = r.V > 1 && P % r.V == 0 && align % (r.V * (bf16 ? 2 : 4)) == 0;
+  r.lds = 4LL * 2 * r.TP * 4;
+  r.wgs = B * ((P + r.TP - 1) / r.TP);
+  return r;
+}
+void launch_layer_norm_nchw(const LayerNormNchwLaunch& p, void* stream);
 
 // ---- Discrete-continuous (DISCO) convolutions on the sphere, both directions (disco.hip).  Forward, the gather half:
 //   y[n, p, k', j'] = sum_e val[e] * x[n, k_e, (d_e + s j') mod nlon_in],  e over CSR row p * nlat_out + k',

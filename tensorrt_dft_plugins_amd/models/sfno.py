@@ -401,8 +401,9 @@ class SFNONet(nn.Module):
     ``instance_norm``, the bf16 spherical line and the bf16 ``fno_pointwise``.  ``pos`` cast to the input's dtype and
     expanded over the batch is cached on the module per dtype and batch size.
 
-    Out of scope: resolution changes between blocks (``scale_factor``), LayerNorm over NCHW, and weight-for-weight
-    compatibility with any published checkpoint."""
+    Out of scope: resolution changes between blocks (``scale_factor``), LayerNorm over NCHW inside this network
+    (``models.ChannelLayerNorm`` and ``models.PreNormMLP`` are there for users who build their own blocks), and
+    weight-for-weight compatibility with any published checkpoint."""
 
     def __init__(self, cfg: Optional[SFNOConfig] = None, backend: str = "amd"):
         super().__init__()

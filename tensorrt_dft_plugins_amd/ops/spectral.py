@@ -30,6 +30,7 @@ from .._loader import load_plugins
 from . import dft as D
 
 __all__ = ["pack_afno_weights", "afno_fused_available", "afno_spectral_h", "c2r_w_add", "layer_norm", "instance_norm",
+           "layer_norm_nchw", "fno_pointwise_ln",
            "afno_mlp_available", "afno_mlp_block_size_ok", "afno_spectral_mlp", "afno_block_mlp_hand",
            "afno_block_amd", "afno_block_fused", "afno_block_fused_f32",
            "afno_block_spectral", "afno_block_mlp", "fno_spectral_mix", "sfno_mix", "sfno_mix_split", "split_bf16", "module_cached",
@@ -193,6 +194,27 @@ def instance_norm(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: 
     and one write; larger planes are cut into chunks whose (count, mean, M2) partials are merged in a fixed order,
     two reads and one write; ``torch.ops.amd_dft.instance_norm_info`` names the route)."""
     return _ops().instance_norm(x, weight, bias, float(eps))
+
+
+def layer_norm_nchw(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                    eps: float = 1e-5) -> torch.Tensor:
+    """LayerNorm of x [B, C, *spatial] (fp32 or bf16) over the channels of each (b, pixel):
+    ``(x - mean) * rsqrt(var + eps) * weight[c] + bias[c]`` with the biased variance over ``c`` -- ``nn.LayerNorm(C)``
+    on the channel dimension without the two permutes.  ``weight`` / ``bias``: [C], fp32 or x's dtype, either may be
+    absent.  fp32 statistics and arithmetic, the result in x's dtype.  Native op on every device (CPU: ATen in fp64;
+    GPU: csrc/spectral/layer_norm_nchw.hip -- up to 128 channels stay in registers between the moment pass and the
+    normalise pass, more are read twice; ``torch.ops.amd_dft.layer_norm_nchw_info`` names the route)."""
+    return _ops().layer_norm_nchw(x, weight, bias, float(eps))
+
+
+def fno_pointwise_ln(spec: Optional[torch.Tensor], x: torch.Tensor, gamma: Optional[torch.Tensor],
+                     beta: Optional[torch.Tensor], eps: float, w: torch.Tensor, b: Optional[torch.Tensor] = None,
+                     gelu: bool = True) -> torch.Tensor:
+    """``act(spec + W LN(x) + b)`` in one kernel: the 1x1 convolution ``w`` [Cout, Cin] of the LayerNorm of
+    x [B, Cin, *spatial] over its channels (``gamma`` / ``beta`` [Cin] or absent), plus the optional addend ``spec``
+    [B, Cout, *spatial] and bias, then erf-GELU if ``gelu``.  The normalised tensor is never stored: the MFMA kernel
+    of ``fno_pointwise`` normalises each slab as it stages it (every ``Cin``, csrc/spectral/fno_pointwise_mfma.hip)."""
+    return _ops().fno_pointwise_ln(spec, x, gamma, beta, float(eps), w, b, bool(gelu))
 
 
 def _gelu_linear(y2: torch.Tensor, fc: torch.nn.Linear) -> torch.Tensor:
